@@ -20,6 +20,11 @@ Hangs end loudly: the process group and the collective watchdog (parallel/watchd
 the warm-up (``--warmup-timeout``) and every timed step (``--step-timeout``): on expiry every
 thread's stack goes to stderr and the process exits non-zero.
 
+A plain run does only what its headline figure needs: set up, warm up, time the K steps, write
+``--dump-outputs DIR`` if asked (the last timed step's loss and logits as ``.npy``, from seeded
+initial weights and inputs) and print the one JSON line, whose ``ms_per_step``
+is the wall time of one timed step.  ``--full`` is where anything beyond that runs.
+
 ``--impl dtf``   (default) this framework: hand-written HIP kernels, MirroredStrategy.
 ``--impl torch`` the stock PyTorch-ROCm comparator (MIOpen convs, DDP) on the same data.
 """
@@ -76,6 +81,19 @@ def parse():
     p.add_argument("--dump-master", default=None,
                    help="after the timed steps, save the (rank-0) fp32 master weights to this "
                         "file (tests compare the forced-reducer run bit for bit with the plain one)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed step returned to its "
+                        "caller as DIR/<name>.npy (float32, rank 0): the loss and, for ResNet-50, "
+                        "the logits it was computed from (an array past 4M elements as a fixed "
+                        "seeded sample of 4M).  Initial weights and inputs are seeded, so two "
+                        "builds run with the same arguments can be compared output for output")
+    p.add_argument("--full", action="store_true",
+                   help="also run whatever the bench measures beyond its headline figure.  A "
+                        "plain run sets up, warms up, times --steps steps and prints the result "
+                        "line, and today nothing else exists: comparators, other models and "
+                        "strategies are selected by their own options (--impl, --model, "
+                        "--strategy) and the per-kernel benches live in tools/.  Anything extra "
+                        "added to this file belongs behind this option")
     p.add_argument("--model", choices=("resnet50", "bert_base"), default="resnet50",
                    help="resnet50: the headline metric; bert_base: BASELINE config 5 "
                         "(MLM, LAMB, MultiWorkerMirroredStrategy) in tokens/sec")
@@ -246,10 +264,33 @@ def build_dtf(args, dev):
         logits = model(images)
         loss = ops.sparse_softmax_cross_entropy(logits, labels)
         opt.minimize(loss, global_step=gstep)
+        step.logits = logits.detach()  # --dump-outputs: the last step's (a view, no graph kept)
         return loss
 
     step.optimizer = opt
     return step, strategy
+
+
+DUMP_SAMPLE = 4 << 20   # --dump-outputs: elements kept of an array larger than this (16 MB fp32)
+
+
+def dump_outputs(path, loss, logits):
+    """--dump-outputs: what the last timed step handed its caller, as ``<name>.npy`` (float32):
+    the loss and, where the step exposes them, the logits it was computed from.  An array of more
+    than DUMP_SAMPLE elements is written as the same seeded sample of its flattened elements in
+    every run (ascending indices from ``numpy.random.default_rng(1234)``).  The updated weights
+    are state, not a result: ``--dump-master`` saves those."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1)}
+    if logits is not None:
+        arrays["logits"] = logits.detach()
+    for name, t in arrays.items():
+        a = t.float().cpu().numpy()
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(1234).choice(a.size, DUMP_SAMPLE, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def build_bert(args, dev):
@@ -480,6 +521,9 @@ def main():
     args = parse()
     refuse_probes()
     if args.strategy == "ps_async":
+        if args.dump_outputs:
+            fail("--dump-outputs is not available with --strategy ps_async (Hogwild updates are "
+                 "not reproducible run to run)")
         from distributedtensorflow_amd.utils import ps_bench
         if args.job_name:
             return ps_bench.run_task(args)
@@ -629,6 +673,8 @@ def main():
         opt_for_stats.synchronize_variables()
         if rank == 0:
             torch.save(opt_for_stats.space.master.detach().cpu(), args.dump_master)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, getattr(step, "logits", None))
     ranks_info = None
     if dist.is_initialized() and dist.get_world_size() > 1:
         ranks_info = rank_diagnostics(elapsed, args.steps, comm_info, reducer, dev, rccl_log)

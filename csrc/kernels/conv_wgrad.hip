@@ -1171,8 +1171,13 @@ conv_wgrad_stem_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ 
   for (; s < nstrip; s += G, ++it) {
     DTF_WAIT_VM(0);            // this strip's DMAs (own) landed ...
     // FZ: form this strip's dY in its stage (last read two trips ago, before the previous
-    // trip's barrier)
-    if constexpr (FZ) zform(s, lds + (it & 1) * (kStStage / 2));
+    // trip's barrier).  A thread forms pixels whose x rows OTHER waves DMA'd, so everyone's
+    // DMAs must have landed first: without this barrier a late DMA overwrote formed dY with
+    // raw x (garbage stem gradients, different every run, once a block walks many strips)
+    if constexpr (FZ) {
+      __syncthreads();
+      zform(s, lds + (it & 1) * (kStStage / 2));
+    }
     __syncthreads();           // ... everyone's; everyone finished reading the other stage
     if constexpr (FZ) zload(s + G);
     issue(s + G, (it + 1) & 1);

@@ -91,6 +91,39 @@ def test_dtf_env_recorded(monkeypatch):
     assert dtf_env() == {"DTF_GEMM_STREAM": "0"}
 
 
+def test_dump_outputs_files_and_fixed_sample(monkeypatch, tmp_path):
+    """--dump-outputs: float32 .npy files; an array past DUMP_SAMPLE elements is written as the
+    same seeded sample every time; --full and --dump-outputs parse, both off by default."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path)])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == str(tmp_path)
+
+    logits = torch.arange(12, dtype=torch.float32).reshape(3, 4).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "s"), torch.tensor(2.5), logits)
+    out = {n: np.load(tmp_path / "s" / f"{n}.npy") for n in ("loss", "logits")}
+    assert all(v.dtype == np.float32 for v in out.values())
+    assert out["loss"].tolist() == [2.5]
+    assert np.array_equal(out["logits"], logits.float().numpy())
+    bench.dump_outputs(str(tmp_path / "n"), torch.tensor(1.0), None)
+    assert sorted(os.listdir(tmp_path / "n")) == ["loss.npy"]
+
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    big = torch.arange(5000, dtype=torch.float32).reshape(50, 100)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(2.5), big)
+    w = np.load(tmp_path / "a" / "logits.npy")
+    assert w.dtype == np.float32 and w.shape == (1000,)
+    assert np.all(np.diff(w) > 0) and w.min() >= 0 and w.max() < 5000
+    assert np.array_equal(w, np.load(tmp_path / "b" / "logits.npy"))
+
+
 def test_bucket_size_auto_by_default_at_n_gt_1(monkeypatch):
     sys.path.insert(0, ROOT)
     import bench

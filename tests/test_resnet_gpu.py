@@ -771,14 +771,16 @@ def test_wgrad_stem_kernel_vs_fp32(n, acc):
     torch.testing.assert_close(outs[0], outs[1], rtol=1e-4, atol=1e-3)
 
 
-@pytest.mark.parametrize("n", [2, 5])
+@pytest.mark.parametrize("n", [2, 5, 24])
 def test_stem_wgrad_forms_pool_bn_backward_on_load_bit_identical(n):
     """The stem's BN + ReLU + max-pool backward apply folded into the stem weight gradient
     (conv_wgrad_stem_kernel<true>: d(stem conv output) formed per strip from the pooled gradient,
     argmax bytes and BN input, never stored) against the apply pass + the strip wgrad kernel:
     the conv weight gradient and BN gamma / beta gradients bit for bit; n = 5 leaves the last
-    blocks' second strip past the batch.  The lazy record must be consumed (the apply pass not
-    run) on the fused arm."""
+    blocks' second strip past the batch; n = 24 has every block walk 5-6 strips, so each LDS
+    stage is re-formed while other waves' DMAs for it are in flight (the forming pass must wait
+    for all of them).  The lazy record must be consumed (the apply pass not run) on the fused
+    arm."""
     torch.manual_seed(0)
     m = resnet50().cuda()
     x = torch.randn(n, 224, 224, 3, device="cuda").bfloat16()
