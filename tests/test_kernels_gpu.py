@@ -4,6 +4,8 @@ Shapes cover the reference's MNIST CNN and ResNet-50's 
 geometries (N-K1..N-K5) at reduced batch.  Inputs are asymmetric random data (never symmetric
 operands: a transposed MFMA C-write would pass a symmetric test — guide §3).
 """
+import contextlib
+
 import pytest
 import torch
 
@@ -174,33 +176,189 @@ def test_conv_element_gather_paths(case):
     # many rows / ragged unroll tails / a channel count that does not divide the block
     (64, True, True, (3, 37, 41)), (96, True, True, (2, 13, 17)), (128, True, False, (5, 29, 31))])
 def test_batch_norm(C, relu, res, shape):
+    _bn_check(_bn_case(C, relu, res, shape))
+
+
+def _bn_case(C, relu, res, shape, integer=False):
+    """Inputs of one BatchNorm case and its fp32 reference (computed once, shared by every knob
+    setting).  ``integer``: x in [-3, 3] and an integer dy, so that every per-channel sum of x,
+    x^2 and dz is an integer below 2^24 -- exact in fp32 in any summation order."""
     torch.manual_seed(1)
-    x = (torch.randn(*shape, C, device=dev) * 2 + 0.5).to(torch.bfloat16)
+    if integer:
+        x = torch.randint(-3, 4, (*shape, C), device=dev).to(torch.bfloat16)
+    else:
+        x = (torch.randn(*shape, C, device=dev) * 2 + 0.5).to(torch.bfloat16)
     r = torch.randn_like(x) if res else None
     gamma = torch.rand(C, device=dev) + 0.5
     beta = torch.randn(C, device=dev)
     rm1, rv1 = torch.zeros(C, device=dev), torch.ones(C, device=dev)
-    rm2, rv2 = rm1.clone(), rv1.clone()
-    nat, ref = _native(), _ref()
     xr = x.float().requires_grad_(True)
     gr, br = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
     rr = r.float().requires_grad_(True) if res else None
-    yr = ref.batch_norm(xr, gr, br, rm1, rv1, True, 0.9, 1e-5, relu, rr)
-    dy = torch.randn_like(yr)
+    yr = _ref().batch_norm(xr, gr, br, rm1, rv1, True, 0.9, 1e-5, relu, rr)
+    dy = torch.randint(-3, 4, yr.shape, device=dev).float() if integer else torch.randn_like(yr)
     yr.backward(dy)
+    return dict(C=C, relu=relu, x=x, r=r, gamma=gamma, beta=beta, dy=dy, yr=yr.detach(),
+                rm1=rm1, rv1=rv1, dx=xr.grad, dgamma=gr.grad, dbeta=br.grad,
+                dres=rr.grad if res else None)
+
+
+def _bn_check(case):
+    """The native BatchNorm forward and backward against the fp32 reference of ``case``; returns
+    the native outputs."""
+    C, x, r = case["C"], case["x"], case["r"]
+    rm2, rv2 = torch.zeros(C, device=dev), torch.ones(C, device=dev)
     xn = x.clone().requires_grad_(True)
-    gn, bn = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
-    rn = r.clone().requires_grad_(True) if res else None
-    yn = nat.batch_norm(xn, gn, bn, rm2, rv2, True, 0.9, 1e-5, relu, rn)
-    assert _rel(yn, yr) < 1e-2
-    assert torch.allclose(rm1, rm2, atol=1e-4, rtol=1e-4)
-    assert torch.allclose(rv1, rv2, atol=1e-3, rtol=1e-3)
-    yn.backward(dy.to(torch.bfloat16))
-    assert _rel(xn.grad, xr.grad) < 2e-2
-    assert _rel(gn.grad, gr.grad) < 1e-2
-    assert _rel(bn.grad, br.grad) < 1e-2
-    if res:
-        assert _rel(rn.grad, rr.grad) < 1e-2
+    gn = case["gamma"].clone().requires_grad_(True)
+    bn = case["beta"].clone().requires_grad_(True)
+    rn = r.clone().requires_grad_(True) if r is not None else None
+    yn = _native().batch_norm(xn, gn, bn, rm2, rv2, True, 0.9, 1e-5, case["relu"], rn)
+    assert _rel(yn, case["yr"]) < 1e-2
+    assert torch.allclose(case["rm1"], rm2, atol=1e-4, rtol=1e-4)
+    assert torch.allclose(case["rv1"], rv2, atol=1e-3, rtol=1e-3)
+    yn.backward(case["dy"].to(torch.bfloat16))
+    assert _rel(xn.grad, case["dx"]) < 2e-2
+    assert _rel(gn.grad, case["dgamma"]) < 1e-2
+    assert _rel(bn.grad, case["dbeta"]) < 1e-2
+    if r is not None:
+        assert _rel(rn.grad, case["dres"]) < 1e-2
+    return dict(y=yn.detach(), rm=rm2, rv=rv2, dx=xn.grad, dgamma=gn.grad, dbeta=bn.grad,
+                dres=rn.grad if r is not None else None)
+
+
+@contextlib.contextmanager
+def _bn_knobs(stats_blocks, grid_cap):
+    """Target block count of the statistics / reduce passes and grid cap of the apply sweeps
+    (0: the default); tiny values give every block the many trips of the benchmark shapes."""
+    K = _native()._K
+    K.bn_set_stats_blocks(stats_blocks)
+    K.bn_set_grid_cap(grid_cap)
+    try:
+        yield
+    finally:
+        K.bn_set_stats_blocks(0)
+        K.bn_set_grid_cap(0)
+
+
+def _same(a, b, keys):
+    for k in keys:
+        if a[k] is not None or b[k] is not None:
+            assert torch.equal(a[k], b[k]), k
+
+
+# rows per block iteration rpi = 256 / (C / 8); one trip of a block covers 4 * rpi rows
+BN_TRIP_SHAPES = [
+    (64, (3, 37, 41)),      # M 4551, rpi 32: 36 / 12 / 6 reduce trips at 1 / 3 / 7 blocks
+    (96, (2, 13, 17)),      # M 442, rpi 21, four idle threads: 6 / 2 / 1 trips, ragged tails
+    (2048, (4, 7, 9)),      # M 252, rpi 1: 63 / 21 / 9 trips
+    (8, (3, 37, 41)),       # M 4551, rpi 256: 5 / 2 / 1 trips
+]
+# ReLU mask kinds of the backward: none (0), the forward's bit mask (1), recomputed from x (2).
+# Kind 3 (from the saved y) has no caller left in ops/: every entry passes y = 0.
+BN_TRIP_VARIANTS = [(False, False), (True, True), (True, False), (False, True)]
+BN_KNOBS = [(0, 0), (1, 1), (3, 2), (7, 3)]
+
+
+@pytest.mark.parametrize("relu,res", BN_TRIP_VARIANTS)
+@pytest.mark.parametrize("C,shape", BN_TRIP_SHAPES)
+def test_batch_norm_many_trips(C, shape, relu, res):
+    """test_batch_norm's checks with the reduce passes forced to 1, 3 and 7 blocks and the apply
+    sweeps capped at 1, 2 and 3 blocks: every block walks its loop several times, with ragged
+    unroll tails, as at the benchmark's M (at the defaults a block makes one trip here)."""
+    case = _bn_case(C, relu, res, shape)
+    for sb, cap in BN_KNOBS:
+        with _bn_knobs(sb, cap):
+            _bn_check(case)
+
+
+@pytest.mark.parametrize("relu,res", [(True, False), (True, True), (False, False)])
+@pytest.mark.parametrize("C,shape", BN_TRIP_SHAPES)
+def test_batch_norm_exact_sums_any_block_count(C, shape, relu, res):
+    """Integer-valued x and dy: the per-channel sums of x, x^2 and dz are exact whatever the
+    block count, so the mean and variance (through the running statistics), y and dbeta must not
+    change by a bit between 1024, 1, 3 and 7 target blocks."""
+    case = _bn_case(C, relu, res, shape, integer=True)
+    outs = []
+    for sb in (0, 1, 3, 7):
+        with _bn_knobs(sb, 0):
+            outs.append(_bn_check(case))
+    for o in outs[1:]:
+        _same(outs[0], o, ("y", "rm", "rv", "dbeta"))
+    want = case["dy"].double() * ((outs[0]["y"] > 0) if relu else 1)
+    assert torch.equal(outs[0]["dbeta"].double(), want.reshape(-1, C).sum(0))
+
+
+@pytest.mark.parametrize("relu,res", BN_TRIP_VARIANTS)
+@pytest.mark.parametrize("C,shape", BN_TRIP_SHAPES)
+def test_batch_norm_grid_cap_bit_identical(C, shape, relu, res):
+    """The apply sweeps are elementwise given the coefficients: capping their grid (the reduce
+    grid left alone) must not change y, dx or the residual gradient -- which also pins the ReLU
+    bit mask the capped forward wrote -- by a bit."""
+    case = _bn_case(C, relu, res, shape)
+    base = _bn_check(case)
+    for cap in (1, 2, 3):
+        with _bn_knobs(0, cap):
+            _same(base, _bn_check(case), ("y", "rm", "rv", "dx", "dres", "dgamma", "dbeta"))
+
+
+def _dual_bn_case(C, shape):
+    g = torch.Generator(device=dev).manual_seed(3)
+    x = (torch.randn(*shape, C, device=dev, generator=g) * 2 + 1).bfloat16()
+    xp = (torch.randn(*shape, C, device=dev, generator=g) - 0.5).bfloat16()
+    params = [torch.rand(C, device=dev, generator=g) + 0.5, torch.randn(C, device=dev, generator=g),
+              torch.rand(C, device=dev, generator=g) + 0.5, torch.randn(C, device=dev, generator=g)]
+    dy = torch.randn(*shape, C, device=dev, generator=g).bfloat16()
+    return x, xp, params, dy
+
+
+def _dual_bn_check(case):
+    """relu(bn(x) + bn(xp)) in one apply / one reduce / one backward apply pass against the fp32
+    formula with batch statistics (the thresholds of test_batch_norm_add_batch_norm_vs_fp32)."""
+    x0, xp0, params0, dy = case
+    C = x0.shape[-1]
+    x, xp = x0.clone().requires_grad_(), xp0.clone().requires_grad_()
+    params = [t.clone().requires_grad_() for t in params0]
+    rm, rv, rmp, rvp = (torch.zeros(C, device=dev), torch.ones(C, device=dev),
+                        torch.zeros(C, device=dev), torch.ones(C, device=dev))
+    y = _native().batch_norm_add_batch_norm(x, params[0], params[1], rm, rv, xp, params[2],
+                                            params[3], rmp, rvp, True, 0.9, 1e-5)
+    y.backward(dy)
+    red = tuple(range(x0.dim() - 1))
+
+    def bn(t, ga, be):
+        t = t.float()
+        mu = t.mean(red)
+        var = t.var(red, unbiased=False)
+        return (t - mu) / torch.sqrt(var + 1e-5) * ga + be
+
+    xr, xpr = x0.float().requires_grad_(), xp0.float().requires_grad_()
+    rp = [t.clone().requires_grad_() for t in params0]
+    # the ReLU mask of the native (bf16-rounded) output, so mask flips at ~0 do not count
+    yr = (bn(xr, rp[0], rp[1]) + bn(xpr, rp[2], rp[3])) * (y.detach().float() > 0)
+    yr.backward(dy.float())
+    assert _rel(y, yr) < 1e-2
+    assert _rel(x.grad, xr.grad) < 1e-2 and _rel(xp.grad, xpr.grad) < 1e-2
+    for p, r in zip(params, rp):
+        assert _rel(p.grad, r.grad) < 1e-2
+    torch.testing.assert_close(rm, 0.1 * x0.float().mean(red), rtol=1e-3, atol=1e-3)
+    torch.testing.assert_close(rmp, 0.1 * xp0.float().mean(red), rtol=1e-3, atol=1e-3)
+    return dict(y=y.detach(), dx=x.grad, dxp=xp.grad, rm=rm, rv=rv, rmp=rmp, rvp=rvp,
+                dgamma=params[0].grad, dbeta=params[1].grad, dgamma_p=params[2].grad,
+                dbeta_p=params[3].grad)
+
+
+@pytest.mark.parametrize("C,shape", BN_TRIP_SHAPES)
+def test_batch_norm_add_batch_norm_many_trips(C, shape):
+    """The dual kernels (bn_apply_dual, bn_bwd_reduce_dual, bn_bwd_apply_dual) under the same
+    block counts and caps; the two apply passes are again bit-identical under a cap alone."""
+    case = _dual_bn_case(C, shape)
+    base = _dual_bn_check(case)
+    for sb, cap in BN_KNOBS[1:]:
+        with _bn_knobs(sb, cap):
+            _dual_bn_check(case)
+    for cap in (1, 2, 3):
+        with _bn_knobs(0, cap):
+            _same(base, _dual_bn_check(case), tuple(base))
 
 
 @pytest.mark.parametrize("shape,k,s,p", [((2, 112, 112, 64), 3, 2, 1), ((4, 28, 28, 32), 2, 2, 0),

@@ -295,6 +295,56 @@ def test_fused_stem_bn_relu_maxpool_bit_identical():
     assert (gc - ga).abs().max() <= 1e-3 * ga.abs().max()
 
 
+def _stem_tail_grads(x, gamma, beta, dp, fused_bwd, caps=(0, 0)):
+    """(dx, dgamma, dbeta) of maxpool3x3/2(relu(BN(x))) at op level, with the pool gather fused
+    into the BN backward passes or not, under (reduce, apply) grid caps (0: the default 4096)."""
+    prev = native._FUSE_STEM_POOL_BWD
+    try:
+        native._FUSE_STEM_POOL_BWD = fused_bwd
+        native._K.pool_bn_bwd_set_caps(*caps)         # values <= 0 are ignored
+        c = x.shape[-1]
+        xn = x.clone().requires_grad_(True)
+        gn, bn = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+        y = native.batch_norm_relu_max_pool(xn, gn, bn, torch.zeros(c, device="cuda"),
+                                            torch.ones(c, device="cuda"), True, 0.9, 1e-5, 3, 2, 1)
+        y.backward(dp)
+        return xn.grad, gn.grad, bn.grad
+    finally:
+        native._FUSE_STEM_POOL_BWD = prev
+        native._K.pool_bn_bwd_set_caps(4096, 4096)
+
+
+@pytest.mark.parametrize("shape", [(3, 30, 26, 64), (3, 30, 26, 16)])
+def test_fused_stem_pool_bn_backward_grid_caps(shape):
+    """The fused stem pool + BN backward with its grids capped so that every block makes several
+    trips, as at the benchmark batch (C = 64: 19 blocks of lanes -> 10 apply trips at cap 2, 7
+    and 19 reduce trips at caps 3 and 1; C = 16: 5 blocks -> 3, 2 and 5 trips).  The apply pass is
+    elementwise given the coefficients: bit-identical under its cap.  The reduce sums in another
+    order under a cap: the bounds of test_fused_stem_bn_relu_maxpool_bit_identical against the
+    unfused path."""
+    g = torch.Generator(device="cuda").manual_seed(11)
+    n, h, w, c = shape
+    x = (torch.randn(shape, device="cuda", generator=g) * 2 + 0.5).bfloat16()
+    gamma = torch.rand(c, device="cuda", generator=g) + 0.5
+    beta = torch.randn(c, device="cuda", generator=g)
+    dp = torch.randn(n, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c, device="cuda", generator=g).bfloat16()
+    unfused = _stem_tail_grads(x, gamma, beta, dp, False)
+    base = _stem_tail_grads(x, gamma, beta, dp, True)
+    capped = _stem_tail_grads(x, gamma, beta, dp, True, (0, 2))
+    for a, b in zip(base, capped):
+        assert torch.equal(a, b)
+    for caps in ((0, 0), (3, 0), (1, 0), (1, 2)):
+        got = base if caps == (0, 0) else _stem_tail_grads(x, gamma, beta, dp, True, caps)
+        for name, a, b in zip(("dx", "dgamma", "dbeta"), got, unfused):
+            cos = torch.nn.functional.cosine_similarity(a.double().flatten(), b.double().flatten(),
+                                                        dim=0).item()
+            diff = (a.float() - b.float()).abs().max().item()
+            print(f"stem pool+BN bwd caps {caps} {name}: 1-cos {1 - cos:.3e} max diff {diff:.3e} "
+                  f"of max {b.float().abs().max().item():.3e}")
+            assert cos > 0.99999, (caps, name, cos)
+            assert diff <= 1e-3 * b.float().abs().max().item(), (caps, name, diff)
+
+
 def test_masked_grad_materialize():
     """Fallback of the lazy residual gradient: dy * bit mask, vs torch."""
     torch.manual_seed(0)
