@@ -113,6 +113,8 @@ void dtf_s2d_input(const bf16_t*, bf16_t*, int, int, int, int, int, int, int, in
                    hipStream_t);
 void dtf_softmax_xent(const float*, const void*, int, int, int, float*, float*, float,
                       hipStream_t);
+void dtf_softmax_xent_smooth(const float*, const void*, int, int, int, float*, float*, float,
+                             float, hipStream_t);
 void dtf_sgd_momentum(float*, const float*, float*, bf16_t*, long, const float*, float, float,
                       float, int, int*, hipStream_t);
 void dtf_adam(float*, const float*, float*, float*, bf16_t*, long, const float*, float, float,
@@ -122,6 +124,8 @@ void dtf_adagrad(float*, const float*, float*, bf16_t*, long, const float*, floa
 void dtf_lamb(float*, float*, float*, float*, bf16_t*, const void*, int, const float*,
               const float*, float, float, float, const float*, float, float*, int*, hipStream_t);
 int dtf_lamb_chunk_bytes();
+void dtf_lars(float*, const float*, float*, bf16_t*, const void*, int, const void*, const float*,
+              float, float, float, float, float, int, float*, int*, hipStream_t);
 void dtf_sumsq(const float*, long, float*, hipStream_t);
 void dtf_cast_f32_bf16(const float*, bf16_t*, long, hipStream_t);
 void dtf_conv_igemm(const bf16_t*, const bf16_t*, bf16_t*, const ConvGeom&, const TapTable&, int,
@@ -664,6 +668,13 @@ PYBIND11_MODULE(_dtf_hip, m) {
                      P<float>(loss_rows), P<float>(grad), gscale, S(st));
     check_launch("softmax_xent");
   });
+  m.def("softmax_xent_smooth", [](uintptr_t logits, uintptr_t labels, int label_bytes, int B,
+                                  int V, uintptr_t loss_rows, uintptr_t grad, float gscale,
+                                  float smoothing, uintptr_t st) {
+    dtf_softmax_xent_smooth(P<const float>(logits), P<const void>(labels), label_bytes, B, V,
+                            P<float>(loss_rows), P<float>(grad), gscale, smoothing, S(st));
+    check_launch("softmax_xent_smooth");
+  });
   m.def("sgd_momentum", [](uintptr_t p, uintptr_t g, uintptr_t a, uintptr_t shadow, long n,
                            uintptr_t lr, float mom, float wd, float gscale, int nesterov,
                            uintptr_t nonfinite, uintptr_t st) {
@@ -694,6 +705,15 @@ PYBIND11_MODULE(_dtf_hip, m) {
     check_launch("lamb");
   });
   m.def("lamb_chunk_bytes", &dtf_lamb_chunk_bytes);
+  m.def("lars", [](uintptr_t p, uintptr_t g, uintptr_t a, uintptr_t shadow, uintptr_t chunks,
+                   int nchunks, uintptr_t segs, uintptr_t lr, float mom, float wd, float eeta,
+                   float eps, float gscale, int nesterov, uintptr_t partial, uintptr_t nonfinite,
+                   uintptr_t st) {
+    dtf_lars(P<float>(p), P<const float>(g), P<float>(a), P<bf16_t>(shadow),
+             P<const void>(chunks), nchunks, P<const void>(segs), P<const float>(lr), mom, wd,
+             eeta, eps, gscale, nesterov, P<float>(partial), P<int>(nonfinite), S(st));
+    check_launch("lars");
+  });
   m.def("sumsq", [](uintptr_t x, long n, uintptr_t out, uintptr_t st) {
     dtf_sumsq(P<const float>(x), n, P<float>(out), S(st));
     check_launch("sumsq");

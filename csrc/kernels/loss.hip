@@ -2,44 +2,75 @@
 // TF semantics (run_mnist_distributed.py:113): loss = mean_b(-log softmax(logits_b)[label_b]);
 // the gradient (softmax - onehot) / B is produced in the same pass (one wave per row; the
 // row max / sum use 64-lane shuffles) and cached for the backward.
+//
+// Label smoothing (tf.losses.softmax_cross_entropy(label_smoothing=e), the same definition as
+// torch's): the target row is (1-e) onehot + e/V, so
+//   loss_b   = lse - (1-e) x[label] - (e/V) sum_i x_i
+//   grad_b,i = (p_i - (1-e) [i = label] - e/V) / B
+// It is the SMOOTH instantiation of the same kernel (sum_i x_i rides the first sweep); e = 0
+// launches the plain instantiation, whose code and results are unchanged.
 #include "common.h"
 
 namespace {
-template <typename LT>
+template <typename LT, bool SMOOTH>
 __global__ void __launch_bounds__(256)
 xent_kernel(const float* __restrict__ logits, const LT* __restrict__ labels, int B, int V,
-            float* __restrict__ loss_rows, float* __restrict__ grad, float grad_scale) {
+            float* __restrict__ loss_rows, float* __restrict__ grad, float grad_scale,
+            float smoothing) {
   const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   if (wave >= B) return;
   const float* row = logits + (long)wave * V;
-  float mx = -INFINITY;
-  for (int i = lane; i < V; i += 64) mx = fmaxf(mx, row[i]);
+  float mx = -INFINITY, sx = 0.f;
+  for (int i = lane; i < V; i += 64) {
+    mx = fmaxf(mx, row[i]);
+    if (SMOOTH) sx += row[i];
+  }
   mx = wave_max(mx);
+  if (SMOOTH) sx = wave_sum(sx);
   float s = 0.f;
   for (int i = lane; i < V; i += 64) s += __expf(row[i] - mx);
   s = wave_sum(s);
   const float lse = mx + __logf(s);
   const int lab = (int)labels[wave];
-  if (lane == 0) loss_rows[wave] = lse - row[lab];
+  const float on = SMOOTH ? 1.f - smoothing : 1.f;     // weight of the true class
+  const float off = SMOOTH ? smoothing / V : 0.f;      // weight spread over every class
+  if (lane == 0) loss_rows[wave] = SMOOTH ? lse - on * row[lab] - off * sx : lse - row[lab];
   if (grad) {
     const float inv = 1.f / s;
     float* g = grad + (long)wave * V;
     for (int i = lane; i < V; i += 64) {
       float p = __expf(row[i] - mx) * inv;
-      g[i] = (p - (i == lab ? 1.f : 0.f)) * grad_scale;
+      if (SMOOTH)
+        g[i] = (p - (i == lab ? on : 0.f) - off) * grad_scale;
+      else
+        g[i] = (p - (i == lab ? 1.f : 0.f)) * grad_scale;
     }
   }
+}
+
+template <bool SMOOTH>
+void launch_xent(const float* logits, const void* labels, int label_bytes, int B, int V,
+                 float* loss_rows, float* grad, float grad_scale, float smoothing,
+                 hipStream_t st) {
+  const int blocks = (B * 64 + 255) / 256;
+  if (label_bytes == 8)
+    hipLaunchKernelGGL((xent_kernel<int64_t, SMOOTH>), dim3(blocks), dim3(256), 0, st, logits,
+                       (const int64_t*)labels, B, V, loss_rows, grad, grad_scale, smoothing);
+  else
+    hipLaunchKernelGGL((xent_kernel<int32_t, SMOOTH>), dim3(blocks), dim3(256), 0, st, logits,
+                       (const int32_t*)labels, B, V, loss_rows, grad, grad_scale, smoothing);
 }
 }  // namespace
 
 void dtf_softmax_xent(const float* logits, const void* labels, int label_bytes, int B, int V,
                       float* loss_rows, float* grad, float grad_scale, hipStream_t st) {
-  const int blocks = (B * 64 + 255) / 256;
-  if (label_bytes == 8)
-    hipLaunchKernelGGL(xent_kernel<int64_t>, dim3(blocks), dim3(256), 0, st, logits,
-                       (const int64_t*)labels, B, V, loss_rows, grad, grad_scale);
-  else
-    hipLaunchKernelGGL(xent_kernel<int32_t>, dim3(blocks), dim3(256), 0, st, logits,
-                       (const int32_t*)labels, B, V, loss_rows, grad, grad_scale);
+  launch_xent<false>(logits, labels, label_bytes, B, V, loss_rows, grad, grad_scale, 0.f, st);
+}
+
+void dtf_softmax_xent_smooth(const float* logits, const void* labels, int label_bytes, int B,
+                             int V, float* loss_rows, float* grad, float grad_scale,
+                             float smoothing, hipStream_t st) {
+  launch_xent<true>(logits, labels, label_bytes, B, V, loss_rows, grad, grad_scale, smoothing,
+                    st);
 }

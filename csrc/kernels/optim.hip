@@ -10,6 +10,12 @@
 //   Adagrad  (tf.train.AdagradOptimizer):   acc += g^2; p -= lr * g * rsqrt(acc)   (acc0 = 0.1)
 //   LAMB     (per-tensor trust ratio):      u = m_hat/(sqrt(v_hat)+eps) + wd*p;
 //                                           p -= lr * (|p|/|u|) * u
+//   LARS     (tf.contrib.opt.LARSOptimizer): decayed tensors: g2 = g + wd*p,
+//                                           s = lr * eeta*|p| / (|g| + wd*|p| + eps);
+//                                           others: g2 = g, s = lr;
+//                                           a = mu*a + s*g2;  p -= a
+//                                           (nesterov: p -= s*g2 + mu*a)
+//            Its norms are slab-reduced (bitwise reproducible); LAMB's use float atomics.
 // Every kernel optionally writes the bf16 compute shadow of p in the same pass (saves the
 // separate cast of the fp32 master every step) and flags non-finite gradients.
 // Hyper-parameters that change per step (lr, lr_t) are read from DEVICE memory so a captured
@@ -159,6 +165,125 @@ lamb_phase2_kernel(float* __restrict__ p, const float* __restrict__ u,
   }
 }
 
+// ---- LARS: the LAMB chunk table, but the per-tensor norms go through a slab (one partial row
+// per chunk, plain stores) that every update block of the tensor re-adds in the same fixed
+// order -- no float atomics, so the trust ratio and the whole update are bitwise reproducible
+// and every block of a tensor forms the bit-identical step size.
+// segs[seg] = {first_row, row_count, decayed, 0}: the tensor's rows in THIS chunk table.
+__global__ void __launch_bounds__(kT)
+lars_norm_kernel(const float* __restrict__ p, const float* __restrict__ g,
+                 const Chunk* __restrict__ chunks, const int4* __restrict__ segs, float gscale,
+                 float2* __restrict__ partial, int* nonfinite) {
+  __shared__ float red[2][kT / 64];
+  const Chunk c = chunks[blockIdx.x];
+  if (!segs[c.seg].z) return;   // no trust ratio: the update pass flags this tensor's gradients
+  const float* pw = p + c.start;
+  const float* gw = g + c.start;
+  const int n4 = c.len >> 2;
+  float sw = 0.f, sg = 0.f;
+  for (int j = threadIdx.x; j < n4; j += kT) {
+    const float4 pv = reinterpret_cast<const float4*>(pw)[j];
+    const float4 gv = reinterpret_cast<const float4*>(gw)[j];
+    const float pp[4] = {pv.x, pv.y, pv.z, pv.w};
+    const float gg[4] = {gv.x, gv.y, gv.z, gv.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      flag_nonfinite(nonfinite, gg[k]);
+      const float gr = gg[k] * gscale;
+      sw += pp[k] * pp[k];
+      sg += gr * gr;
+    }
+  }
+  // scalar tail
+  for (int j = n4 * 4 + threadIdx.x; j < c.len; j += kT) {
+    flag_nonfinite(nonfinite, gw[j]);
+    const float gr = gw[j] * gscale;
+    sw += pw[j] * pw[j];
+    sg += gr * gr;
+  }
+  sw = wave_sum(sw);
+  sg = wave_sum(sg);
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sw; red[1][threadIdx.x >> 6] = sg; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float a = 0.f, b = 0.f;
+    for (int k = 0; k < kT / 64; ++k) { a += red[0][k]; b += red[1][k]; }
+    partial[blockIdx.x] = make_float2(a, b);
+  }
+}
+
+__global__ void __launch_bounds__(kT)
+lars_update_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ a,
+                   bf16_t* __restrict__ shadow, const Chunk* __restrict__ chunks,
+                   const int4* __restrict__ segs, const float* __restrict__ lr_ptr,
+                   const float2* __restrict__ partial, float momentum, float wd, float eeta,
+                   float eps, float gscale, int nesterov, int* nonfinite) {
+  __shared__ float red[2][kT / 64];
+  const Chunk c = chunks[blockIdx.x];
+  const int4 seg = segs[c.seg];
+  const bool decayed = seg.z != 0;
+  float s = *lr_ptr, wdv = 0.f;
+  if (decayed) {   // block-uniform
+    // thread t adds rows t, t + kT, ... in that order, then the same wave / block tree in every
+    // block of the tensor
+    float sw = 0.f, sg = 0.f;
+    for (int r = threadIdx.x; r < seg.y; r += kT) {
+      const float2 v = partial[seg.x + r];
+      sw += v.x;
+      sg += v.y;
+    }
+    sw = wave_sum(sw);
+    sg = wave_sum(sg);
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sw; red[1][threadIdx.x >> 6] = sg; }
+    __syncthreads();
+    float tw = 0.f, tg = 0.f;
+    for (int k = 0; k < kT / 64; ++k) { tw += red[0][k]; tg += red[1][k]; }
+    const float wn = sqrtf(tw), gn = sqrtf(tg);
+    const float trust = (wn > 0.f && gn > 0.f) ? eeta * wn / (gn + wd * wn + eps) : 1.f;
+    s *= trust;
+    wdv = wd;
+  }
+  int* const flag = decayed ? nullptr : nonfinite;   // the norm pass saw the decayed tensors
+  float* pw = p + c.start;
+  const float* gw = g + c.start;
+  float* aw = a + c.start;
+  bf16_t* sh = shadow ? shadow + c.start : nullptr;
+  const int n4 = c.len >> 2;
+  for (int j = threadIdx.x; j < n4; j += kT) {
+    const float4 pv = reinterpret_cast<float4*>(pw)[j];
+    const float4 gv = reinterpret_cast<const float4*>(gw)[j];
+    const float4 av = reinterpret_cast<float4*>(aw)[j];
+    float pp[4] = {pv.x, pv.y, pv.z, pv.w};
+    const float gg[4] = {gv.x, gv.y, gv.z, gv.w};
+    float aa[4] = {av.x, av.y, av.z, av.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      flag_nonfinite(flag, gg[k]);
+      const float u = s * (gg[k] * gscale + wdv * pp[k]);
+      aa[k] = momentum * aa[k] + u;
+      pp[k] -= nesterov ? u + momentum * aa[k] : aa[k];
+    }
+    reinterpret_cast<float4*>(pw)[j] = make_float4(pp[0], pp[1], pp[2], pp[3]);
+    reinterpret_cast<float4*>(aw)[j] = make_float4(aa[0], aa[1], aa[2], aa[3]);
+    if (sh) {
+      uint2 o;
+      o.x = pack2(pp[0], pp[1]);
+      o.y = pack2(pp[2], pp[3]);
+      reinterpret_cast<uint2*>(sh)[j] = o;
+    }
+  }
+  // scalar tail
+  for (int j = n4 * 4 + threadIdx.x; j < c.len; j += kT) {
+    flag_nonfinite(flag, gw[j]);
+    const float u = s * (gw[j] * gscale + wdv * pw[j]);
+    const float ai = momentum * aw[j] + u;
+    aw[j] = ai;
+    const float pi = pw[j] - (nesterov ? u + momentum * ai : ai);
+    pw[j] = pi;
+    if (sh) sh[j] = f2bf(pi);
+  }
+}
+
 __global__ void __launch_bounds__(kT)
 sumsq_kernel(const float* __restrict__ x, long n, float* __restrict__ out) {
   __shared__ float red[kT / 64];
@@ -221,6 +346,19 @@ void dtf_lamb(float* p, float* g, float* m, float* v, bf16_t* shadow, const void
 }
 
 int dtf_lamb_chunk_bytes() { return (int)sizeof(Chunk); }
+
+// chunks: the LAMB row layout; segs: int32 {first_row, row_count, decayed, 0} per tensor, indexing
+// THIS table; partial: one float2 per row of the table.  g is left untouched.
+void dtf_lars(float* p, const float* g, float* a, bf16_t* shadow, const void* chunks, int nchunks,
+              const void* segs, const float* lr_ptr, float momentum, float wd, float eeta,
+              float eps, float gscale, int nesterov, float* partial, int* nonfinite,
+              hipStream_t st) {
+  hipLaunchKernelGGL(lars_norm_kernel, dim3(nchunks), dim3(kT), 0, st, p, g,
+                     (const Chunk*)chunks, (const int4*)segs, gscale, (float2*)partial, nonfinite);
+  hipLaunchKernelGGL(lars_update_kernel, dim3(nchunks), dim3(kT), 0, st, p, g, a, shadow,
+                     (const Chunk*)chunks, (const int4*)segs, lr_ptr, (const float2*)partial,
+                     momentum, wd, eeta, eps, gscale, nesterov, nonfinite);
+}
 
 void dtf_sumsq(const float* x, long n, float* out, hipStream_t st) {
   hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for(n)), dim3(kT), 0, st, x, n, out);

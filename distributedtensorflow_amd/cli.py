@@ -14,6 +14,9 @@ Keeps the reference's flags and adds strategy selection:
     python train.py --model resnet50 --strategy mirrored --num_gpus 8        # configs 2 / 3
     python train.py --model resnet50 --strategy ps --num_ps 1 --num_gpus 8   # config 4
     python train.py --model bert_base --strategy multiworker --num_gpus 8    # config 5
+    # large-batch ResNet recipe: LARS + label smoothing + warm-up / polynomial decay
+    python train.py --model resnet50 --num_gpus 8 --optimizer lars --learning_rate LR
+                    --label_smoothing 0.1
 
 The chief prints the reference's ``Worker (i): loss = x.xx (global step: n)`` line every
 ``--log_every`` steps and writes ``Global Step`` / ``Loss`` TensorBoard scalars under
@@ -59,8 +62,11 @@ def build_parser():
     p.add_argument("--model", choices=MODELS, default="mnist_cnn")
     p.add_argument("--strategy", choices=STRATEGIES, default=None)
     p.add_argument("--device", choices=("auto", "cpu", "gpu"), default="auto")
-    p.add_argument("--optimizer", choices=("adam", "adagrad", "momentum", "sgd", "lamb"),
-                   default=None)
+    p.add_argument("--optimizer", choices=("adam", "adagrad", "momentum", "sgd", "lamb", "lars"),
+                   default=None,
+                   help="lars: the large-batch ResNet recipe (needs --learning_rate)")
+    p.add_argument("--label_smoothing", type=float, default=0.0,
+                   help="label smoothing of the sparse softmax cross-entropy loss")
     p.add_argument("--num_ps", type=int, default=None, help="colocated PS owners (strategy ps)")
     p.add_argument("--variable_placement", choices=("balanced", "round_robin"),
                    default="balanced")
@@ -100,7 +106,7 @@ def _spawn_local(args, argv):
     return subprocess.call(cmd)
 
 
-def _make_optimizer(name, lr, model_name, batch_global):
+def _make_optimizer(name, lr, model_name, batch_global, max_steps=None):
     from . import optimizers as O
     from .optimizers.optimizers import cosine_decay, polynomial_decay
     if name == "adam":
@@ -116,6 +122,12 @@ def _make_optimizer(name, lr, model_name, batch_global):
         return O.MomentumOptimizer(lr, 0.9)
     if name == "lamb":
         return O.LAMBOptimizer(polynomial_decay(lr, 10000, warmup_steps=100), weight_decay=0.01)
+    if name == "lars":
+        # large-batch recipe: warm-up over the first 5% of the run, then polynomial (power 2)
+        # decay to zero at the last step
+        return O.LARSOptimizer(polynomial_decay(lr, max_steps, power=2,
+                                                warmup_steps=max(1, max_steps // 20)),
+                               0.9, weight_decay=1e-4)
     raise ValueError(name)
 
 
@@ -213,7 +225,7 @@ def run(args):
             from .models import bert
             model = getattr(bert, args.model)()
         model.train()
-        opt = _make_optimizer(opt_name, lr, args.model, batch * nrep)
+        opt = _make_optimizer(opt_name, lr, args.model, batch * nrep, args.max_steps)
         if args.sync_replicas and server is not None:
             nw = len(server.worker_ranks())
             opt = dtf.train.SyncReplicasOptimizer(
@@ -234,7 +246,7 @@ def run(args):
                 onehot = torch.nn.functional.one_hot(y, 10).to(logits.dtype)
                 loss = ops.softmax_cross_entropy_clipped_sum(logits, onehot)
             else:
-                loss = ops.sparse_softmax_cross_entropy(logits, y)
+                loss = ops.sparse_softmax_cross_entropy(logits, y, args.label_smoothing)
         opt.minimize(loss, global_step=global_step)
         return {"loss": loss}
 
@@ -304,7 +316,11 @@ def evaluate_mnist(model, args, device, dtype):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    args, _unparsed = build_parser().parse_known_args(argv)
+    parser = build_parser()
+    args, _unparsed = parser.parse_known_args(argv)
+    if args.optimizer == "lars" and args.learning_rate is None:
+        # no LARS learning rate has been validated on real data: there is no default to fall to
+        parser.error("--optimizer lars requires --learning_rate")
     if (args.num_gpus or 0) > 1 and "WORLD_SIZE" not in os.environ and not args.job_name:
         return _spawn_local(args, argv)
     return run(args)

@@ -192,10 +192,12 @@ def dense(x, w, b=None, relu=False, impl=None, layout="OI"):
     return reference.dense(x, w, b, relu)
 
 
-def sparse_softmax_cross_entropy(logits, labels):
+def sparse_softmax_cross_entropy(logits, labels, label_smoothing=0.0):
+    """Mean sparse softmax cross-entropy; ``label_smoothing`` e (large-batch ResNet recipe)
+    mixes the one-hot target with the uniform distribution: (1-e) onehot + e/V."""
     if _use_native(logits):
-        return _native().sparse_softmax_cross_entropy(logits, labels)
-    return reference.sparse_softmax_cross_entropy(logits, labels)
+        return _native().sparse_softmax_cross_entropy(logits, labels, label_smoothing)
+    return reference.sparse_softmax_cross_entropy(logits, labels, label_smoothing)
 
 
 def softmax_cross_entropy_clipped_sum(logits, onehot):

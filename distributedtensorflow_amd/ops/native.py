@@ -1927,7 +1927,7 @@ class _MasterCast(torch.autograd.Function):
 
 class _SoftmaxXent(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels):
+    def forward(ctx, logits, labels, label_smoothing=0.0):
         lg = logits.detach().float().contiguous()
         B, V = lg.shape
         lab = labels.contiguous()
@@ -1935,8 +1935,13 @@ class _SoftmaxXent(torch.autograd.Function):
             lab = lab.long()
         rows = torch.empty(B, device=lg.device, dtype=torch.float32)
         grad = torch.empty_like(lg)
-        _K.softmax_xent(lg.data_ptr(), lab.data_ptr(), lab.element_size(), B, V, rows.data_ptr(),
-                        grad.data_ptr(), 1.0 / B, _st())
+        if label_smoothing:
+            _K.softmax_xent_smooth(lg.data_ptr(), lab.data_ptr(), lab.element_size(), B, V,
+                                   rows.data_ptr(), grad.data_ptr(), 1.0 / B,
+                                   float(label_smoothing), _st())
+        else:
+            _K.softmax_xent(lg.data_ptr(), lab.data_ptr(), lab.element_size(), B, V,
+                            rows.data_ptr(), grad.data_ptr(), 1.0 / B, _st())
         ctx.save_for_backward(grad)
         ctx.ldt = logits.dtype
         return rows.mean()
@@ -1944,13 +1949,15 @@ class _SoftmaxXent(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         (grad,) = ctx.saved_tensors
-        return (grad * g).to(ctx.ldt), None
+        return (grad * g).to(ctx.ldt), None, None
 
 
-def sparse_softmax_cross_entropy(logits, labels):
+def sparse_softmax_cross_entropy(logits, labels, label_smoothing=0.0):
     if logits.dim() != 2:
         raise ValueError("logits must be [B, V]")
-    return _SoftmaxXent.apply(logits, labels)
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError("label_smoothing must be in [0, 1]")
+    return _SoftmaxXent.apply(logits, labels, float(label_smoothing))
 
 
 # ----------------------------------------------------------------------------- transformer ops

@@ -116,9 +116,12 @@ def dense(x, w, b=None, relu=False):
     return torch.relu(y) if relu else y
 
 
-def sparse_softmax_cross_entropy(logits, labels):
-    """Mean over batch of -log softmax(logits)[label] (TF default reduction)."""
-    return F.cross_entropy(logits.float(), labels.long())
+def sparse_softmax_cross_entropy(logits, labels, label_smoothing=0.0):
+    """Mean over batch of -log softmax(logits)[label] (TF default reduction); with
+    ``label_smoothing`` e the target row is (1-e) onehot + e/V (TF's and torch's definition)."""
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError("label_smoothing must be in [0, 1]")
+    return F.cross_entropy(logits.float(), labels.long(), label_smoothing=float(label_smoothing))
 
 
 def softmax_cross_entropy_clipped_sum(logits, onehot):

@@ -280,6 +280,120 @@ class LAMBOptimizer(Optimizer):
                 p.sub_(lr * trust * u)
 
 
+class LARSOptimizer(Optimizer):
+    """LARS (layer-wise adaptive rate scaling, You et al. 2017) for large-batch ResNet training,
+    with the signature and update of ``tf.contrib.opt.LARSOptimizer``.  With g the (scaled)
+    gradient, a the momentum slot and lr this step's learning rate, a variable that passes
+    ``decay_filter`` (default: everything but batch-norm variables and biases, LARS's usual
+    skip list) takes
+
+        trust = eeta * |w| / (|g| + weight_decay * |w| + epsilon)   (1 if |w| or |g| is 0)
+        s = lr * trust;  g2 = g + weight_decay * w
+
+    and any other variable s = lr, g2 = g.  Then a = momentum * a + s * g2 and w -= a
+    (``use_nesterov``: w -= s * g2 + momentum * a).
+
+    The one slot is checkpointed under the ``name`` argument.  "LARSOptimizer" is
+    tf.contrib's default as best remembered; TF is not importable here, so the suffix is this
+    project's decision and not a verified parity with TF checkpoints.
+
+    GPU: two launches over LAMB's chunk table.  The norm pass stores one partial {sum w^2,
+    sum g^2} per chunk into a slab (``_norms``); every update block re-adds its tensor's rows in
+    one fixed order, so results are bitwise reproducible (no float atomics) and the gradient
+    buffer is left untouched."""
+
+    elementwise = False
+    # a checkpoint restore sets ``iterations`` (the step of the learning-rate schedule) from
+    # the saved global step, the variable TF's schedules are functions of
+    iterations_from_global_step = True
+
+    def __init__(self, learning_rate, momentum=0.9, weight_decay=1e-4, eeta=1e-3, epsilon=0.0,
+                 use_nesterov=False, name="LARSOptimizer", decay_filter=None, chunk=4096, **kw):
+        super().__init__(learning_rate, name, weight_decay=weight_decay,
+                         decay_filter=decay_filter, **kw)
+        if chunk <= 0 or chunk % 4:
+            raise ValueError("chunk must be a positive multiple of 4 (16-byte aligned rows)")
+        self.momentum, self.eeta, self.epsilon = momentum, eeta, epsilon
+        self.use_nesterov, self.chunk = use_nesterov, chunk
+        self.slot_names = (name,)
+
+    def get_config(self):
+        return {"type": "lars", "learning_rate": self.learning_rate(), "momentum": self.momentum,
+                "weight_decay": self.weight_decay, "eeta": self.eeta, "epsilon": self.epsilon,
+                "use_nesterov": self.use_nesterov, "name": self.name, "chunk": self.chunk}
+
+    def _build_slots(self):
+        sp = self.space
+        self.slots = [FlatSlot(self.name, sp.new_slot())]
+        # chunk table rows (seg, len, start), as LAMB's -- one block per row
+        rows = []
+        for seg, (v, o) in enumerate(zip(sp.order, sp.offsets)):
+            n = v.numel()
+            for c in range(0, n, self.chunk):
+                rows.append((seg, min(self.chunk, n - c), o + c))
+        self._decayed = [bool(self.decay_filter(v)) for v in sp.order]
+        self._rows = rows
+        self._tables = {}
+        # the slab of per-row partial sums {sum w^2, sum g^2}; a parameter-server shard that
+        # applies concurrently on several streams gives every stream its own copy
+        self._norms = torch.zeros(2 * max(1, len(rows)), dtype=torch.float32, device=sp.device)
+        if sp.device.type == "cuda":
+            self._chunk_table()       # upload the whole-space table now, outside graph capture
+
+    def _chunk_table(self):
+        """(chunks, segs, rows) for the whole space, or for the variables inside ``self._range``
+        (a colocated parameter-server shard; shard ranges fall on variable boundaries).  segs
+        holds {first_row, row_count, decayed, 0} per variable and indexes THIS table."""
+        key = getattr(self, "_range", None)
+        if key not in self._tables:
+            lo, hi = key if key is not None else (0, self.space.numel)
+            rows = [r for r in self._rows if lo <= r[2] < hi]
+            tbl = torch.zeros(max(1, len(rows)), 4, dtype=torch.int32)
+            segs = torch.zeros(len(self._decayed), 4, dtype=torch.int32)
+            segs[:, 2] = torch.tensor(self._decayed, dtype=torch.int32)
+            for i, (seg, ln, st) in enumerate(rows):
+                tbl[i, 0], tbl[i, 1] = seg, ln
+                tbl[i, 2], tbl[i, 3] = st & 0xFFFFFFFF if st < 2 ** 31 else st - 2 ** 32, st >> 32
+                if segs[seg, 1] == 0:
+                    segs[seg, 0] = i
+                segs[seg, 1] += 1
+            dev = self.space.device
+            self._tables[key] = (tbl.to(dev), segs.to(dev), len(rows))
+        return self._tables[key]
+
+    def _apply_native(self, gscale):
+        self._maybe_refresh_hyper()
+        sp, a = self.space, self.slots[0].buf
+        chunks, segs, nchunks = self._chunk_table()
+        if nchunks == 0:
+            return
+        _K().lars(sp.master.data_ptr(), sp.grad.data_ptr(), a.data_ptr(), _sh(sp, 0),
+                  chunks.data_ptr(), nchunks, segs.data_ptr(), self._lr_dev.data_ptr(),
+                  float(self.momentum), float(self.weight_decay), float(self.eeta),
+                  float(self.epsilon), gscale, int(self.use_nesterov), self._norms.data_ptr(),
+                  self._nonfinite.data_ptr(), _st())
+
+    def _apply_reference(self, gscale):
+        lr, mu, wd = self.learning_rate(), self.momentum, self.weight_decay
+        sp, a = self.space, self.slots[0].buf
+        lo, hi = getattr(self, "_range", None) or (0, sp.numel)
+        with torch.no_grad():
+            for var, o in zip(sp.order, sp.offsets):
+                if not lo <= o < hi:
+                    continue
+                n = var.numel()
+                g, p, aa = sp.grad[o:o + n] * gscale, sp.master[o:o + n], a[o:o + n]
+                s = lr
+                if self.decay_filter(var):
+                    wn, gn = float(p.norm()), float(g.norm())
+                    if wn > 0 and gn > 0:
+                        s = lr * self.eeta * wn / (gn + wd * wn + self.epsilon)
+                    g = g + wd * p
+                u = s * g
+                aa.mul_(mu).add_(u)
+                p.sub_(u + mu * aa if self.use_nesterov else aa)
+
+
 def clip_by_global_norm_(space, max_norm):
     """Scale the flat gradient buffer so that its global L2 norm <= max_norm; returns the norm."""
     if space.device.type == "cuda":

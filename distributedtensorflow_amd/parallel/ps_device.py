@@ -198,12 +198,13 @@ class LayoutSpace:
 
 def _make_optimizer(cfg, space):
     from ..optimizers import (AdagradOptimizer, AdamOptimizer, GradientDescentOptimizer,
-                              LAMBOptimizer, MomentumOptimizer)
+                              LAMBOptimizer, LARSOptimizer, MomentumOptimizer)
     from .strategy import _NullReducer
     cfg = dict(cfg)
     kind = cfg.pop("type")
     cls = {"adam": AdamOptimizer, "adagrad": AdagradOptimizer, "momentum": MomentumOptimizer,
-           "sgd": GradientDescentOptimizer, "lamb": LAMBOptimizer}[kind]
+           "sgd": GradientDescentOptimizer, "lamb": LAMBOptimizer,
+           "lars": LARSOptimizer}[kind]
     opt = cls(**cfg)
     opt.decay_filter = lambda v: getattr(v, "_dtf_decay", True)
     opt.space = space
@@ -295,7 +296,7 @@ class OwnerShard:
     def _hyper_buffers(self):
         o = self.opt
         out = {"_lr_dev": o._lr_dev.clone(), "_nonfinite": o._nonfinite}
-        for name in ("_hyper", "_norms"):          # LAMB
+        for name in ("_hyper", "_norms"):          # LAMB; LARS (_norms: its partial-sum slab)
             if hasattr(o, name):
                 out[name] = getattr(o, name).clone()
         return out

@@ -104,7 +104,7 @@ def choose_plane(requested, ps_device):
 class _Shard:
     def __init__(self, spec, values, device):
         from ..optimizers import (AdagradOptimizer, AdamOptimizer, GradientDescentOptimizer,
-                                  LAMBOptimizer, MomentumOptimizer)
+                                  LAMBOptimizer, LARSOptimizer, MomentumOptimizer)
         self.names = spec["names"]
         self.shapes = [tuple(s) for s in spec["shapes"]]
         self.numel = int(values.numel())
@@ -112,7 +112,8 @@ class _Shard:
         opt = dict(spec["optimizer"])
         kind = opt.pop("type")
         cls = {"adam": AdamOptimizer, "adagrad": AdagradOptimizer, "momentum": MomentumOptimizer,
-               "sgd": GradientDescentOptimizer, "lamb": LAMBOptimizer}[kind]
+               "sgd": GradientDescentOptimizer, "lamb": LAMBOptimizer,
+               "lars": LARSOptimizer}[kind]
         self.params = [torch.nn.Parameter(t.clone().to(device)) for t in
                        _split(values, self.shapes)]
         for p, n in zip(self.params, self.names):

@@ -254,6 +254,11 @@ class Saver:
             b1p = float(reader.get_tensor("beta1_power"))
             self.optimizer.iterations = max(0, int(round(np.log(b1p) /
                                                          np.log(self.optimizer.beta1))) - 1)
+        elif getattr(self.optimizer, "iterations_from_global_step", False) and \
+                "global_step" in have:
+            # no TF variable carries the update count of such an optimizer: as in TF, its
+            # schedule is a function of the global step
+            self.optimizer.iterations = int(np.asarray(reader.get_tensor("global_step")).item())
         if strict and missing:
             raise KeyError(f"variables not found in checkpoint {save_path}: {missing[:8]}")
         return missing
