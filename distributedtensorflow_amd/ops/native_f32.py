@@ -76,7 +76,7 @@ class _DenseF32(torch.autograd.Function):
         x2 = x.reshape(-1, i).contiguous()
         M = x2.shape[0]
         o = w.shape[0] if layout == "OI" else w.shape[1]
-        wd = w.detach()
+        wd = w.detach().contiguous()     # the strides below assume a dense [o, i] / [i, o]
         sbn, sbk = (i, 1) if layout == "OI" else (1, o)
         y = torch.empty(M, o, device=x.device, dtype=_F32)
         gemm_f32(M, o, i, x2, i, 1, wd, sbn, sbk, y, o, 1,
@@ -109,7 +109,7 @@ class _DenseF32(torch.autograd.Function):
 
 
 def dense(x, w, b=None, relu=False, layout="OI"):
-    _check(x, w)
+    _check(x, w, b)
     return _DenseF32.apply(x, w, b, bool(relu), layout)
 
 
@@ -163,7 +163,7 @@ class _ConvF32(torch.autograd.Function):
 
 
 def conv2d_bias_relu(x, w, b=None, stride=1, padding=0, relu=True):
-    _check(x, w)
+    _check(x, w, b)
     return _ConvF32.apply(x, w, b, stride, padding, bool(relu))
 
 
