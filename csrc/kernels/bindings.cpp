@@ -111,6 +111,9 @@ void dtf_pool_bn_bwd_apply(const bf16_t*, const uint8_t*, const bf16_t*, const f
                            int, int, int, int, int, hipStream_t);
 void dtf_s2d_input(const bf16_t*, bf16_t*, int, int, int, int, int, int, int, int, int,
                    hipStream_t);
+void dtf_eval_rows(uintptr_t, int, const void*, int, int, int, int, float*, int*, hipStream_t);
+void dtf_metrics_accumulate(const float*, const int*, const float*, int, int, double*,
+                            hipStream_t);
 void dtf_softmax_xent(const float*, const void*, int, int, int, float*, float*, float,
                       hipStream_t);
 void dtf_softmax_xent_smooth(const float*, const void*, int, int, int, float*, float*, float,
@@ -1029,5 +1032,18 @@ PYBIND11_MODULE(_dtf_hip, m) {
     dtf_mlm_xent(P<const bf16_t>(logits), P<const int64_t>(labels), P<const float>(weights),
                  P<const float>(denom), N, V, ld, P<float>(loss_rows), P<bf16_t>(grad), S(st));
     check_launch("mlm_xent");
+  });
+  // evaluation metrics (metrics.hip): elem_bytes 2 = bf16 / 4 = fp32 logits with row stride ld
+  m.def("eval_rows", [](uintptr_t logits, int elem_bytes, uintptr_t labels, int label_bytes,
+                        int N, int V, int ld, uintptr_t loss_rows, uintptr_t rank, uintptr_t st) {
+    dtf_eval_rows(logits, elem_bytes, P<const void>(labels), label_bytes, N, V, ld,
+                  P<float>(loss_rows), P<int>(rank), S(st));
+    check_launch("eval_rows");
+  });
+  m.def("metrics_accumulate", [](uintptr_t loss_rows, uintptr_t rank, uintptr_t weights, int N,
+                                 int k, uintptr_t state, uintptr_t st) {
+    dtf_metrics_accumulate(P<const float>(loss_rows), P<const int>(rank),
+                           P<const float>(weights), N, k, P<double>(state), S(st));
+    check_launch("metrics_accumulate");
   });
 }

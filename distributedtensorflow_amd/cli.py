@@ -17,6 +17,8 @@ Keeps the reference's flags and adds strategy selection:
     # large-batch ResNet recipe: LARS + label smoothing + warm-up / polynomial decay
     python train.py --model resnet50 --num_gpus 8 --optimizer lars --learning_rate LR
                     --label_smoothing 0.1
+    # loss / top-1 / top-k over all replicas: at the end (--eval) and every N steps (--eval_every)
+    python train.py --model resnet50 --num_gpus 8 --eval --eval_steps 20 --eval_every 500
 
 The chief prints the reference's ``Worker (i): loss = x.xx (global step: n)`` line every
 ``--log_every`` steps and writes ``Global Step`` / ``Loss`` TensorBoard scalars under
@@ -79,7 +81,14 @@ def build_parser():
     p.add_argument("--save_checkpoint_steps", type=int, default=None)
     p.add_argument("--save_checkpoint_secs", type=int, default=600)
     p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--eval", action="store_true", help="evaluate on the MNIST test set at the end")
+    p.add_argument("--eval", action="store_true",
+                   help="evaluate at the end, over every replica: the MNIST test set, or "
+                        "--eval_steps synthetic batches for ResNet / BERT")
+    p.add_argument("--eval_every", type=int, default=0,
+                   help="also evaluate every N global steps during training (0 = off)")
+    p.add_argument("--eval_steps", type=int, default=10,
+                   help="batches per replica of an evaluation on the synthetic sets")
+    p.add_argument("--eval_top_k", type=int, default=5, help="k of the reported top-k accuracy")
     return p
 
 
@@ -250,7 +259,17 @@ def run(args):
         opt.minimize(loss, global_step=global_step)
         return {"loss": loss}
 
+    # ---- evaluation: every replica of a strategy evaluates its shard; in a between-graph
+    # cluster the chief worker alone does, on the variables it pulled
+    eval_fn = eval_hook = None
+    if (args.eval or args.eval_every) and (server is None or is_chief):
+        eval_fn = _make_eval_fn(args, model, opt, strategy, device, dtype, batch,
+                                nrep if server is None else 1, rid if server is None else 0)
     hooks = [StopAtStepHook(last_step=args.max_steps)]
+    if eval_fn is not None and args.eval_every:
+        from .train import EvalHook
+        eval_hook = EvalHook(eval_fn, args.eval_every)
+        hooks.append(eval_hook)
     cfg = ConfigProto(allow_soft_placement=True, intra_op_parallelism_threads=os.cpu_count(),
                       inter_op_parallelism_threads=os.cpu_count())
     logs = None
@@ -266,6 +285,8 @@ def run(args):
             log_directory = os.path.join(args.log_dir, stamp)
             logs = logger.TensorBoardOutputFormat(dir=log_directory)
             print("Logging to", log_directory, flush=True)
+            if eval_hook is not None:
+                eval_hook.writer = logs
         first_step = global_step.value()
         while not sess.should_stop():
             out = sess.run([train_op, "loss", global_step])
@@ -289,8 +310,17 @@ def run(args):
     steps_done = global_step.value() - (first_step or 0)
     if steps_done > 0 and server is None:
         result["examples_per_sec"] = round(steps_done * batch * nrep / elapsed, 1)
-    if args.eval and args.model.startswith("mnist") and is_chief:
-        result["test_accuracy"] = evaluate_mnist(model, args, device, dtype)
+    ev = None
+    if eval_fn is not None and args.eval:
+        ev = eval_fn()                     # collective: every replica of the strategy is here
+    elif eval_hook is not None and eval_hook.results:
+        ev = eval_hook.results[-1][1]
+    if ev is not None:
+        result["eval_loss"] = round(ev["loss"], 4)
+        result["eval_top_1"] = round(ev["top_1"], 4)
+        result["eval_top_k"] = round(ev["top_k"], 4)
+        if args.model.startswith("mnist"):
+            result["test_accuracy"] = round(ev["top_1"], 4)
     if is_chief:
         print(json.dumps(result), flush=True)
     if server is not None:
@@ -298,20 +328,39 @@ def run(args):
     return 0
 
 
-def evaluate_mnist(model, args, device, dtype):
-    import torch
+def _make_eval_fn(args, model, opt, strategy, device, dtype, batch, shards, shard_index):
+    """-> eval_fn() -> {"loss", "top_1", "top_k", "count"}: one pass of this replica's shard of
+    the evaluation set through ``train.evaluate`` (collective under a collective strategy)."""
+    from .metrics import ClassificationMetrics
+    from .train import evaluate
+    if args.model.startswith("mnist"):
+        from .data import DeviceArrayDataset, mnist
+        imgs, labels = mnist.load_arrays(args.data_dir, "test")
+        per = max(1, min(1000, len(labels) // shards))
+        data = DeviceArrayDataset(imgs, labels, per, device, dtype, shuffle=False,
+                                  num_shards=shards, shard_index=shard_index)
 
-    from .data import mnist
-    imgs, labels = mnist.load_arrays(args.data_dir, "test")
-    model.eval()
-    correct = 0
-    with torch.no_grad():
-        for i in range(0, len(labels), 1000):
-            x = torch.as_tensor(imgs[i:i + 1000]).to(device).to(dtype) / 255.0
-            pred = model(x).argmax(-1).cpu().numpy()
-            correct += int((pred == labels[i:i + 1000]).sum())
-    model.train()
-    return round(correct / len(labels), 4)
+        def batches():
+            return data.single_pass()
+    else:
+        if args.model.startswith("resnet"):
+            from .data import SyntheticImageNet
+            data = SyntheticImageNet(batch, args.image_size, device=device, dtype=dtype,
+                                     pool=max(1, min(2, args.eval_steps)),
+                                     seed=4321 + shard_index)
+        else:
+            from .data import SyntheticMLM
+            data = SyntheticMLM(batch, args.seq_len, device=device, seed=4321 + shard_index,
+                                pool=max(1, min(2, args.eval_steps)))
+
+        def batches():
+            return data.single_pass(args.eval_steps)
+    metrics = ClassificationMetrics(k=args.eval_top_k, strategy=strategy)
+
+    def eval_fn():
+        metrics.reset()
+        return evaluate(model, batches(), metrics, optimizer=opt, strategy=strategy)
+    return eval_fn
 
 
 def main(argv=None):

@@ -60,6 +60,16 @@ class DeviceArrayDataset:
         self._pos += self.batch_size
         return self._gather(idx)
 
+    def single_pass(self, batch_size=None):
+        """A finite iterator for evaluation: this shard's examples in order, once, the remainder
+        batch included, no shuffle.  With ``num_shards`` / ``shard_index`` every example of the
+        set is seen exactly once across the replicas.  Independent of the endless training
+        iteration (its position, epoch and shuffle generator are not touched)."""
+        bs = int(batch_size or self.batch_size)
+        for pos in range(0, self.n, bs):
+            idx = torch.arange(pos, min(pos + bs, self.n), device=self.device)
+            yield self._gather(idx)
+
     def _gather(self, idx):
         if (self.device.type == "cuda" and self.images.dtype == torch.uint8
                 and self.dtype in (torch.bfloat16, torch.float32)

@@ -32,6 +32,13 @@ class SyntheticImageNet:
         self.i += 1
         return self.images[k], self.labels[k]
 
+    def single_pass(self, steps):
+        """A finite iterator for evaluation: ``steps`` batches of the pool, from its start;
+        the endless iteration's position is not touched."""
+        for i in range(int(steps)):
+            k = i % len(self.images)
+            yield self.images[k], self.labels[k]
+
 
 class SyntheticMLM:
     def __init__(self, batch_size, seq_len=128, vocab_size=30522, max_predictions=20,
@@ -59,3 +66,9 @@ class SyntheticMLM:
         b = self.batches[self.i % len(self.batches)]
         self.i += 1
         return b
+
+    def single_pass(self, steps):
+        """A finite iterator for evaluation: ``steps`` batches of the pool, from its start;
+        the endless iteration's position is not touched."""
+        for i in range(int(steps)):
+            yield self.batches[i % len(self.batches)]

@@ -294,6 +294,29 @@ def mlm_loss(logits, labels, weights=None, vocab=None):
     return reference.mlm_loss(logits, labels, weights, vocab)
 
 
+def eval_rows(logits, labels, vocab=None):
+    """Per-row evaluation loss and stable descending rank of the label, one read of the logits:
+    ``(loss_rows fp32 [N], rank int32 [N])``.  ``rank = #{j: x_j > x_label} + #{j < label:
+    x_j == x_label}``; the label is in the top k iff ``rank < k`` (for k = 1: ``torch.argmax``'s
+    first-maximal-index rule; stricter than TF's ``in_top_k``, which counts strictly greater
+    logits only).  A label outside ``[0, V)`` marks an ignored row (rank -1, loss 0); a NaN label
+    logit is a miss (rank V).  ``vocab``: the class count when rows are padded past it.  Native
+    path: bf16 / fp32 logits with unit column stride are read in place, row-strided views
+    included."""
+    if _use_native(logits):
+        return _native().eval_rows(logits, labels, vocab)
+    return reference.eval_rows(logits, labels, vocab)
+
+
+def in_top_k(logits, labels, k):
+    """bool[N]: the label is among the k largest logits under the stable tie rule of
+    :func:`eval_rows` (ignored rows are False)."""
+    if int(k) < 1:
+        raise ValueError("in_top_k: k must be at least 1")
+    rank = eval_rows(logits, labels)[1]
+    return (rank >= 0) & (rank < int(k))
+
+
 # ----------------------------------------------------------------------------- variable fence
 # A colocated parameter server gathers the updated variable shards AFTER the optimizer step,
 # asynchronously, bucket by bucket, while the next forward already runs (parallel/ps_strategy.py).
@@ -337,7 +360,7 @@ _OPS = ("conv2d", "conv2d_bias_relu", "batch_norm", "batch_norm_add_batch_norm",
         "bias_dropout_add_layer_norm", "embedding_layer_norm", "bias_gelu", "bias_gelu_dense",
         "dense_gelu_dense", "relu", "max_pool2d", "global_avg_pool", "sparse_softmax_cross_entropy",
         "softmax_cross_entropy_clipped_sum", "gelu", "attention", "dropout", "attention_qkv",
-        "mlm_loss")
+        "mlm_loss", "eval_rows", "in_top_k")
 _FENCED = _OPS
 for _name in _OPS:
     globals()[_name] = _dispatch(_name, globals()[_name], True)
@@ -349,5 +372,5 @@ __all__ = [
     "max_pool2d", "global_avg_pool", "dense", "sparse_softmax_cross_entropy",
     "softmax_cross_entropy_clipped_sum", "layer_norm", "gelu", "attention", "dropout",
     "bias_dropout_add_layer_norm", "embedding_layer_norm", "bias_gelu", "bias_gelu_dense",
-    "dense_gelu_dense", "attention_qkv", "mlm_loss",
+    "dense_gelu_dense", "attention_qkv", "mlm_loss", "eval_rows", "in_top_k",
 ]

@@ -1960,6 +1960,60 @@ def sparse_softmax_cross_entropy(logits, labels, label_smoothing=0.0):
     return _SoftmaxXent.apply(logits, labels, float(label_smoothing))
 
 
+# ----------------------------------------------------------------------------- evaluation
+
+def eval_rows(logits, labels, vocab=None):
+    """(loss_rows fp32 [N], rank int32 [N]) in one sweep of the logits (csrc/kernels/metrics.hip;
+    semantics: ops/reference.py eval_rows).  bf16 / fp32 logits with unit column stride are read
+    where they are -- no copy, no upcast -- whatever their row stride or alignment (the
+    ``[:, :V]`` view of BERT's padded-vocabulary logits included)."""
+    if logits.dim() != 2:
+        raise ValueError("logits must be [N, V]")
+    if not logits.is_cuda:
+        raise ValueError("native eval_rows needs a GPU tensor")
+    N, W = logits.shape
+    V = W if vocab is None else int(vocab)
+    if not 0 < V <= W:
+        raise ValueError(f"eval_rows: vocab {vocab} outside the logits width {W}")
+    lg = logits.detach()
+    if lg.dtype not in (_BF16, torch.float32):
+        lg = lg.float()
+    if lg.stride(1) != 1 or (N > 1 and lg.stride(0) < V):
+        lg = lg.contiguous()
+    ld = lg.stride(0) if N > 1 else V
+    lab = labels.reshape(-1)
+    if lab.dtype not in (torch.int64, torch.int32):
+        lab = lab.long()
+    lab = lab.contiguous()
+    if lab.numel() != N:
+        raise ValueError(f"eval_rows: {lab.numel()} labels for {N} rows")
+    if lab.device != lg.device:
+        raise ValueError("eval_rows: labels and logits on different devices")
+    rows = torch.empty(N, device=lg.device, dtype=torch.float32)
+    rank = torch.empty(N, device=lg.device, dtype=torch.int32)
+    _K.eval_rows(lg.data_ptr(), lg.element_size(), lab.data_ptr(), lab.element_size(), N, V, ld,
+                 rows.data_ptr(), rank.data_ptr(), _st())
+    return rows, rank
+
+
+def metrics_accumulate(state, loss_rows, rank, weights, k):
+    """state[0..3] (fp64, on the device) += [sum w, sum w loss, sum w [rank<1], sum w [rank<k]]
+    in a fixed order (one block, no atomics); ``weights``: optional fp32 per-row weights."""
+    N = rank.numel()
+    if state.dtype != torch.float64 or state.numel() != 4 or not state.is_contiguous():
+        raise ValueError("metrics state must be 4 contiguous fp64 values")
+    if loss_rows.dtype != torch.float32 or rank.dtype != torch.int32 or loss_rows.numel() != N:
+        raise ValueError("metrics_accumulate: fp32 loss rows and int32 ranks of one length")
+    w = None
+    if weights is not None:
+        w = weights.reshape(-1).float().contiguous()
+        if w.numel() != N:
+            raise ValueError(f"metrics_accumulate: {w.numel()} weights for {N} rows")
+    _K.metrics_accumulate(loss_rows.contiguous().data_ptr(), rank.contiguous().data_ptr(), _p(w),
+                          N, int(k), state.data_ptr(), _st())
+    return state
+
+
 # ----------------------------------------------------------------------------- transformer ops
 # (LayerNorm / GELU / attention for BERT live in .native_nlp to keep this file focused)
 

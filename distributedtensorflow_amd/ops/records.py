@@ -33,6 +33,7 @@ Plain Python objects: importable without the HIP extension (kernels are reached 
 """
 from __future__ import annotations
 
+import contextlib
 import weakref
 
 _LIVE = weakref.WeakSet()          # records created since the last end_step()
@@ -223,5 +224,19 @@ def end_step():
     return len(recs)
 
 
+@contextlib.contextmanager
+def isolated():
+    """Work that is not part of a training step (an evaluation between two steps): records made
+    inside get a registry of their own, released on exit, and the registry of the step outside
+    -- with whatever it holds -- is put back exactly as it was."""
+    global _LIVE
+    outer, _LIVE = _LIVE, weakref.WeakSet()
+    try:
+        yield
+    finally:
+        end_step()
+        _LIVE = outer
+
+
 __all__ = ["BnDeferred", "Recompute", "MaskedGrad", "LazyBnDx", "LazyStemDz", "GradSlot",
-           "ReleasedRecordError", "live_count", "end_step"]
+           "ReleasedRecordError", "live_count", "end_step", "isolated"]

@@ -282,6 +282,47 @@ def mlm_loss(logits, labels, weights=None, vocab=None):
     return (w * nll).sum() / w.sum().clamp_min(1e-5)
 
 
+def eval_rows(logits, labels, vocab=None, loss_dtype=torch.float32):
+    """Per-row evaluation loss and rank of the label: the oracle of the ``eval_rows`` kernel.
+
+    ``loss_rows[i] = logsumexp(x_i) - x_i[label_i]`` in fp64 on the stored values (unsmoothed),
+    returned as ``loss_dtype``; ``rank[i]`` (int32) is the stable descending rank of the label,
+
+        rank = #{j : x_j > x_label} + #{j < label : x_j == x_label}
+
+    so the label is in the top k iff ``rank < k``, ties included: among equal logits the lower
+    index ranks first, which for k = 1 is ``torch.argmax``'s rule.  This is stricter than TF's
+    ``in_top_k``, which counts strictly greater logits only and so admits every member of a tie
+    at the k boundary.  ``vocab``: the class count when the rows are padded past it (columns from
+    ``vocab`` on are not classes, whatever they hold).  A label outside ``[0, vocab)`` marks an
+    ignored row (rank -1, loss 0); a NaN label logit is a miss (rank = vocab)."""
+    if logits.dim() != 2:
+        raise ValueError("logits must be [N, V]")
+    N, ld = logits.shape
+    V = ld if vocab is None else int(vocab)
+    if not 0 < V <= ld:
+        raise ValueError(f"eval_rows: vocab {vocab} outside the logits width {ld}")
+    lab = labels.reshape(-1).long()
+    if lab.numel() != N:
+        raise ValueError(f"eval_rows: {lab.numel()} labels for {N} rows")
+    loss = torch.zeros(N, dtype=torch.float64, device=logits.device)
+    rank = torch.full((N,), -1, dtype=torch.int32, device=logits.device)
+    cols = torch.arange(V, device=logits.device)
+    step = max(1, (1 << 22) // V)                      # bounds the fp64 working set
+    for r0 in range(0, N, step):
+        x = logits[r0:r0 + step, :V].double()
+        lb = lab[r0:r0 + step]
+        ok = (lb >= 0) & (lb < V)
+        xl = x.gather(1, lb.clamp(0, V - 1).unsqueeze(1))
+        gt = (x > xl).sum(1)
+        eq = ((x == xl) & (cols.unsqueeze(0) < lb.unsqueeze(1))).sum(1)
+        rk = torch.where(torch.isnan(xl.squeeze(1)), torch.full_like(gt, V), gt + eq)
+        rank[r0:r0 + step] = torch.where(ok, rk, torch.full_like(rk, -1)).to(torch.int32)
+        ls = torch.logsumexp(x, 1) - xl.squeeze(1)
+        loss[r0:r0 + step] = torch.where(ok, ls, torch.zeros_like(ls))
+    return loss.to(loss_dtype), rank
+
+
 def space_to_depth_operands(x, w, stride, pad, want_x=True):
     """Rewrite a strided conv (the ResNet stem: 7x7 / 2, pad 3, C = 3) as a stride-1 VALID conv
     on the space-to-depth input.  Output pixel p reads padded input rows s*p + r, r < R; with

@@ -25,8 +25,9 @@ import time
 import torch
 import torch.distributed as dist
 
-from .strategy import (BucketedAllReduce, MirroredStrategy, Strategy, _broadcast_training_state,
-                       _NullReducer, collective_cluster_changed, comm_call,
+from .strategy import (BucketedAllReduce, MirroredStrategy, ReduceOp, Strategy,
+                       _broadcast_training_state, _NullReducer, _torch_op,
+                       collective_cluster_changed, comm_call,
                        force_reducer_default, init_process_group_from_env, rejoin_collective)
 
 
@@ -773,6 +774,15 @@ class ParameterServerStrategy(Strategy):
     @property
     def ps_client(self):
         return self._client
+
+    def all_reduce_(self, t, op=ReduceOp.SUM):
+        """Colocated owners are one collective world (evaluation metrics are summed over it);
+        a between-graph worker has no peer to reduce with."""
+        if self.collective:
+            dist.all_reduce(t, _torch_op(op))
+            if op == ReduceOp.MEAN:
+                t /= self.num_replicas_in_sync
+        return t
 
     def barrier(self):
         if self.mode == "colocated" and dist.is_initialized():
