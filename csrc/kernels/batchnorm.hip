@@ -15,7 +15,7 @@
 //   expression), so the backward never reads y (-2 B/element in both backward passes).
 #include <stdexcept>
 
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -66,7 +66,9 @@ DTF_DEV void relu_mask8(float* g, const float* xv, uint32_t mbyte, uint4 yraw, i
   }
 }
 
-DTF_DEV void load8f(const float* __restrict__ p, int cg, float* v) {
+// common.h's load8f by 8-float chunk, indexed in float4 units: the element-indexed form compiles
+// to other address arithmetic in these kernels, so this spelling stays
+DTF_DEV void load8cg(const float* __restrict__ p, int cg, float* v) {
   const float4 a = reinterpret_cast<const float4*>(p)[cg * 2];
   const float4 b = reinterpret_cast<const float4*>(p)[cg * 2 + 1];
   v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
@@ -122,10 +124,10 @@ bn_reduce_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
 #pragma unroll
   for (int i = 0; i < 8; ++i) { a0[i] = 0.f; a1[i] = 0.f; a2[i] = 0.f; ksc[i] = 0.f; ksh[i] = 0.f; }
   if (MODE >= 1 && active) {
-    load8f(mean, cg, mu);
-    load8f(invstd, cg, is);
-    if (MK == 2) { load8f(fsc, cg, ksc); load8f(fsh, cg, ksh); }
-    if (MODE == 2) { load8f(meanp, cg, mup); load8f(invstdp, cg, isp); }
+    load8cg(mean, cg, mu);
+    load8cg(invstd, cg, is);
+    if (MK == 2) { load8cg(fsc, cg, ksc); load8cg(fsh, cg, ksh); }
+    if (MODE == 2) { load8cg(meanp, cg, mup); load8cg(invstdp, cg, isp); }
   }
   const int m0 = blockIdx.x * rows_per_block;
   const int m1 = min(m0 + rows_per_block, M);
@@ -321,9 +323,9 @@ bn_apply_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ res,
   const int cg = threadIdx.x % tpr, ro = threadIdx.x / tpr;
   if (ro >= rpi) return;
   float sc[8], sh[8], rsc[8], rsh[8];
-  load8f(scale, cg, sc);
-  load8f(shift, cg, sh);
-  if (DUAL) { load8f(rscale, cg, rsc); load8f(rshift, cg, rsh); }
+  load8cg(scale, cg, sc);
+  load8cg(shift, cg, sh);
+  if (DUAL) { load8cg(rscale, cg, rsc); load8cg(rshift, cg, rsh); }
   const uint4* X4 = reinterpret_cast<const uint4*>(x);
   const uint4* R4 = reinterpret_cast<const uint4*>(res);
   uint4* Y4 = reinterpret_cast<uint4*>(y);
@@ -415,11 +417,11 @@ bn_bwd_apply_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ y,
   const int cg = threadIdx.x % tpr, ro = threadIdx.x / tpr;
   if (ro >= rpi) return;
   float ka[8], kb[8], kc[8], ksc[8], ksh[8], pa[8], pb[8], pc[8];
-  load8f(cA, cg, ka);
-  load8f(cB, cg, kb);
-  load8f(cC, cg, kc);
-  if (MK == 2) { load8f(fsc, cg, ksc); load8f(fsh, cg, ksh); }
-  if (DUAL) { load8f(cAp, cg, pa); load8f(cBp, cg, pb); load8f(cCp, cg, pc); }
+  load8cg(cA, cg, ka);
+  load8cg(cB, cg, kb);
+  load8cg(cC, cg, kc);
+  if (MK == 2) { load8cg(fsc, cg, ksc); load8cg(fsh, cg, ksh); }
+  if (DUAL) { load8cg(cAp, cg, pa); load8cg(cBp, cg, pb); load8cg(cCp, cg, pc); }
   const uint4* XP4 = reinterpret_cast<const uint4*>(xp);
   uint4* DXP4 = reinterpret_cast<uint4*>(dxp);
   const uint4* D4 = reinterpret_cast<const uint4*>(dy);

@@ -12,267 +12,9 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "launch.h"
 
 namespace py = pybind11;
-
-#define DTF_MAX_TAPS 64
-struct TapTable { int n; int dh[DTF_MAX_TAPS]; int dw[DTF_MAX_TAPS]; };
-struct TapTableW { int n; int dh[DTF_MAX_TAPS]; int dw[DTF_MAX_TAPS]; };
-struct ConvGeom {
-  int N, H, W, C, P, Q, sh, sw, Kout, Kpad, Ho, Wo, osh, osw, oh0, ow0, acc;
-  const bf16_t* acc_src;
-  const uint8_t* acc_mask;
-  const float* bias;
-  int relu;
-  int nt;
-  const float* lsc;
-  const float* lsh;
-  bf16_t* ly;
-};
-struct BnBwdEpi {
-  const bf16_t* x; const float* mean; const float* invstd; const float* fsc; const float* fsh;
-  const uint8_t* mask; float* part; int mkind; int row0;
-};
-constexpr int kWtMaxJobs = 48;
-struct WtJobs {
-  const bf16_t* src[kWtMaxJobs];
-  bf16_t* dst[kWtMaxJobs];
-  int K[kWtMaxJobs], T[kWtMaxJobs], C[kWtMaxJobs];
-  int tile_end[kWtMaxJobs];
-  int n;
-};
-void dtf_filter_transpose(const WtJobs&, hipStream_t);
-struct WgradGeom { int N, H, W, C, P, Q, sh, sw, Kout, ldw; long m_per_split; long slab; };
-
-// ---- launchers defined in the .hip translation units
-int dtf_bn_partial_blocks(long M, int C);
-long dtf_bn_workspace_floats(long M, int C);
-void dtf_bn_fwd_stats(const bf16_t*, long, int, float*, hipStream_t);
-void dtf_bn_fwd_finalize(const float*, long, int, const float*, const float*, float*, float*,
-                         float, float, float*, float*, float*, float*, hipStream_t);
-void dtf_bn_fwd_finalize_g(const float*, int, long, int, const float*, const float*, float*,
-                           float*, float, float, float*, float*, float*, float*, hipStream_t);
-long dtf_bn_workspace_floats_g(int, int);
-int dtf_conv_stats_rows(long, int, int, int, int);
-void dtf_conv_set_halo(int);
-int dtf_gemm_conv_part_images(int, int, int, int, int, int);
-void dtf_gemm_set_pp2_strided(int);
-int dtf_conv_tile_rows(const ConvGeom&, const TapTable&, int bnb);
-bool dtf_conv_bnl_ok(const ConvGeom&, const TapTable&);
-void dtf_conv_set_bnl_probe(int);
-void dtf_gemm_stream_set_bnb_probe(int);
-void dtf_conv_set_halo_bnb(int);
-void dtf_conv_set_dma_mode(int);
-void dtf_conv_set_small_k(int);
-void dtf_conv_set_stem_halo(int);
-void dtf_conv_set_halo_strips(int);
-void dtf_conv_set_halo_freg(int);
-void dtf_bn_infer_finalize(int, const float*, const float*, const float*, const float*, float,
-                           float*, float*, float*, float*, hipStream_t);
-void dtf_bn_apply(const bf16_t*, const bf16_t*, bf16_t*, uint8_t*, const float*, const float*,
-                  long, int, int, hipStream_t);
-void dtf_bn_bwd_reduce(const bf16_t*, const bf16_t*, const uint8_t*, const bf16_t*, const float*,
-                       const float*, long, int, int, float*, const float*, const float*,
-                       hipStream_t);
-void dtf_bn_bwd_finalize_g(const float*, int, long, int, const float*, const float*, const float*,
-                           float*, float*, float*, float*, float*, int, hipStream_t);
-void dtf_bn_bwd_finalize(const float*, long, int, const float*, const float*, const float*,
-                         float*, float*, float*, float*, float*, int, hipStream_t);
-void dtf_relu_mask_apply(const bf16_t*, const uint8_t*, bf16_t*, long, hipStream_t);
-void dtf_bn_apply_dual(const bf16_t*, const bf16_t*, bf16_t*, uint8_t*, const float*, const float*,
-                       const float*, const float*, long, int, int, hipStream_t);
-void dtf_bn_bwd_reduce_dual(const bf16_t*, const uint8_t*, const bf16_t*, const float*,
-                            const float*, const bf16_t*, const float*, const float*, long, int,
-                            float*, float*, hipStream_t);
-void dtf_bn_bwd_apply_dual(const bf16_t*, const uint8_t*, const bf16_t*, const float*,
-                           const float*, const float*, bf16_t*, const bf16_t*, const float*,
-                           const float*, const float*, bf16_t*, long, int, hipStream_t);
-void dtf_bn_bwd_apply(const bf16_t*, const bf16_t*, const uint8_t*, const bf16_t*, const float*,
-                      const float*, const float*, bf16_t*, bf16_t*, long, int, int, const float*,
-                      const float*, hipStream_t);
-void dtf_maxpool_fwd(const bf16_t*, bf16_t*, uint8_t*, int, int, int, int, int, int, int, int,
-                     int, int, int, int, hipStream_t);
-void dtf_maxpool_bwd(const bf16_t*, const uint8_t*, bf16_t*, int, int, int, int, int, int, int,
-                     int, int, int, int, int, hipStream_t);
-void dtf_gap_fwd(const bf16_t*, bf16_t*, int, int, int, hipStream_t);
-void dtf_gap_bwd(const bf16_t*, bf16_t*, int, int, int, hipStream_t);
-void dtf_bn_relu_maxpool_fwd(const bf16_t*, const float*, const float*, bf16_t*, uint8_t*, int,
-                             int, int, int, int, int, int, int, int, int, int, int, hipStream_t);
-void dtf_pool_set_blocked(int);
-void dtf_s2d_set_rows(int);
-int dtf_pool_bn_bwd_blocks(int, int, int, int);
-void dtf_pool_bn_bwd_set_caps(int, int);
-void dtf_pool_bn_bwd_reduce(const bf16_t*, const uint8_t*, const bf16_t*, const float*,
-                            const float*, const float*, const float*, float*, int, int, int, int,
-                            int, int, hipStream_t);
-void dtf_pool_bn_bwd_apply(const bf16_t*, const uint8_t*, const bf16_t*, const float*,
-                           const float*, const float*, const float*, const float*, bf16_t*, int,
-                           int, int, int, int, int, hipStream_t);
-void dtf_s2d_input(const bf16_t*, bf16_t*, int, int, int, int, int, int, int, int, int,
-                   hipStream_t);
-void dtf_eval_rows(uintptr_t, int, const void*, int, int, int, int, float*, int*, hipStream_t);
-void dtf_metrics_accumulate(const float*, const int*, const float*, int, int, double*,
-                            hipStream_t);
-void dtf_softmax_xent(const float*, const void*, int, int, int, float*, float*, float,
-                      hipStream_t);
-void dtf_softmax_xent_smooth(const float*, const void*, int, int, int, float*, float*, float,
-                             float, hipStream_t);
-void dtf_sgd_momentum(float*, const float*, float*, bf16_t*, long, const float*, float, float,
-                      float, int, int*, hipStream_t);
-void dtf_adam(float*, const float*, float*, float*, bf16_t*, long, const float*, float, float,
-              float, float, float, int*, hipStream_t);
-void dtf_adagrad(float*, const float*, float*, bf16_t*, long, const float*, float, int*,
-                 hipStream_t);
-void dtf_lamb(float*, float*, float*, float*, bf16_t*, const void*, int, const float*,
-              const float*, float, float, float, const float*, float, float*, int*, hipStream_t);
-int dtf_lamb_chunk_bytes();
-void dtf_lars(float*, const float*, float*, bf16_t*, const void*, int, const void*, const float*,
-              float, float, float, float, float, int, float*, int*, hipStream_t);
-void dtf_sumsq(const float*, long, float*, hipStream_t);
-void dtf_cast_f32_bf16(const float*, bf16_t*, long, hipStream_t);
-void dtf_conv_igemm(const bf16_t*, const bf16_t*, bf16_t*, const ConvGeom&, const TapTable&, int,
-                    float*, const BnBwdEpi&, hipStream_t);
-bool dtf_conv_igemm_grouped(const bf16_t*, bf16_t*, const ConvGeom&, int, const bf16_t* const*,
-                            const int*, const int*, const int*,
-                            const std::vector<std::vector<int>>&,
-                            const std::vector<std::vector<int>>&, const BnBwdEpi&, const int*,
-                            hipStream_t);
-void dtf_conv_wgrad(const bf16_t*, const bf16_t*, float*, float*, WgradGeom, const TapTableW&,
-                    int, int, int, hipStream_t);
-
-int dtf_conv_wgrad_splits(long, int, int, long, int);
-int dtf_conv_wgrad_halo_splits(int, int, int, int, int, int, int, int, int, const TapTableW&);
-void dtf_wgrad_set_halo(int);
-void dtf_wgrad_set_stem(int);
-int dtf_wgrad_stem_dz_splits(int);
-void dtf_conv_wgrad_stem_dz(const bf16_t*, const bf16_t*, const uint8_t*, const bf16_t*,
-                            const float*, const float*, const float*, const float*, const float*,
-                            float*, float*, int, int, hipStream_t);
-void dtf_conv_set_halo_stages(int);
-void dtf_wgrad_set_dma_mode(int);
-void dtf_wgrad_set_pipe(int);
-void dtf_wgrad_set_pp(int);
-void dtf_wgrad_set_dense(int);
-void dtf_wgrad_set_direct(int);
-void dtf_wgrad_set_deep(int);
-void dtf_conv_set_gemm(int);
-void dtf_bn_set_nt(int);
-void dtf_bn_set_grid_cap(int);
-void dtf_bn_set_stats_blocks(int);
-void dtf_conv_set_nt(int);
-void dtf_gemm_set_nt(int);
-void dtf_gemm_set_dbg(int);
-void dtf_gemm_set_stream(int);
-void dtf_gemm_stream_bnb(const bf16_t*, const bf16_t*, bf16_t*, int, int, int, int, int, int,
-                         const bf16_t*, const bf16_t*, const uint8_t*, const bf16_t*,
-                         const float*, const float*, const float*, const float*, const uint8_t*,
-                         int, float*, int, hipStream_t, const bf16_t*, const bf16_t*, int);
-bool dtf_gemm_stream_ok(int, int, int, int, int, int);
-void dtf_gemm_stream_apply(const bf16_t*, const bf16_t*, bf16_t*, int, int, int, const bf16_t*,
-                           const float*, const float*, uint8_t*, hipStream_t);
-void dtf_gemm_stream_bnb_dual(const bf16_t*, const bf16_t*, bf16_t*, int, int, int, int, int, int,
-                              const bf16_t*, const bf16_t*, const uint8_t*, const bf16_t*,
-                              const float*, const float*, const uint8_t*, float*, const bf16_t*,
-                              const float*, const float*, float*, hipStream_t);
-void dtf_gemm_stream_probe(const bf16_t*, const bf16_t*, bf16_t*, int, int, int, hipStream_t);
-void dtf_gemm_stream_pre(const bf16_t*, const bf16_t*, bf16_t*, int, int, int, const float*,
-                         const float*, bf16_t*, float*, hipStream_t, int);
-void dtf_gemm_set_stagger(int, int);
-void dtf_gemm_set_group(int);
-int dtf_wgrad_get_pipe();
-void dtf_lds_probe(int, int, int*, int, hipStream_t);
-int dtf_max_dynamic_lds(int);
-// transformer kernels (nlp.hip)
-void dtf_ln_fwd(const bf16_t*, const float*, const bf16_t*, const float*, const float*, bf16_t*,
-                bf16_t*, float*, float*, int, int, float, float, uint32_t, float, uint32_t,
-                const int64_t*, const int64_t*, const bf16_t*, const bf16_t*, const bf16_t*, int,
-                hipStream_t);
-int dtf_ln_bwd_blocks(int);
-void dtf_ln_set_wide(int);
-void dtf_ln_bwd(const bf16_t*, const bf16_t*, const float*, const float*, const float*, bf16_t*,
-                bf16_t*, float*, float*, float*, float*, int, int, float, uint32_t, float,
-                uint32_t, hipStream_t, int);
-void dtf_bias_gelu_fwd(const bf16_t*, const float*, bf16_t*, long, int, hipStream_t);
-int dtf_bias_gelu_bwd_blocks(int);
-int dtf_bf16_col_sum_ws_floats(int);
-void dtf_bf16_col_sum(const bf16_t*, int, int, float*, float*, int, hipStream_t);
-void dtf_slab_reduce(const float*, float*, long, int, int, hipStream_t);
-// fused first-stage c3 backward (conv1x1_bwd.hip)
-bool dtf_conv1x1_bwd_ok(int, int, int);
-int dtf_conv1x1_bwd_blocks(int, int);
-void dtf_conv1x1_bwd_set_grid(int);
-void dtf_conv1x1_bwd_set_w16(int);
-bool dtf_conv1x1_bwd_lazy_ok(int, int, int);
-int dtf_conv1x1_bwd_lazy_blocks(int, int);
-void dtf_conv1x1_bwd_lazy(const bf16_t*, const bf16_t*, const uint8_t*, const float*, const float*,
-                          const float*, const bf16_t*, const bf16_t*, const bf16_t*, const float*,
-                          const float*, const float*, const float*, bf16_t*, float*, float*, int,
-                          int, int, const bf16_t*, hipStream_t);
-void dtf_conv1x1_bwd(const bf16_t*, const bf16_t*, const bf16_t*, const bf16_t*, const float*,
-                     const float*, const float*, const float*, bf16_t*, float*, float*, int, int,
-                     int, hipStream_t);
-void dtf_bias_gelu_bwd(const bf16_t*, const bf16_t*, const float*, bf16_t*, float*, float*, int,
-                       int, hipStream_t, int);
-void dtf_attn_fwd(const bf16_t*, const float*, bf16_t*, float*, int, int, int, float, float,
-                  uint32_t, hipStream_t, uint32_t*);
-long dtf_attn_keep_words(int, int, int, float);
-void dtf_attn_set_keep(int);
-void dtf_attn_bwd(const bf16_t*, const float*, const bf16_t*, const bf16_t*, const float*, float*,
-                  bf16_t*, int, int, int, float, float, uint32_t, hipStream_t, float*,
-                  const uint32_t*);
-int dtf_attn_bwd_fused(int);
-int dtf_pos_type_grad_ws_floats(int, int, int);
-void dtf_attn_set_wide(int);
-void dtf_attn_set_fused(int);
-void dtf_pos_type_grad(const bf16_t*, const int64_t*, int, int, int, int, float*, float*, float*,
-                       hipStream_t);
-void dtf_segment_sum(const int64_t*, const int64_t*, const bf16_t*, float*, int, int,
-                     hipStream_t);
-void dtf_mlm_xent(const bf16_t*, const int64_t*, const float*, const float*, int, int, int,
-                  float*, bf16_t*, hipStream_t);
-
-// ---- dense GEMM (gemm.hip)
-void dtf_gemm_nt_bias_gelu(const bf16_t*, const bf16_t*, bf16_t*, bf16_t*, int, int, int, int,
-                           int, const float*, hipStream_t);
-void dtf_gemm_nt_gelu_bwd(const bf16_t*, const bf16_t*, bf16_t*, int, int, int, int, int,
-                          const bf16_t*, const float*, float*, hipStream_t);
-void dtf_gemm_nt(const bf16_t*, const bf16_t*, bf16_t*, int, int, int, int, int, int,
-                 const float*, const bf16_t*, int, float*, hipStream_t, const bf16_t*,
-                 const uint8_t*);
-int dtf_gemm_tile_rows(int);
-void dtf_gemm_set_variant(int);
-void dtf_gemm_set_pp(int);
-void dtf_gemm_set_pp2(int);
-int dtf_gemm_get_pp2();
-bool dtf_gemm_pp2_ok(int M, int N, int K, int lda, int ldb);
-int dtf_bias_relu_bwd_ws_floats(int);
-void dtf_gather_u8_scale(const uint8_t*, const int64_t*, void*, int, int, float, int, hipStream_t);
-// ---- fp32 path (f32.hip)
-void dtf_gemm_f32(const float*, const float*, float*, const float*, int, int, int, long, long,
-                  long, long, long, long, float, int, int, float*, hipStream_t);
-int dtf_gemm_f32_splits(int, int, int);
-void dtf_im2col_f32(const float*, float*, int, int, int, int, int, int, int, int, int, int, int,
-                    int, hipStream_t);
-void dtf_col2im_f32(const float*, float*, int, int, int, int, int, int, int, int, int, int, int,
-                    int, hipStream_t);
-void dtf_maxpool_f32_fwd(const float*, float*, uint8_t*, int, int, int, int, int, int, int, int,
-                         hipStream_t);
-void dtf_maxpool_f32_bwd(const float*, const uint8_t*, float*, int, int, int, int, int, int, int,
-                         int, hipStream_t);
-int dtf_bias_relu_bwd_f32_ws_floats(int);
-void dtf_bias_relu_bwd_f32(const float*, const float*, float*, int, int, float*, float*, int, int,
-                           hipStream_t);
-void dtf_clipped_xent(const float*, const float*, int, int, float*, float*, float, hipStream_t);
-void dtf_bias_relu_bwd(const bf16_t*, const bf16_t*, bf16_t*, int, int, float*, float*, int, int,
-                       hipStream_t);
-
-// ---- HIP IPC buffers (ipc.cpp) handed to torch as DLPack capsules
-uintptr_t dtf_ipc_alloc(size_t, int);
-std::string dtf_ipc_handle(uintptr_t, int);
-uintptr_t dtf_ipc_open(const std::string&, int);
-void dtf_ipc_close(uintptr_t, int);
-void dtf_ipc_free(uintptr_t, int);
 
 namespace dlp {   // DLPack ABI (v0.8 DLManagedTensor, "dltensor" capsule)
 struct Device { int32_t device_type; int32_t device_id; };
@@ -331,20 +73,27 @@ static TT make_taps(const std::vector<int>& dh, const std::vector<int>& dw) {
   return t;
 }
 
-// rccl_comm.cpp: native RCCL communicator
-int dtf_rccl_load(const std::string& path);
-std::string dtf_rccl_unique_id();
-long dtf_rccl_comm_init(const std::string& uid, int nranks, int rank, int device);
-void dtf_rccl_comm_destroy(long comm, int abort);
-int dtf_rccl_async_error(long comm);
-void dtf_rccl_all_reduce(long comm, long send, long recv, long count, int dtype, int op, long stream);
-void dtf_rccl_reduce_scatter(long comm, long send, long recv, long recvcount, int dtype, int op,
-                             long stream);
-void dtf_rccl_all_gather(long comm, long send, long recv, long sendcount, int dtype, long stream);
-void dtf_rccl_broadcast(long comm, long send, long recv, long count, int dtype, int root, long stream);
-void dtf_rccl_reduce(long comm, long send, long recv, long count, int dtype, int op, int root,
-                     long stream);
-void dtf_rccl_group(int start);
+// geom = [N, H, W, C, P, Q, sh, sw, Kout, Kpad, Ho, Wo, osh, osw, oh0, ow0] (+ acc, default 0);
+// the pointer / epilogue fields stay null for the caller to fill
+static ConvGeom conv_geom(const char* who, const std::vector<int>& geom) {
+  if (geom.size() != 16 && geom.size() != 17)
+    throw std::runtime_error(std::string(who) + ": geom needs 16 (+acc) ints");
+  return ConvGeom{geom[0], geom[1], geom[2],  geom[3],  geom[4],  geom[5],  geom[6],  geom[7],
+                  geom[8], geom[9], geom[10], geom[11], geom[12], geom[13], geom[14], geom[15],
+                  geom.size() == 17 ? geom[16] : 0};
+}
+
+// bnb = [x, mean, invstd, fsc, fsh, mask, part, mkind] (+ row0 when entries == 9: fused
+// BN-backward sums), or [] for none
+static BnBwdEpi bnb_epi(const char* who, const std::vector<uintptr_t>& bnb, size_t entries) {
+  if (bnb.empty()) return BnBwdEpi{};
+  if (bnb.size() != entries)
+    throw std::runtime_error(std::string(who) + ": bnb needs " + std::to_string(entries) +
+                             " entries");
+  return BnBwdEpi{P<const bf16_t>(bnb[0]), P<const float>(bnb[1]), P<const float>(bnb[2]),
+                  P<const float>(bnb[3]), P<const float>(bnb[4]), P<const uint8_t>(bnb[5]),
+                  P<float>(bnb[6]), (int)bnb[7], entries == 9 ? (int)bnb[8] : 0};
+}
 
 PYBIND11_MODULE(_dtf_hip, m) {
   m.def("rccl_load", &dtf_rccl_load);
@@ -473,11 +222,7 @@ PYBIND11_MODULE(_dtf_hip, m) {
   m.def("gemm_stream_set_bnb_probe", &dtf_gemm_stream_set_bnb_probe);
   m.def("conv_tile_rows", [](std::vector<int> geom, std::vector<int> dh, std::vector<int> dw,
                              int bnb) {
-    if (geom.size() != 16 && geom.size() != 17)
-      throw std::runtime_error("conv_tile_rows: geom needs 16 (+acc) ints");
-    ConvGeom g{geom[0], geom[1], geom[2],  geom[3],  geom[4],  geom[5],  geom[6],  geom[7],
-               geom[8], geom[9], geom[10], geom[11], geom[12], geom[13], geom[14], geom[15],
-               geom.size() == 17 ? geom[16] : 0};
+    const ConvGeom g = conv_geom("conv_tile_rows", geom);   // checked before the taps
     return dtf_conv_tile_rows(g, make_taps<TapTable>(dh, dw), bnb);
   }, py::arg("geom"), py::arg("dh"), py::arg("dw"), py::arg("bnb") = 0);
   m.def("conv_set_halo_bnb", &dtf_conv_set_halo_bnb);
@@ -730,25 +475,17 @@ PYBIND11_MODULE(_dtf_hip, m) {
                          uintptr_t stats, std::vector<uintptr_t> bnb, uintptr_t acc_src,
                          uintptr_t acc_mask, uintptr_t bias, int relu, uintptr_t bnl_sc,
                          uintptr_t bnl_sh, uintptr_t bnl_y) {
-    if (geom.size() != 16 && geom.size() != 17)
-      throw std::runtime_error("conv_igemm: geom needs 16 (+acc) ints");
-    ConvGeom g{geom[0], geom[1], geom[2],  geom[3],  geom[4],  geom[5],  geom[6],  geom[7],
-               geom[8], geom[9], geom[10], geom[11], geom[12], geom[13], geom[14], geom[15],
-               geom.size() == 17 ? geom[16] : 0, P<const bf16_t>(acc_src),
-               P<const uint8_t>(acc_mask), P<const float>(bias), relu};
+    ConvGeom g = conv_geom("conv_igemm", geom);
+    g.acc_src = P<const bf16_t>(acc_src);
+    g.acc_mask = P<const uint8_t>(acc_mask);
+    g.bias = P<const float>(bias);
+    g.relu = relu;
     if (g.acc == 2 && (!g.acc_src || !g.acc_mask))
       throw std::runtime_error("conv_igemm: acc 2 needs acc_src and acc_mask");
     g.lsc = P<const float>(bnl_sc);
     g.lsh = P<const float>(bnl_sh);
     g.ly = P<bf16_t>(bnl_y);
-    // bnb = [x, mean, invstd, fsc, fsh, mask, part, mkind, row0] (fused BN-backward sums) or []
-    BnBwdEpi e{};
-    if (!bnb.empty()) {
-      if (bnb.size() != 9) throw std::runtime_error("conv_igemm: bnb needs 9 entries");
-      e = BnBwdEpi{P<const bf16_t>(bnb[0]), P<const float>(bnb[1]), P<const float>(bnb[2]),
-                   P<const float>(bnb[3]), P<const float>(bnb[4]), P<const uint8_t>(bnb[5]),
-                   P<float>(bnb[6]), (int)bnb[7], (int)bnb[8]};
-    }
+    const BnBwdEpi e = bnb_epi("conv_igemm", bnb, 9);
     dtf_conv_igemm(P<const bf16_t>(x), P<const bf16_t>(w), P<bf16_t>(y), g,
                    make_taps<TapTable>(dh, dw), bk, P<float>(stats), e, S(st));
     check_launch("conv_igemm");
@@ -769,16 +506,8 @@ PYBIND11_MODULE(_dtf_hip, m) {
     if (oh0.size() != n || ow0.size() != n || kpad.size() != n || dh.size() != n ||
         dw.size() != n || (!bnb.empty() && row0.size() != n))
       throw std::runtime_error("conv_igemm_grouped: per-class lists differ in length");
-    ConvGeom g{geom[0], geom[1], geom[2],  geom[3],  geom[4],  geom[5],  geom[6],  geom[7],
-               geom[8], geom[9], geom[10], geom[11], geom[12], geom[13], geom[14], geom[15],
-               geom[16]};
-    BnBwdEpi e{};
-    if (!bnb.empty()) {
-      if (bnb.size() != 8) throw std::runtime_error("conv_igemm_grouped: bnb needs 8 entries");
-      e = BnBwdEpi{P<const bf16_t>(bnb[0]), P<const float>(bnb[1]), P<const float>(bnb[2]),
-                   P<const float>(bnb[3]), P<const float>(bnb[4]), P<const uint8_t>(bnb[5]),
-                   P<float>(bnb[6]), (int)bnb[7], 0};
-    }
+    const ConvGeom g = conv_geom("conv_igemm_grouped", geom);
+    const BnBwdEpi e = bnb_epi("conv_igemm_grouped", bnb, 8);   // row0 comes per class
     std::vector<const bf16_t*> w(n);
     for (size_t i = 0; i < n; ++i) w[i] = P<const bf16_t>(wts[i]);
     const bool ok = dtf_conv_igemm_grouped(P<const bf16_t>(x), P<bf16_t>(y), g, (int)n, w.data(),
@@ -790,11 +519,7 @@ PYBIND11_MODULE(_dtf_hip, m) {
   m.def("gemm_conv_part_images", &dtf_gemm_conv_part_images);
   m.def("gemm_set_pp2_strided", &dtf_gemm_set_pp2_strided);
   m.def("conv_bnl_ok", [](std::vector<int> geom, std::vector<int> dh, std::vector<int> dw) {
-    if (geom.size() != 16 && geom.size() != 17)
-      throw std::runtime_error("conv_bnl_ok: geom needs 16 (+acc) ints");
-    ConvGeom g{geom[0], geom[1], geom[2],  geom[3],  geom[4],  geom[5],  geom[6],  geom[7],
-               geom[8], geom[9], geom[10], geom[11], geom[12], geom[13], geom[14], geom[15],
-               geom.size() == 17 ? geom[16] : 0};
+    const ConvGeom g = conv_geom("conv_bnl_ok", geom);
     return dtf_conv_bnl_ok(g, make_taps<TapTable>(dh, dw));
   });
   m.def("bn_bwd_finalize_g", [](uintptr_t part, int G, long M, int C, uintptr_t gamma,

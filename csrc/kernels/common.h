@@ -41,6 +41,12 @@ DTF_DEV uint4 pack8(const float* f) {
   r.w = pack2(f[6], f[7]);
   return r;
 }
+// 8 consecutive floats p[first_elem .. first_elem + 7] (16-B aligned) as two float4 loads
+DTF_DEV void load8f(const float* __restrict__ p, int first_elem, float* v) {
+  const float4 a = *reinterpret_cast<const float4*>(p + first_elem);
+  const float4 b = *reinterpret_cast<const float4*>(p + first_elem + 4);
+  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
 
 // 16-B store, non-temporal when `nt` (a wave-uniform flag): outputs written once and read by a
 // later kernel pass, far larger than L2 / MALL
@@ -102,7 +108,17 @@ DTF_DEV void dma16(const i32x4_t& r, uint32_t lds, uint32_t voff) {
                "s_mov_b32 m0, %0"
                : "=&s"(save) : "s"(l), "v"(voff), "s"(r) : "memory");
 }
+// The same descriptor as the compiler's resource type, for the raw_buffer_load / store builtins.
+DTF_DEV __amdgpu_buffer_rsrc_t buffer_rsrc(const void* p, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
+}
 #define DTF_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
+// s_waitcnt vmcnt(N) with N a compile-time expression (DTF_WAIT_VM takes a literal)
+template <int N>
+DTF_DEV void wait_vm() {
+  static_assert(N >= 0 && N < 64, "vmcnt range");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
 DTF_DEV void raw_barrier() {
   asm volatile("" ::: "memory");
   __builtin_amdgcn_s_barrier();

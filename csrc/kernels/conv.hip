@@ -37,38 +37,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
-
-#define DTF_MAX_TAPS 64
-
-struct TapTable {
-  int n;
-  int dh[DTF_MAX_TAPS];
-  int dw[DTF_MAX_TAPS];
-};
-
-struct ConvGeom {
-  int N, H, W, C;        // input
-  int P, Q;              // output grid of this launch
-  int sh, sw;            // input stride
-  int Kout;              // output channels (GEMM N)
-  int Kpad;              // filter row stride (T*C rounded up to BK)
-  int Ho, Wo;            // output tensor spatial dims
-  int osh, osw, oh0, ow0;// output placement
-  int acc;               // 1: Y += result (dgrad accumulating onto a residual gradient)
-                         // 2: Y = result + acc_src * relu_mask (see acc_add8)
-  const bf16_t* acc_src; // acc 2: the residual BN's incoming dy, [N, Ho, Wo, Kout] like Y
-  const uint8_t* acc_mask;  // acc 2: that BN's forward ReLU bit mask (1 byte per 8 channels)
-  const float* bias;        // fused epilogue (register kernel only): Y = act(conv + bias[k])
-  int relu;                 //   tf.layers.conv2d(activation=tf.nn.relu) -- MNIST K3/K5
-  int nt;                   // non-temporal output stores (set by dtf_conv_igemm)
-  // BN + ReLU on load (halo kernels, forward): X is a BatchNorm INPUT; the kernel normalises its
-  // patch in LDS with y = bf16(max(x * lsc[c] + lsh[c], 0)) -- the apply pass's arithmetic -- and
-  // writes the rows it owns to ly (the weight gradient's operand), so the apply pass never runs
-  const float* lsc;
-  const float* lsh;
-  bf16_t* ly;
-};
+#include "launch.h"
 
 // Residual-gradient accumulation in the dgrad epilogue.  acc 1 reads the materialised residual
 // gradient back from Y; acc 2 forms it on the fly as dy * relu_mask from the residual BN's own
@@ -90,38 +59,15 @@ DTF_DEV uint4 acc_add8(const ConvGeom& g, const bf16_t* Y, long off, uint4 v) {
   return pack8(a);
 }
 
-// Fused BatchNorm-backward statistics in the DATA-GRADIENT epilogue: when this launch produces
-// dy of a training-mode BN's output (the BN sits right before this conv in the forward pass), the
-// epilogue also accumulates, per channel, sum(dz) and sum(dz * (x - mean) * invstd) with
-// dz = dy * relu_mask(x) -- exactly bn_reduce_kernel<1>'s sums, from the bf16-ROUNDED final dy
-// (after a fused residual accumulation) -- into row `row0 + tile` of a [rows][2][Kout] slab the
-// BN's finalize combines.  Saves the backward reduce pass its full re-read of dy.
+// short-reduction variants
 // bit 0: one LDS stage when the whole reduction is one K-step; bit 1: BK 32 for 1x1 convs with
 // C <= 128; bit 2: BK 32 for every 1x1; bit 3: BK 32 for every register-kernel conv; bit 4:
 // the <= 128-VGPR (4 waves/SIMD) build of the BK-32 kernels (see dtf_conv_igemm)
 static int g_small_k = 31;  // bits 0-4: same-box A/B +2.4 % (bit 2), +2.0 % (bit 4), +0.5 % (bit 3)
 
-struct BnBwdEpi {
-  const bf16_t* x;          // BN input, same [N, Ho, Wo, Kout] layout as Y
-  const float* mean;
-  const float* invstd;
-  const float* fsc;         // forward scale / shift (mask recomputed from x, mkind 2)
-  const float* fsh;
-  const uint8_t* mask;      // ReLU bit mask (mkind 1)
-  float* part;              // null: off
-  int mkind;                // 0 no ReLU, 1 bit mask, 2 from x
-  int row0;
-};
-
 namespace {
 
 constexpr int kThreads = 256;
-
-DTF_DEV void load8(const float* __restrict__ p, int c, float* v) {
-  const float4 a = *reinterpret_cast<const float4*>(p + c);
-  const float4 b = *reinterpret_cast<const float4*>(p + c + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
 
 // per-thread BN-backward partial sums of one 8-channel column chunk
 struct BnbAcc {
@@ -130,9 +76,9 @@ struct BnbAcc {
 #pragma unroll
     for (int i = 0; i < 8; ++i) { s0[i] = 0.f; s1[i] = 0.f; mu[i] = 0.f; is[i] = 0.f; sc[i] = 0.f; sh[i] = 0.f; }
     if (!ok) return;
-    load8(e.mean, c, mu);
-    load8(e.invstd, c, is);
-    if (e.mkind == 2) { load8(e.fsc, c, sc); load8(e.fsh, c, sh); }
+    load8f(e.mean, c, mu);
+    load8f(e.invstd, c, is);
+    if (e.mkind == 2) { load8f(e.fsc, c, sc); load8f(e.fsh, c, sh); }
   }
   DTF_DEV void add(const BnBwdEpi& e, long off, const uint4& v) {
     float g[8], xv[8];
@@ -195,9 +141,6 @@ DTF_DEV int swz_chunk(int row, int chunk) {
   return chunk ^ ((row / RPB) % CPR);
 }
 
-DTF_DEV __amdgpu_buffer_rsrc_t rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
 DTF_DEV uint4 bload16(__amdgpu_buffer_rsrc_t r, uint32_t off) {
   return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
@@ -243,8 +186,8 @@ conv_igemm_body(const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wt,
   const int n_lo = m0 / PQ;
   const int n_hi = min(g.N - 1, (min(m0 + BM, M) - 1) / PQ);
   const long img = (long)g.H * g.W * g.C;
-  const auto rx = rsrc(X + n_lo * img, (uint32_t)((n_hi - n_lo + 1) * img * 2));
-  const auto rw = rsrc(Wt, (uint32_t)g.Kout * g.Kpad * 2u);
+  const auto rx = buffer_rsrc(X + n_lo * img, (uint32_t)((n_hi - n_lo + 1) * img * 2));
+  const auto rw = buffer_rsrc(Wt, (uint32_t)g.Kout * g.Kpad * 2u);
 
   if constexpr (GATHER != 0) {
     if (tid == 0)
@@ -1553,7 +1496,6 @@ int dtf_conv_stats_rows(long M, int Kout, int C, int taps, int W) {
 // kernel (256 x 256 tiles, 1.2-1.3 PF on long-K GEMMs vs ~0.9 for the 256 x 128 DMA kernel)
 static int g_conv_gemm = 1;
 void dtf_conv_set_gemm(int v) { g_conv_gemm = v; }
-int dtf_gemm_conv_part_images(int N, int H, int W, int C, int P, int Q);
 static bool use_conv_gemm(const ConvGeom& g, const TapTable& taps) {
   const bool unit = g.osh == 1 && g.osw == 1 && g.oh0 == 0 && g.ow0 == 0 && g.Ho == g.P &&
                     g.Wo == g.Q;
@@ -1572,11 +1514,6 @@ static bool use_conv_gemm(const ConvGeom& g, const TapTable& taps) {
          (unit ? (taps.n > 1 || proj) : g.acc != 2) && g.Kpad == taps.n * g.C && !g.bias &&
          !g.relu && g.H < 16384 && g.W < 32768;
 }
-void dtf_gemm_conv(const bf16_t* X, const bf16_t* Wt, bf16_t* Y, int N, int H, int W, int C,
-                   int P, int Q, int sh, int sw, int Kout, int ntaps, const int* dh, const int* dw,
-                   int Ho, int Wo, int osh, int osw, int oh0, int ow0,
-                   float* stats, const bf16_t* Cin, const bf16_t* acc_src,
-                   const uint8_t* acc_mask, hipStream_t st);
 
 // M tiles (= BN-statistics slab rows) of exactly the kernel dtf_conv_igemm will pick for this
 // forward launch (no fused BN-backward epilogue)
@@ -1784,15 +1721,6 @@ bool dtf_conv_igemm_grouped(const bf16_t* X, bf16_t* Y, const ConvGeom& g0, int 
 // (53 launches / ResNet-50 step).  Block = one 64 x 64 (k, c) tile of one tap of one filter,
 // staged through a padded LDS tile so both the reads (along c) and the writes (along k) are
 // coalesced.  Jobs are found by a scan of the (<= kWtMaxJobs) cumulative tile counts.
-constexpr int kWtMaxJobs = 48;
-struct WtJobs {
-  const bf16_t* src[kWtMaxJobs];
-  bf16_t* dst[kWtMaxJobs];
-  int K[kWtMaxJobs], T[kWtMaxJobs], C[kWtMaxJobs];
-  int tile_end[kWtMaxJobs];     // exclusive prefix sum of T * ceil(K/64) * ceil(C/64)
-  int n;
-};
-
 namespace {
 __global__ void __launch_bounds__(256) filter_transpose_kernel(const WtJobs jobs) {
   __shared__ bf16_t tile[64][66];

@@ -31,7 +31,7 @@
 #include <stdexcept>
 #include <string>
 
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -115,12 +115,6 @@ DTF_DEV s4_t tr4(const bf16_t* base, int col0, int lane) {
 
 DTF_DEV f32x4_t mfma16(const bf16x8_t& a, const bf16x8_t& b, const f32x4_t& c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-template <int N>
-DTF_DEV void wait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 template <class F>

@@ -13,25 +13,7 @@
 #include <stdexcept>
 #include <string>
 
-#include "common.h"
-
-#define DTF_MAX_TAPS 64
-
-struct TapTableW {
-  int n;
-  int dh[DTF_MAX_TAPS];
-  int dw[DTF_MAX_TAPS];
-};
-
-struct WgradGeom {
-  int N, H, W, C;   // input X
-  int P, Q;         // dY spatial
-  int sh, sw;
-  int Kout;
-  int ldw;          // dW row stride (>= T*C)
-  long m_per_split; // reduction pixels per split (multiple of BKM)
-  long slab;        // floats per split slab (Kout * ldw)
-};
+#include "launch.h"
 
 namespace {
 constexpr int kThreads = 256;
@@ -50,9 +32,6 @@ typedef __attribute__((ext_vector_type(4))) short s4_t;
 typedef __attribute__((address_space(3))) s4_t lds_s4_t;
 constexpr uint32_t kOOB = 0xFFFFFFF0u;   // byte offset the buffer range check always rejects
 
-DTF_DEV __amdgpu_buffer_rsrc_t rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
 DTF_DEV uint4 bload16(__amdgpu_buffer_rsrc_t r, uint32_t off) {
   return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
@@ -109,8 +88,8 @@ conv_wgrad_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ dY,
   const int PQ = g.P * g.Q;
   const int n_lo = ms / PQ, n_hi = max(n_lo, (me - 1) / PQ);
   const long img = (long)g.H * g.W * g.C;
-  const auto rx = rsrc(X + n_lo * img, (uint32_t)((n_hi - n_lo + 1) * img * 2));
-  const auto ry = rsrc(dY + (long)ms * g.Kout, (uint32_t)max(me - ms, 0) * g.Kout * 2u);
+  const auto rx = buffer_rsrc(X + n_lo * img, (uint32_t)((n_hi - n_lo + 1) * img * 2));
+  const auto ry = buffer_rsrc(dY + (long)ms * g.Kout, (uint32_t)max(me - ms, 0) * g.Kout * 2u);
   const int HW = g.H * g.W;
 
   // branch-free loads: padding / out-of-range lanes get an out-of-range buffer offset -> zeros

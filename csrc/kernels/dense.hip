@@ -9,7 +9,7 @@
 // autograd's ReluGrad kernel + a separate BiasAddGrad reduction over the same tensor.
 #include <stdexcept>
 
-#include "common.h"
+#include "launch.h"
 
 namespace {
 

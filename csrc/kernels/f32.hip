@@ -19,7 +19,7 @@
 //     clipped-log softmax cross-entropy (templates/00_mnist_replica.py:160-164) fwd + bwd.
 #include <stdexcept>
 
-#include "common.h"
+#include "launch.h"
 
 typedef __attribute__((ext_vector_type(4))) float f32x4v;
 

@@ -26,7 +26,7 @@
 #include <stdexcept>
 #include <string>
 
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -68,17 +68,6 @@ template <int BK>
 DTF_DEV int gswz(int row, int ch) {
   constexpr int CPR = BK / 8, RPB = 16 / CPR;
   return ch ^ ((row / RPB) % CPR);
-}
-
-// s_waitcnt vmcnt(N) with N a template literal
-template <int N>
-DTF_DEV void wait_vm() {
-  static_assert(N == 0 || N == 6 || N == 8 || N == 12 || N == 16, "add the wait count");
-  if constexpr (N == 0) DTF_WAIT_VM(0);
-  else if constexpr (N == 6) DTF_WAIT_VM(6);
-  else if constexpr (N == 8) DTF_WAIT_VM(8);
-  else if constexpr (N == 12) DTF_WAIT_VM(12);
-  else DTF_WAIT_VM(16);
 }
 
 // BM x BN block tile, BK-deep K-steps, NS-slot LDS ring (DMAs issued NS-1 steps ahead), NW waves.
@@ -1901,8 +1890,6 @@ void dtf_gemm_conv(const bf16_t* X, const bf16_t* Wt, bf16_t* Y, int N, int H, i
 // dX = dY . W (gemm_nt form, B = W^T rows) for a data gradient that feeds a GELU: the epilogue
 // applies gelu'(a + b) and leaves the per-tile column sums of the result (the GELU bias's
 // gradient, first level) in colsum [dtf_gemm_tile_rows(M)][N]; C and a dense [M][N].
-bool dtf_gemm_pp2_ok(int M, int N, int K, int lda, int ldb);
-
 void dtf_gemm_nt_gelu_bwd(const bf16_t* A, const bf16_t* B, bf16_t* C, int M, int N, int K,
                           int lda, int ldb, const bf16_t* gelu_a, const float* gelu_b,
                           float* colsum, hipStream_t st) {
@@ -1939,11 +1926,6 @@ void dtf_gemm_nt_bias_gelu(const bf16_t* A, const bf16_t* B, bf16_t* Z, bf16_t* 
     launch_gemm_pp2<0>(g, (long)(M - 1) * lda * 2 + 2L * K, (long)(N - 1) * ldb * 2 + 2L * K, st);
   else launch_gemm<256, 256, 64, 2, 2>(g, st);
 }
-
-bool dtf_gemm_stream_ok(int M, int N, int K, int lda, int ldb, int ldc);
-void dtf_gemm_stream(const bf16_t* A, const bf16_t* B, bf16_t* C, int M, int N, int K, int lda,
-                     int ldb, int ldc, const bf16_t* Cin, float* stats, const bf16_t* acc_src,
-                     const uint8_t* acc_mask, int nt, hipStream_t st);
 
 // the persistent kernel gemm_pp2 takes this dense GEMM: K % 64 == 0, K >= 128, whole operands
 // addressable with 32-bit buffer offsets

@@ -31,7 +31,7 @@
 #include <stdexcept>
 #include <string>
 
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -86,17 +86,6 @@ struct StreamArgs {
 };
 
 DTF_DEV int sswz(int row, int ch) { return ch ^ ((row >> 1) & 7); }   // 64-deep panel swizzle
-
-DTF_DEV __amdgpu_buffer_rsrc_t srsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
-
-// s_waitcnt vmcnt(N), N a compile-time count
-template <int N>
-DTF_DEV void wait_vmc() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // MODE: 0 plain, 1 + Cin, 2 + acc_src * relu_bit; STATS: BN statistics slab of the output;
 // BMK >= 0: BN-backward sums of the output (0 no ReLU, 1 ReLU bit mask, 2 ReLU from x)
@@ -154,7 +143,7 @@ __global__ void __launch_bounds__(kST, 1) gemm_stream_kernel(const StreamArgs g)
 
   // A: this wave's 32 rows x K, straight into MFMA operand registers
   const __amdgpu_buffer_rsrc_t ra =
-      srsrc(g.A + m0 * g.lda, (uint32_t)(((long)(rows_blk - 1) * g.lda + K) * 2));
+      buffer_rsrc(g.A + m0 * g.lda, (uint32_t)(((long)(rows_blk - 1) * g.lda + K) * 2));
   bf16x8_t af[2][KS];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -171,7 +160,7 @@ __global__ void __launch_bounds__(kST, 1) gemm_stream_kernel(const StreamArgs g)
   bf16x8_t yf[2][KS3R];
   if constexpr (K3 > 0) {
     const __amdgpu_buffer_rsrc_t ry2 =
-        srsrc(g.y2 + m0 * K3, (uint32_t)(((long)(rows_blk - 1) * K3 + K3) * 2));
+        buffer_rsrc(g.y2 + m0 * K3, (uint32_t)(((long)(rows_blk - 1) * K3 + K3) * 2));
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int r = wave * kSWR + i * 16 + frow;
@@ -214,17 +203,17 @@ __global__ void __launch_bounds__(kST, 1) gemm_stream_kernel(const StreamArgs g)
 
   // epilogue addressing: lane -> rows t * 8 + lane / 8 (t < 4) of the wave's 32, 16-B chunk lane % 8
   const long ldc = g.ldc;
-  const __amdgpu_buffer_rsrc_t rc = srsrc(g.C + m0 * ldc, (uint32_t)(rows_blk * ldc * 2));
+  const __amdgpu_buffer_rsrc_t rc = buffer_rsrc(g.C + m0 * ldc, (uint32_t)(rows_blk * ldc * 2));
   const __amdgpu_buffer_rsrc_t rcin =
-      srsrc(mode == 1 || mode == 3 ? (const void*)(g.Cin + m0 * ldc)
-                                   : (const void*)(g.acc_src + m0 * ldc),
-            mode ? (uint32_t)(rows_blk * ldc * 2) : 0u);
+      buffer_rsrc(mode == 1 || mode == 3 ? (const void*)(g.Cin + m0 * ldc)
+                                         : (const void*)(g.acc_src + m0 * ldc),
+                  mode ? (uint32_t)(rows_blk * ldc * 2) : 0u);
   const __amdgpu_buffer_rsrc_t ramask =
-      srsrc(mode == 3 ? (const void*)(g.amask + m0 * ldc / 8) : (const void*)g.C,
-            mode == 3 ? (uint32_t)(rows_blk * ldc / 8) : 0u);
+      buffer_rsrc(mode == 3 ? (const void*)(g.amask + m0 * ldc / 8) : (const void*)g.C,
+                  mode == 3 ? (uint32_t)(rows_blk * ldc / 8) : 0u);
   const __amdgpu_buffer_rsrc_t rmask =
-      srsrc(mode == 2 ? (const void*)(g.acc_mask + m0 * ldc / 8) : (const void*)g.C,
-            mode == 2 ? (uint32_t)(rows_blk * ldc / 8) : 0u);
+      buffer_rsrc(mode == 2 ? (const void*)(g.acc_mask + m0 * ldc / 8) : (const void*)g.C,
+                  mode == 2 ? (uint32_t)(rows_blk * ldc / 8) : 0u);
   const int er = lane >> 3, ec = lane & 7;
   auto eoff = [&](int t, int c) -> uint32_t {     // byte offset of (row, chunk) in C / Cin
     const int rr = wave * kSWR + t * 8 + er;
@@ -233,14 +222,14 @@ __global__ void __launch_bounds__(kST, 1) gemm_stream_kernel(const StreamArgs g)
   uint4 pre[S], bxp[S], bpp[S];
   uint32_t pmask[S], bmp[S];
   const __amdgpu_buffer_rsrc_t rbx =
-      srsrc(BNB && K3 == 0 ? (const void*)(g.bx + m0 * ldc) : (const void*)g.C,
-            BNB ? (uint32_t)(rows_blk * ldc * 2) : 0u);
+      buffer_rsrc(BNB && K3 == 0 ? (const void*)(g.bx + m0 * ldc) : (const void*)g.C,
+                  BNB ? (uint32_t)(rows_blk * ldc * 2) : 0u);
   const __amdgpu_buffer_rsrc_t rbm =
-      srsrc(BMK == 1 ? (const void*)(g.bmask + m0 * ldc / 8) : (const void*)g.C,
-            BMK == 1 ? (uint32_t)(rows_blk * ldc / 8) : 0u);
+      buffer_rsrc(BMK == 1 ? (const void*)(g.bmask + m0 * ldc / 8) : (const void*)g.C,
+                  BMK == 1 ? (uint32_t)(rows_blk * ldc / 8) : 0u);
   const __amdgpu_buffer_rsrc_t rbp =
-      srsrc(DUAL ? (const void*)(g.bxp + m0 * ldc) : (const void*)g.C,
-            DUAL ? (uint32_t)(rows_blk * ldc * 2) : 0u);
+      buffer_rsrc(DUAL ? (const void*)(g.bxp + m0 * ldc) : (const void*)g.C,
+                  DUAL ? (uint32_t)(rows_blk * ldc * 2) : 0u);
   auto prefetch = [&](int c) {
     if constexpr (L == 0) return;
     const int cc = c < nch ? c : 0;
@@ -283,7 +272,7 @@ __global__ void __launch_bounds__(kST, 1) gemm_stream_kernel(const StreamArgs g)
     // flight; the scale / shift reads wait for the A rows, in issue order), stored once as the
     // weight gradient's operand
     const __amdgpu_buffer_rsrc_t ry =
-        srsrc(g.pre_y + m0 * g.lda, (uint32_t)(((long)(rows_blk - 1) * g.lda + K) * 2));
+        buffer_rsrc(g.pre_y + m0 * g.lda, (uint32_t)(((long)(rows_blk - 1) * g.lda + K) * 2));
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int k0 = ks * 32 + fq * 8;
@@ -312,9 +301,9 @@ __global__ void __launch_bounds__(kST, 1) gemm_stream_kernel(const StreamArgs g)
   bf16_t* ws = stg + wave * kSWR * kSP;
   for (int c = 0; c < nch; ++c) {
     // this wave's DMAs of chunk c landed (everything issued after them may still fly) ...
-    if (c >= 2) wait_vmc<2 * SST + 2 * L + D>();
-    else if (c == 1) wait_vmc<2 * L + D + SST + Y>();
-    else wait_vmc<D + L + Y>();
+    if (c >= 2) wait_vm<2 * SST + 2 * L + D>();
+    else if (c == 1) wait_vm<2 * L + D + SST + Y>();
+    else wait_vm<D + L + Y>();
     if constexpr (HASPRM) {
       if (c == 0 && tid * 4 < g.N) {
 #pragma unroll
@@ -426,7 +415,7 @@ __global__ void __launch_bounds__(kST, 1) gemm_stream_kernel(const StreamArgs g)
       for (int t = 0; t < S; ++t)
         bxp[t] = *reinterpret_cast<const uint4*>(ws + (t * 8 + er) * kSP + ec * 8);
     }
-    if constexpr (L != 0) wait_vmc<D>();      // this chunk's prefetched epilogue operands
+    if constexpr (L != 0) wait_vm<D>();      // this chunk's prefetched epilogue operands
     float b1[8], b2[8], b3[8], bmu[8], bis[8], bsc[8], bsh[8];
     if constexpr (BNB) {
 #pragma unroll

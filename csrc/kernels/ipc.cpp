@@ -14,6 +14,8 @@
 #include <stdexcept>
 #include <string>
 
+#include "launch.h"
+
 namespace {
 void ok(hipError_t e, const char* what) {
   if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));

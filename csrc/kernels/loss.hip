@@ -9,7 +9,7 @@
 //   grad_b,i = (p_i - (1-e) [i = label] - e/V) / B
 // It is the SMOOTH instantiation of the same kernel (sum_i x_i rides the first sweep); e = 0
 // launches the plain instantiation, whose code and results are unchanged.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 template <typename LT, bool SMOOTH>

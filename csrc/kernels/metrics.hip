@@ -27,7 +27,7 @@
 // rows; rows of weight 0 are dropped whatever their loss holds.  Fixed order -- thread t adds
 // rows t, t+256, ... in fp64, a fixed LDS tree, thread 0 adds to the state -- and no atomics:
 // two runs give a bit-identical state, and with 0/1 weights the hit counts are exact integers.
-#include "common.h"
+#include "launch.h"
 
 #include <stdexcept>
 #include <string>
@@ -116,8 +116,7 @@ eval_rows_kernel(const T* __restrict__ base, int off0, uint32_t bytes,
   }
   const int lab = (int)lab_raw;
   const float xl = Elem<T>::one(base + off0 + (long)row * ld + lab);
-  const auto rl = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(base), (short)0, (int)bytes,
-                                                    0x00020000);
+  const auto rl = buffer_rsrc(base, bytes);
   const uint32_t b0 = ((uint32_t)off0 + (uint32_t)row * (uint32_t)ld) * ES;
   const uint32_t a0 = b0 & ~15u;
   const int head = (int)((b0 - a0) / ES);

@@ -23,7 +23,7 @@
 //  * MLM cross-entropy over bf16 logits with per-prediction weights (loss = sum(w*nll)/sum(w)).
 #include <type_traits>
 
-#include "common.h"
+#include "launch.h"
 
 namespace {
 
@@ -1336,8 +1336,7 @@ mlm_xent_kernel(const bf16_t* __restrict__ logits, const int64_t* __restrict__ l
   const int row = (blockIdx.x * 256 + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   if (row >= N) return;
-  const auto rl = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(logits), (short)0,
-                                                    (int)((uint32_t)N * ld * 2u), 0x00020000);
+  const auto rl = buffer_rsrc(logits, (uint32_t)N * ld * 2u);
   const uint32_t b0 = (uint32_t)row * ld * 2u;
   const uint32_t a0 = b0 & ~15u;
   const int head = (int)(b0 - a0) >> 1;

@@ -20,7 +20,7 @@
 // separate cast of the fp32 master every step) and flags non-finite gradients.
 // Hyper-parameters that change per step (lr, lr_t) are read from DEVICE memory so a captured
 // hipGraph replays correctly.
-#include "common.h"
+#include "launch.h"
 
 namespace {
 constexpr int kT = 256;

@@ -2,7 +2,7 @@
 // (no atomics: each input pixel sums the <= ceil(k/s)^2 outputs whose argmax selected it),
 // and global average pool forward/backward.  SURVEY.md K4/K4b/K6 (MNIST 2x2/2) and N-K3
 // (ResNet-50 3x3/2 pad 1, 7x7 global average).  8 channels (16 B) per lane.
-#include "common.h"
+#include "launch.h"
 
 #include <stdexcept>
 
@@ -321,12 +321,6 @@ maxpool3s2_bwd_kernel(const bf16_t* __restrict__ dy, const uint8_t* __restrict__
 // windows' (clamped, preloaded) gradients and argmax words; windows past P / Q are skipped.
 // pool3s2_gather (common.h): the 2 x 2 conv pixels' gradient gathered from the 4 pooled outputs
 
-DTF_DEV void load8(const float* __restrict__ p, int cg, float* v) {
-  const float4 a = reinterpret_cast<const float4*>(p + cg * 8)[0];
-  const float4 b = reinterpret_cast<const float4*>(p + cg * 8)[1];
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-
 template <bool APPLY>
 __global__ void __launch_bounds__(kT)
 pool3s2_bn_bwd_kernel(const bf16_t* __restrict__ dy, const uint8_t* __restrict__ arg,
@@ -341,11 +335,11 @@ pool3s2_bn_bwd_kernel(const bf16_t* __restrict__ dy, const uint8_t* __restrict__
   const uint32_t total = (uint32_t)N * HB * WB * cv;
   const int cg = (int)((blockIdx.x * kT + threadIdx.x) % cv);   // fixed: kT % cv == 0
   float k0[8], k1[8], k2[8], ksc[8], ksh[8], a0[8], a1[8];
-  load8(c0, cg, k0);
-  load8(c1, cg, k1);
-  if (APPLY) load8(c2, cg, k2);
-  load8(fsc, cg, ksc);
-  load8(fsh, cg, ksh);
+  load8f(c0, cg * 8, k0);
+  load8f(c1, cg * 8, k1);
+  if (APPLY) load8f(c2, cg * 8, k2);
+  load8f(fsc, cg * 8, ksc);
+  load8f(fsh, cg * 8, ksh);
 #pragma unroll
   for (int e = 0; e < 8; ++e) { a0[e] = 0.f; a1[e] = 0.f; }
   for (uint32_t i = blockIdx.x * kT + threadIdx.x; i < total; i += gridDim.x * kT) {

@@ -5,7 +5,7 @@
 #include <stdexcept>
 #include <string>
 
-#include "common.h"
+#include "launch.h"
 
 namespace {
 __global__ void lds_probe_kernel(int words, int* errors, int spin) {

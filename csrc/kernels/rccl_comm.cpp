@@ -19,6 +19,8 @@
 #include <stdexcept>
 #include <string>
 
+#include "launch.h"
+
 namespace {
 
 struct RcclApi {

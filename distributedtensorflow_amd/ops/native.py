@@ -36,46 +36,43 @@ except ImportError as e:  # pragma: no cover - exercised on boxes without a buil
 _BF16 = torch.bfloat16
 _DENSE_IMPL = os.environ.get("DTF_DENSE", "native")     # native | library (hipBLASLt)
 
-# kernel-variant switches for A/B runs on one box (defaults = the measured best)
-if os.environ.get("DTF_WGRAD_MODE"):
-    _K.wgrad_set_dma_mode(int(os.environ["DTF_WGRAD_MODE"]))
-if os.environ.get("DTF_WGRAD_PP"):       # ping-pong wgrad: 0 off, n: split-K target of n rounds
-    _K.wgrad_set_pp(int(os.environ["DTF_WGRAD_PP"]))
-if os.environ.get("DTF_WGRAD_DENSE"):    # ping-pong wgrad's decode-free one-tap form: 0 off
-    _K.wgrad_set_dense(int(os.environ["DTF_WGRAD_DENSE"]))
-if os.environ.get("DTF_WGRAD_PIPE"):
-    _K.wgrad_set_pipe(int(os.environ["DTF_WGRAD_PIPE"]))
-if os.environ.get("DTF_CONV_DMA"):
-    _K.conv_set_dma_mode(int(os.environ["DTF_CONV_DMA"]))
-if os.environ.get("DTF_CONV_HALO"):
-    _K.conv_set_halo(int(os.environ["DTF_CONV_HALO"]))
-if os.environ.get("DTF_WGRAD_HALO"):
-    _K.wgrad_set_halo(int(os.environ["DTF_WGRAD_HALO"]))
-if os.environ.get("DTF_CONV_STEM_HALO"):
-    _K.conv_set_stem_halo(int(os.environ["DTF_CONV_STEM_HALO"]))
-if os.environ.get("DTF_CONV_HALO_STRIPS"):     # bit f: two strips per block for halo family f
-    _K.conv_set_halo_strips(int(os.environ["DTF_CONV_HALO_STRIPS"]))
-if os.environ.get("DTF_CONV_HALO_FREG"):       # bit f: halo family f streams its filter via VGPRs
-    _K.conv_set_halo_freg(int(os.environ["DTF_CONV_HALO_FREG"]))
-if os.environ.get("DTF_CONV_SMALL_K"):
-    _K.conv_set_small_k(int(os.environ["DTF_CONV_SMALL_K"]))
-if os.environ.get("DTF_GEMM_STREAM"):   # row-streaming GEMM for output-heavy shapes (default on)
-    _K.gemm_set_stream(int(os.environ["DTF_GEMM_STREAM"]))
-if os.environ.get("DTF_C1_W16"):        # stage-0 fused c3 backward as 16-wave blocks (default 0)
-    _K.conv1x1_bwd_set_w16(int(os.environ["DTF_C1_W16"]))
-if os.environ.get("DTF_GEMM_GROUP_M"):  # grouped tile order of the dense GEMMs (0: N fastest)
-    _K.gemm_set_group(int(os.environ["DTF_GEMM_GROUP_M"]))
-if os.environ.get("DTF_BN_GRID_CAP"):     # BN row-sweep grid cap override (2048 = round-2 grids)
-    _K.bn_set_grid_cap(int(os.environ["DTF_BN_GRID_CAP"]))
-if os.environ.get("DTF_BN_STATS_BLOCKS"):  # BN reduce-pass block target (1024 = round-2)
-    _K.bn_set_stats_blocks(int(os.environ["DTF_BN_STATS_BLOCKS"]))
-if os.environ.get("DTF_GEMM_PP2"):      # round-5 persistent GEMM: bit 0 gemm_nt (default), 1 convs
-    _K.gemm_set_pp2(int(os.environ["DTF_GEMM_PP2"]))
-if os.environ.get("DTF_STORE_NT"):      # non-temporal output stores: bit 0 conv, 1 GEMM, 2 BN
-    _nt = int(os.environ["DTF_STORE_NT"])
-    _K.conv_set_nt(_nt & 1)
-    _K.gemm_set_nt((_nt >> 1) & 1)
-    _K.bn_set_nt(7 if _nt & 4 else 0)
+
+def _store_nt(v):
+    _K.conv_set_nt(v & 1)
+    _K.gemm_set_nt((v >> 1) & 1)
+    _K.bn_set_nt(7 if v & 4 else 0)
+
+
+# kernel-variant switches for A/B runs on one box (defaults = the measured best):
+# (environment name, setter, what it selects); unset or empty leaves the setter uncalled
+_ENV_KNOBS = (
+    ("DTF_WGRAD_MODE", _K.wgrad_set_dma_mode, ""),
+    ("DTF_WGRAD_PP", _K.wgrad_set_pp, "ping-pong wgrad: 0 off, n: split-K target of n rounds"),
+    ("DTF_WGRAD_DENSE", _K.wgrad_set_dense, "ping-pong wgrad's decode-free one-tap form: 0 off"),
+    ("DTF_WGRAD_PIPE", _K.wgrad_set_pipe, ""),
+    ("DTF_CONV_DMA", _K.conv_set_dma_mode, ""),
+    ("DTF_CONV_HALO", _K.conv_set_halo, ""),
+    ("DTF_WGRAD_HALO", _K.wgrad_set_halo, ""),
+    ("DTF_CONV_STEM_HALO", _K.conv_set_stem_halo, ""),
+    ("DTF_CONV_HALO_STRIPS", _K.conv_set_halo_strips,
+     "bit f: two strips per block for halo family f"),
+    ("DTF_CONV_HALO_FREG", _K.conv_set_halo_freg,
+     "bit f: halo family f streams its filter via VGPRs"),
+    ("DTF_CONV_SMALL_K", _K.conv_set_small_k, ""),
+    ("DTF_GEMM_STREAM", _K.gemm_set_stream,
+     "row-streaming GEMM for output-heavy shapes (default on)"),
+    ("DTF_C1_W16", _K.conv1x1_bwd_set_w16,
+     "stage-0 fused c3 backward as 16-wave blocks (default 0)"),
+    ("DTF_GEMM_GROUP_M", _K.gemm_set_group, "grouped tile order of the dense GEMMs (0: N fastest)"),
+    ("DTF_BN_GRID_CAP", _K.bn_set_grid_cap,
+     "BN row-sweep grid cap override (2048 = round-2 grids)"),
+    ("DTF_BN_STATS_BLOCKS", _K.bn_set_stats_blocks, "BN reduce-pass block target (1024 = round-2)"),
+    ("DTF_GEMM_PP2", _K.gemm_set_pp2, "round-5 persistent GEMM: bit 0 gemm_nt (default), 1 convs"),
+    ("DTF_STORE_NT", _store_nt, "non-temporal output stores: bit 0 conv, 1 GEMM, 2 BN"),
+)
+for _name, _setter, _ in _ENV_KNOBS:
+    if os.environ.get(_name):
+        _setter(int(os.environ[_name]))
 
 
 def _st():
