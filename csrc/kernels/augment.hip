@@ -1,0 +1,248 @@
+// Fused on-device image augmentation for HBM-resident uint8 image sets (data/images.py): one
+// launch turns a batch of example indices into the model's input,
+//   gather -> crop box (random-resized-crop / pad-crop / centre) -> bilinear resize -> flip ->
+//   per-channel normalisation -> bf16 / fp32 NHWC.
+//
+// The sampling rule is integer arithmetic (ops/reference.py augment_images is the same rule in
+// torch and the tests' oracle; the two agree to the bit).  For output pixel (b, oy, ox):
+//   ox' = flip[b] ? Wo - 1 - ox : ox
+//   per axis, half-pixel centres with 8 fractional bits:
+//     pos = floor((2 o + 1) * side * 256 / (2 O)) - 128, clamped to [0, (side - 1) * 256]
+//     i0 = pos >> 8, f = pos & 255, i1 = min(i0 + 1, side - 1)
+//   taps (y0 + iy, x0 + ix); a tap outside the image reads `fill`
+//   v = ((256 - fy) * ((256 - fx) * p00 + fx * p01) + fy * ((256 - fx) * p10 + fx * p11)
+//        + 32768) >> 16
+//   out = lut[c][v]          (the host builds (v / 255 - mean_c) / std_c in the output dtype)
+//
+// Mapping: a block takes one (example, tile of 16 output rows, chunk of 256 output columns) at a
+// time and grid-strides over those.  It first fills two small LDS tables -- per output column of
+// the chunk and per output row of the tile: the two tap offsets, the weight and whether each tap
+// is inside the image -- so the divisions of the rule are paid once per row / column, not once
+// per pixel.  Its threads then each produce G consecutive elements of one output row: where
+// Wo * C % 8 == 0, 8 whole pixels (G = 8 C, written as 16-B stores; each tap is one load of the
+// pixel's C bytes), otherwise G = 1 (the scalar tail path, one byte per tap).  Consecutive lanes
+// take consecutive groups of a row, so a wave's stores are one contiguous run and its taps fall
+// in the same two source rows.  The example is uniform over
+// the block, so taps are 32-bit offsets from one scalar image base.  The normalisation table
+// (<= 3 KB) is staged in LDS once per block.
+#include <stdexcept>
+
+#include "launch.h"
+
+namespace {
+constexpr int kAugThreads = 256;
+constexpr int kAugRows = 16;             // output rows per tile
+constexpr int kAugCols = 256;            // output columns per chunk (a multiple of 8)
+constexpr int kAugDefaultBlocks = 2048;
+constexpr int kAugTap0 = 256, kAugTap1 = 512;     // table flags: tap 0 / tap 1 inside the image
+
+struct AugAxis {
+  int i0, i1, f;
+};
+
+// pos of output coordinate o of O over a box side of `side` source pixels
+DTF_DEV AugAxis aug_axis(int o, int O, int side) {
+  const uint64_t num = (uint64_t)(2 * o + 1) * (uint64_t)(side > 0 ? side : 0) * 256u;
+  const uint32_t den = 2u * (uint32_t)O;
+  // the 32-bit divide covers every practical shape; the 64-bit one keeps huge boxes exact
+  const int64_t q = (num >> 32) == 0 ? (int64_t)((uint32_t)num / den) : (int64_t)(num / den);
+  const int64_t hi = ((int64_t)side - 1) * 256;
+  int64_t pos = q - 128;
+  pos = pos < 0 ? 0 : pos;
+  pos = pos > hi ? hi : pos;
+  AugAxis a;
+  a.i0 = (int)(pos >> 8);
+  a.f = (int)(pos & 255);
+  a.i1 = a.i0 + 1 < side ? a.i0 + 1 : side - 1;
+  return a;
+}
+
+// One table entry of an axis: taps at (origin + i0, origin + i1) of an axis of `extent` source
+// pixels, `stride` bytes apart -> byte offsets (0 for a tap outside) and weight | flags.
+DTF_DEV void aug_entry(int o, int O, int side, int origin, int extent, int stride, int* off0,
+                       int* off1, int* wf) {
+  const AugAxis a = aug_axis(o, O, side);
+  const int64_t t0 = (int64_t)origin + a.i0, t1 = (int64_t)origin + a.i1;
+  const bool ok0 = t0 >= 0 && t0 < extent, ok1 = t1 >= 0 && t1 < extent;
+  *off0 = ok0 ? (int)t0 * stride : 0;
+  *off1 = ok1 ? (int)t1 * stride : 0;
+  *wf = a.f | (ok0 ? kAugTap0 : 0) | (ok1 ? kAugTap1 : 0);
+}
+
+DTF_DEV int aug_blend(int p00, int p01, int p10, int p11, int fx, int fy) {
+  const int top = (256 - fx) * p00 + fx * p01, bot = (256 - fx) * p10 + fx * p11;
+  return ((256 - fy) * top + fy * bot + 32768) >> 16;
+}
+
+// The C channel bytes of the pixel at byte `off` of an image, in the low bytes of one word.  For
+// C = 3 that is one (unaligned) 4-byte load; it reads one byte past the pixel, so at the image's
+// last pixel it is taken 1 byte lower (`last4` = image bytes - 4) and shifted back.
+template <int C>
+DTF_DEV uint32_t aug_tap(const uint8_t* __restrict__ img, uint32_t off, uint32_t last4) {
+  if constexpr (C == 1) {
+    return img[off];
+  } else {
+    const uint32_t at = off < last4 ? off : last4;
+    uint32_t w;
+    __builtin_memcpy(&w, img + at, 4);
+    return w >> (8 * (off - at));
+  }
+}
+
+template <typename OutT, int C, int G>
+__global__ void __launch_bounds__(kAugThreads)
+augment_kernel(const uint8_t* __restrict__ images, const int64_t* __restrict__ idx,
+               const int* __restrict__ boxes, const uint8_t* __restrict__ flip,
+               const OutT* __restrict__ lut, OutT* __restrict__ out, long N, int B, int Hs, int Ws,
+               int Ho, int Wo, int fill, int tiles, int chunks) {
+  __shared__ OutT s_lut[C * 256];
+  __shared__ int s_x0[kAugCols], s_x1[kAugCols], s_xf[kAugCols];
+  __shared__ int s_y0[kAugRows], s_y1[kAugRows], s_yf[kAugRows];
+  const int tid = threadIdx.x;
+  for (int i = tid; i < C * 256; i += kAugThreads) s_lut[i] = lut[i];
+
+  const uint32_t per_b = (uint32_t)tiles * (uint32_t)chunks;
+  const uint32_t items = (uint32_t)B * per_b;                        // < 2^31: launcher
+  const int64_t row_elems = (int64_t)Wo * C;
+  const uint32_t last4 = (uint32_t)(Hs * Ws * C - 4);               // vector path: >= 0, launcher
+  const uint32_t fillw = (uint32_t)fill * 0x010101u;
+  for (uint32_t u = blockIdx.x; u < items; u += gridDim.x) {
+    const int b = (int)(u / per_b);
+    const int rem = (int)(u - (uint32_t)b * per_b);
+    const int tile = rem / chunks, chunk = rem - tile * chunks;
+    const int oy0 = tile * kAugRows, px0 = chunk * kAugCols;
+    const int rows = Ho - oy0 < kAugRows ? Ho - oy0 : kAugRows;
+    const int cols = Wo - px0 < kAugCols ? Wo - px0 : kAugCols;
+    const int y0 = boxes[4 * b], x0 = boxes[4 * b + 1], bh = boxes[4 * b + 2],
+              bw = boxes[4 * b + 3];
+    const bool fl = flip[b] != 0;
+    const int64_t n = idx[b];
+    const bool img_ok = n >= 0 && n < N;           // a bad index reads as fill, never past the set
+    const uint8_t* img = images + (img_ok ? n : 0) * ((int64_t)Hs * Ws * C);   // block-uniform
+
+    __syncthreads();                 // the previous item's table reads (and the LUT staging)
+    if (tid < cols) {
+      const int ox = px0 + tid;
+      aug_entry(fl ? Wo - 1 - ox : ox, Wo, bw, x0, Ws, C, &s_x0[tid], &s_x1[tid], &s_xf[tid]);
+    }
+    if (tid < rows) {
+      int wf;
+      aug_entry(oy0 + tid, Ho, bh, y0, Hs, Ws * C, &s_y0[tid], &s_y1[tid], &wf);
+      s_yf[tid] = img_ok ? wf : (wf & 255);
+    }
+    __syncthreads();
+
+    const int g0 = px0 * C / G, gpc = cols * C / G;       // this chunk's groups of a row
+    const float inv_gpc = 1.0f / (float)gpc;
+    for (int k = tid; k < rows * gpc; k += kAugThreads) {
+      int r = (int)(((float)k + 0.5f) * inv_gpc);          // k / gpc, r < 16: fixed up below
+      r = r * gpc > k ? r - 1 : r;
+      r = (r + 1) * gpc <= k ? r + 1 : r;
+      const int g = k - r * gpc;
+      const uint32_t ro0 = (uint32_t)s_y0[r], ro1 = (uint32_t)s_y1[r];
+      const int yf = s_yf[r], fy = yf & 255;
+      const bool r0_ok = (yf & kAugTap0) != 0, r1_ok = (yf & kAugTap1) != 0;
+
+      OutT res[G];
+      if constexpr (G == 1) {
+        // tail path: one element; offsets of taps outside the image are 0, so every load is
+        // inside the image
+        const int pi = g / C, c = g - pi * C, xf = s_xf[pi], fx = xf & 255;
+        const uint32_t o0 = (uint32_t)s_x0[pi], o1 = (uint32_t)s_x1[pi];
+        const bool c0_ok = (xf & kAugTap0) != 0, c1_ok = (xf & kAugTap1) != 0;
+        const int v00 = img[ro0 + o0 + c], v01 = img[ro0 + o1 + c];
+        const int v10 = img[ro1 + o0 + c], v11 = img[ro1 + o1 + c];
+        const int p00 = r0_ok && c0_ok ? v00 : fill, p01 = r0_ok && c1_ok ? v01 : fill;
+        const int p10 = r1_ok && c0_ok ? v10 : fill, p11 = r1_ok && c1_ok ? v11 : fill;
+        res[0] = s_lut[c * 256 + aug_blend(p00, p01, p10, p11, fx, fy)];
+      } else {
+        // vector path: 8 whole pixels; each tap is ONE load of the pixel's channels
+#pragma unroll
+        for (int p = 0; p < 8; ++p) {
+          const int pi = g * 8 + p, xf = s_xf[pi], fx = xf & 255;
+          const uint32_t o0 = (uint32_t)s_x0[pi], o1 = (uint32_t)s_x1[pi];
+          const bool c0_ok = (xf & kAugTap0) != 0, c1_ok = (xf & kAugTap1) != 0;
+          const uint32_t w00 = r0_ok && c0_ok ? aug_tap<C>(img, ro0 + o0, last4) : fillw;
+          const uint32_t w01 = r0_ok && c1_ok ? aug_tap<C>(img, ro0 + o1, last4) : fillw;
+          const uint32_t w10 = r1_ok && c0_ok ? aug_tap<C>(img, ro1 + o0, last4) : fillw;
+          const uint32_t w11 = r1_ok && c1_ok ? aug_tap<C>(img, ro1 + o1, last4) : fillw;
+#pragma unroll
+          for (int c = 0; c < C; ++c) {
+            const int v = aug_blend((w00 >> (8 * c)) & 255, (w01 >> (8 * c)) & 255,
+                                    (w10 >> (8 * c)) & 255, (w11 >> (8 * c)) & 255, fx, fy);
+            res[p * C + c] = s_lut[c * 256 + v];
+          }
+        }
+      }
+
+      OutT* dst = out + ((int64_t)b * Ho + oy0 + r) * row_elems + (int64_t)(g0 + g) * G;
+      if constexpr (G == 1) {
+        dst[0] = res[0];
+      } else if constexpr (sizeof(OutT) == 2) {
+#pragma unroll
+        for (int q = 0; q < G / 8; ++q) {
+          const OutT* h = res + 8 * q;
+          uint4 w;                     // the table already holds bf16 bits: pack them as they are
+          w.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
+          w.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
+          w.z = (uint32_t)h[4] | ((uint32_t)h[5] << 16);
+          w.w = (uint32_t)h[6] | ((uint32_t)h[7] << 16);
+          reinterpret_cast<uint4*>(dst)[q] = w;
+        }
+      } else {
+#pragma unroll
+        for (int q = 0; q < G / 4; ++q)
+          reinterpret_cast<float4*>(dst)[q] =
+              make_float4(res[4 * q], res[4 * q + 1], res[4 * q + 2], res[4 * q + 3]);
+      }
+    }
+  }
+}
+
+template <typename OutT, int C>
+void launch_augment(const uint8_t* images, const int64_t* idx, const int* boxes,
+                    const uint8_t* flip, const void* lut, void* out, long N, int B, int Hs, int Ws,
+                    int Ho, int Wo, int fill, int max_blocks, hipStream_t st) {
+  // vector path: Wo % 8 == 0 (what Wo * C % 8 == 0 means for C in {1, 3}), so a chunk holds whole
+  // groups of 8 pixels; an image of under 4 bytes has no room for the 4-byte tap load
+  const bool vec = (Wo * C) % 8 == 0 && (long)Hs * Ws * C >= 4;
+  const int tiles = (Ho + kAugRows - 1) / kAugRows, chunks = (Wo + kAugCols - 1) / kAugCols;
+  const long items = (long)B * tiles * chunks;
+  if (items >= 2147483647L) throw std::runtime_error("augment_images: batch too large");
+  const long cap = max_blocks > 0 ? max_blocks : kAugDefaultBlocks;
+  const dim3 grid((unsigned)(items < cap ? items : cap)), block(kAugThreads);
+  if (vec)
+    hipLaunchKernelGGL((augment_kernel<OutT, C, 8 * C>), grid, block, 0, st, images, idx, boxes, flip,
+                       static_cast<const OutT*>(lut), static_cast<OutT*>(out), N, B, Hs, Ws, Ho,
+                       Wo, fill, tiles, chunks);
+  else
+    hipLaunchKernelGGL((augment_kernel<OutT, C, 1>), grid, block, 0, st, images, idx, boxes, flip,
+                       static_cast<const OutT*>(lut), static_cast<OutT*>(out), N, B, Hs, Ws, Ho,
+                       Wo, fill, tiles, chunks);
+}
+}  // namespace
+
+void dtf_augment_images(const uint8_t* images, const int64_t* idx, const int* boxes,
+                        const uint8_t* flip, const void* lut, void* out, long N, int B, int Hs,
+                        int Ws, int C, int Ho, int Wo, int fill, int out_bf16, int max_blocks,
+                        hipStream_t st) {
+  if (C != 1 && C != 3) throw std::runtime_error("augment_images: C must be 1 or 3");
+  if (N < 1 || Hs < 1 || Ws < 1) throw std::runtime_error("augment_images: empty image set");
+  if (B < 0 || Ho < 1 || Wo < 1) throw std::runtime_error("augment_images: bad output shape");
+  // tap offsets within one image are 32-bit (the set itself may be far larger), and 2 * o + 1
+  // stays inside int
+  if ((long)Hs * Ws * C > 2147483647L || Ho > (1 << 20) || Wo > (1 << 20))
+    throw std::runtime_error("augment_images: one image must stay below 2 GiB");
+  if (fill < 0 || fill > 255) throw std::runtime_error("augment_images: fill must be one byte");
+  if (max_blocks < 0) throw std::runtime_error("augment_images: negative max_blocks");
+  if (B == 0) return;
+#define DTF_AUG(T, CC)                                                                          \
+  launch_augment<T, CC>(images, idx, boxes, flip, lut, out, N, B, Hs, Ws, Ho, Wo, fill,         \
+                        max_blocks, st)
+  if (out_bf16) {
+    if (C == 3) DTF_AUG(bf16_t, 3); else DTF_AUG(bf16_t, 1);
+  } else {
+    if (C == 3) DTF_AUG(float, 3); else DTF_AUG(float, 1);
+  }
+#undef DTF_AUG
+}

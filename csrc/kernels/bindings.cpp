@@ -146,6 +146,15 @@ PYBIND11_MODULE(_dtf_hip, m) {
                         S(st));
     check_launch("gather_u8_scale");
   });
+  m.def("augment_images", [](uintptr_t images, uintptr_t idx, uintptr_t boxes, uintptr_t flip,
+                             uintptr_t lut, uintptr_t out, long N, int B, int Hs, int Ws, int C,
+                             int Ho, int Wo, int fill, int out_bf16, int max_blocks,
+                             uintptr_t st) {
+    dtf_augment_images(P<uint8_t>(images), P<int64_t>(idx), P<int>(boxes), P<uint8_t>(flip),
+                       P<void>(lut), P<void>(out), N, B, Hs, Ws, C, Ho, Wo, fill, out_bf16,
+                       max_blocks, S(st));
+    check_launch("augment_images");
+  });
   m.def("gemm_f32_splits", &dtf_gemm_f32_splits);
   m.def("gemm_f32", [](uintptr_t a, uintptr_t b, uintptr_t c, uintptr_t bias, int M, int N, int K,
                        long sam, long sak, long sbn, long sbk, long scm, long scn, float alpha,

@@ -282,6 +282,12 @@ void dtf_bias_relu_bwd(const bf16_t* dy, const bf16_t* y, bf16_t* dz, int T, int
 void dtf_gather_u8_scale(const uint8_t* images, const int64_t* idx, void* out, int B, int D,
                          float scale, int out_bf16, hipStream_t st);
 
+// ---- augment.hip
+void dtf_augment_images(const uint8_t* images, const int64_t* idx, const int* boxes,
+                        const uint8_t* flip, const void* lut, void* out, long N, int B, int Hs,
+                        int Ws, int C, int Ho, int Wo, int fill, int out_bf16, int max_blocks,
+                        hipStream_t st);
+
 // ---- loss.hip
 void dtf_softmax_xent(const float* logits, const void* labels, int label_bytes, int B, int V,
                       float* loss_rows, float* grad, float grad_scale, hipStream_t st);

@@ -89,6 +89,16 @@ def build_parser():
     p.add_argument("--eval_steps", type=int, default=10,
                    help="batches per replica of an evaluation on the synthetic sets")
     p.add_argument("--eval_top_k", type=int, default=5, help="k of the reported top-k accuracy")
+    p.add_argument("--image_data", default=None, metavar="DIR",
+                   help="train an image model on DIR/train_{images,labels}.npy (uint8 NHWC), kept "
+                        "in device memory and augmented on the device; --eval / --eval_every "
+                        "then evaluate on DIR/val_*.npy")
+    p.add_argument("--augment", choices=("rrc", "pad_crop", "none"), default="rrc",
+                   help="training transform with --image_data: random-resized-crop, pad 4 + "
+                        "crop, or resize only (each with random flips)")
+    p.add_argument("--num_classes", type=int, default=None,
+                   help="classes of the --image_data set (default: 1000 for ResNet, 10 for MNIST "
+                        "models)")
     return p
 
 
@@ -206,7 +216,18 @@ def run(args):
     dtype = torch.bfloat16 if device.type == "cuda" else torch.float32
 
     # ---- data + model
-    if args.model.startswith("mnist"):
+    num_classes = None
+    if args.image_data:
+        if args.model.startswith("bert"):
+            raise SystemExit("--image_data needs an image model")
+        num_classes = args.num_classes or (10 if args.model.startswith("mnist") else 1000)
+        if args.model == "mnist_mlp" and num_classes != 10:
+            raise SystemExit("mnist_mlp has 10 classes")
+        shards = nrep if server is None else 1
+        data = _image_dataset(args, "train", num_classes, batch, device, dtype, shards,
+                              rid if shards > 1 else 0)
+        batch = data.batch_size
+    elif args.model.startswith("mnist"):
         from .data import DeviceArrayDataset, mnist
         imgs, labels = mnist.load_arrays(args.data_dir, "train")
         if args.download_only:
@@ -224,7 +245,11 @@ def run(args):
         data = SyntheticMLM(batch, args.seq_len, device=device, seed=1234 + rid)
 
     with strategy.scope():
-        if args.model == "mnist_cnn":
+        if num_classes is not None and args.model != "mnist_mlp":
+            ctor = dtf.models.MnistCNN if args.model == "mnist_cnn" else \
+                getattr(dtf.models, args.model)
+            model = ctor(num_classes=num_classes)
+        elif args.model == "mnist_cnn":
             model = dtf.models.MnistCNN()
         elif args.model == "mnist_mlp":
             model = dtf.models.MnistMLP(args.hidden_units)
@@ -319,7 +344,9 @@ def run(args):
         result["eval_loss"] = round(ev["loss"], 4)
         result["eval_top_1"] = round(ev["top_1"], 4)
         result["eval_top_k"] = round(ev["top_k"], 4)
-        if args.model.startswith("mnist"):
+        if args.image_data:
+            result["eval_count"] = int(ev["count"])
+        elif args.model.startswith("mnist"):
             result["test_accuracy"] = round(ev["top_1"], 4)
     if is_chief:
         print(json.dumps(result), flush=True)
@@ -328,12 +355,46 @@ def run(args):
     return 0
 
 
+def _image_dataset(args, split, num_classes, batch, device, dtype, shards, shard_index):
+    """--image_data: the HBM-resident ``split`` of DIR as a DeviceImageDataset.  ResNets get
+    --image_size outputs under the ImageNet channel statistics, the MNIST models 28 x 28 x 1
+    scaled to [0, 1]; the batch shrinks to the shard where that is smaller."""
+    from .data import DeviceImageDataset, ImageAugment, images
+    from .data.images import IMAGENET_MEAN, IMAGENET_STD
+    imgs, labels = images.load_arrays(args.image_data, split, num_classes)
+    C = imgs.shape[3]
+    if args.model.startswith("mnist"):
+        if C != 1:
+            raise SystemExit(f"{args.model} takes 1-channel images; {args.image_data} has {C}")
+        size, mean, std = 28, None, None
+    else:
+        if C != 3:
+            raise SystemExit(f"{args.model} takes 3-channel images; {args.image_data} has {C}")
+        size, mean, std = args.image_size, IMAGENET_MEAN, IMAGENET_STD
+    mode = {"rrc": "random_resized_crop", "pad_crop": "pad_crop", "none": "none"}[args.augment]
+    aug = ImageAugment(size, mode=mode, mean=mean, std=std)
+    batch = max(1, min(batch, len(range(shard_index, len(labels), shards))))
+    # between-graph workers all hold the whole set: each shuffles and augments on its own stream
+    stream = args.task_index if args.job_name else shard_index
+    return DeviceImageDataset(imgs, labels, batch, device, aug, dtype=dtype,
+                              shuffle=split == "train", seed=args.seed + stream,
+                              aug_seed=args.seed + 1000003 * (stream + 1),
+                              num_shards=shards, shard_index=shard_index,
+                              flatten=args.model == "mnist_mlp")
+
+
 def _make_eval_fn(args, model, opt, strategy, device, dtype, batch, shards, shard_index):
     """-> eval_fn() -> {"loss", "top_1", "top_k", "count"}: one pass of this replica's shard of
     the evaluation set through ``train.evaluate`` (collective under a collective strategy)."""
     from .metrics import ClassificationMetrics
     from .train import evaluate
-    if args.model.startswith("mnist"):
+    if args.image_data:
+        num_classes = args.num_classes or (10 if args.model.startswith("mnist") else 1000)
+        data = _image_dataset(args, "val", num_classes, batch, device, dtype, shards, shard_index)
+
+        def batches():
+            return data.single_pass()
+    elif args.model.startswith("mnist"):
         from .data import DeviceArrayDataset, mnist
         imgs, labels = mnist.load_arrays(args.data_dir, "test")
         per = max(1, min(1000, len(labels) // shards))

@@ -1,0 +1,296 @@
+"""HBM-resident image sets with fused on-device augmentation.
+
+A pre-resized uint8 image set fits the device whole (ImageNet at 64 x 64 is 15.7 GB, at
+160 x 160 98 GB, of 288 GB of HBM3E), so it is uploaded once and every training batch is ONE
+kernel (``ops.augment_images``): gather, random-resized-crop or pad-crop, bilinear resize, flip,
+per-channel normalisation, cast to the compute dtype, NHWC.  No host pipeline and no per-step
+copy of pixels; the only per-step host work is drawing the crop / flip uniforms from the
+dataset's own CPU generator and forming the B crop boxes from them (20 bytes per example reach
+the device), which is what makes a CPU and a GPU dataset with the same seeds yield the same
+batches.
+
+On disk a set is two arrays per split in one directory (:func:`load_arrays`):
+
+    {split}_images.npy   uint8 [N, H, W, C], C in {1, 3}   (memory-mapped, never copied whole)
+    {split}_labels.npy   integers [N] in [0, num_classes)
+
+Crop boxes are (y0, x0, h, w) in source pixels, int32, one pure function per mode:
+:func:`rrc_boxes`, :func:`pad_crop_boxes`, :func:`center_boxes`.
+"""
+from __future__ import annotations
+
+import math
+import os
+
+import numpy as np
+import torch
+
+from .device import DeviceArrayDataset
+
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+RRC_ATTEMPTS = 10
+
+
+def load_arrays(data_dir, split, num_classes=None):
+    """-> (images, labels) of ``{split}_images.npy`` (uint8 NHWC, memory-mapped) and
+    ``{split}_labels.npy``.  Raises ValueError on a wrong dtype or rank, a length mismatch, or
+    a label outside ``[0, num_classes)``."""
+    ipath = os.path.join(data_dir, f"{split}_images.npy")
+    lpath = os.path.join(data_dir, f"{split}_labels.npy")
+    images = np.load(ipath, mmap_mode="r")
+    labels = np.load(lpath)
+    if images.dtype != np.uint8:
+        raise ValueError(f"{ipath}: dtype {images.dtype}, expected uint8")
+    if images.ndim != 4 or images.shape[3] not in (1, 3):
+        raise ValueError(f"{ipath}: shape {images.shape}, expected [N, H, W, C] with C in (1, 3)")
+    if labels.ndim != 1 or not np.issubdtype(labels.dtype, np.integer):
+        raise ValueError(f"{lpath}: {labels.dtype} {labels.shape}, expected integers [N]")
+    if len(labels) != len(images):
+        raise ValueError(f"{lpath}: {len(labels)} labels for {len(images)} images")
+    if len(labels) and int(labels.min()) < 0:
+        raise ValueError(f"{lpath}: negative label {int(labels.min())}")
+    if num_classes is not None and len(labels) and int(labels.max()) >= num_classes:
+        raise ValueError(f"{lpath}: label {int(labels.max())} >= num_classes {num_classes}")
+    return images, labels
+
+
+# ----------------------------------------------------------------------------- crop boxes
+
+def _round(x):
+    return torch.floor(x + 0.5)                         # half-up
+
+
+def _fallback_box(Hs, Ws, ratio):
+    """The central crop at the aspect ratio nearest the image's inside ``ratio``."""
+    in_ratio = Ws / Hs
+    if in_ratio < ratio[0]:
+        w, h = Ws, int(math.floor(Ws / ratio[0] + 0.5))
+    elif in_ratio > ratio[1]:
+        h, w = Hs, int(math.floor(Hs * ratio[1] + 0.5))
+    else:
+        h, w = Hs, Ws
+    h, w = min(max(h, 1), Hs), min(max(w, 1), Ws)
+    return (Hs - h) // 2, (Ws - w) // 2, h, w
+
+
+def rrc_boxes(u, Hs, Ws, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0)):
+    """RandomResizedCrop boxes (torchvision's / TF official ResNet's semantics) from supplied
+    uniforms ``u`` [B, 10, 4] -> int32 [B, 4] on ``u``'s device, computed in float64.
+
+    Attempt k: ``area = Hs Ws lerp(scale, u0)``, ``ar = exp(lerp(log ratio, u1))``,
+    ``w = round(sqrt(area ar))``, ``h = round(sqrt(area / ar))`` (half-up), valid iff
+    ``1 <= w <= Ws`` and ``1 <= h <= Hs``; ``x0 = floor(u2 (Ws - w + 1))``,
+    ``y0 = floor(u3 (Hs - h + 1))``.  The first valid attempt wins; with none, the central
+    crop at the nearest aspect ratio inside ``ratio``."""
+    if u.dim() != 3 or u.shape[2] != 4:
+        raise ValueError("rrc_boxes: u must be [B, attempts, 4]")
+    u = u.to(torch.float64)
+    area = (Hs * Ws) * (scale[0] + (scale[1] - scale[0]) * u[..., 0])
+    l0, l1 = math.log(ratio[0]), math.log(ratio[1])
+    ar = torch.exp(l0 + (l1 - l0) * u[..., 1])
+    w = _round(torch.sqrt(area * ar))
+    h = _round(torch.sqrt(area / ar))
+    valid = (w >= 1) & (w <= Ws) & (h >= 1) & (h <= Hs)
+    x0 = torch.minimum(torch.floor(u[..., 2] * (Ws - w + 1)), Ws - w)
+    y0 = torch.minimum(torch.floor(u[..., 3] * (Hs - h + 1)), Hs - h)
+    cand = torch.stack([y0, x0, h, w], dim=2).to(torch.int32)            # [B, A, 4]
+    first = torch.argmax(valid.to(torch.uint8), dim=1)                    # first maximal index
+    pick = cand.gather(1, first.view(-1, 1, 1).expand(-1, 1, 4)).squeeze(1)
+    fb = torch.tensor(_fallback_box(Hs, Ws, ratio), dtype=torch.int32, device=u.device)
+    return torch.where(valid.any(dim=1, keepdim=True), pick, fb.unsqueeze(0))
+
+
+def pad_crop_boxes(u, Hs, Ws, out_hw, pad):
+    """Pad-and-crop boxes (the CIFAR transform) from uniforms ``u`` [B, 2]: the box has the
+    output's size and its offsets are uniform in ``[-pad, Hs + pad - Ho]`` x
+    ``[-pad, Ws + pad - Wo]``, so the resize is an exact copy and the padding reads ``fill``."""
+    Ho, Wo = out_hw
+    ny, nx = Hs + 2 * pad - Ho + 1, Ws + 2 * pad - Wo + 1
+    if ny < 1 or nx < 1:
+        raise ValueError(f"pad_crop_boxes: output {out_hw} exceeds the padded {Hs}x{Ws} image")
+    u = u.to(torch.float64)
+    y0 = torch.clamp(torch.floor(u[:, 0] * ny), max=ny - 1) - pad
+    x0 = torch.clamp(torch.floor(u[:, 1] * nx), max=nx - 1) - pad
+    return torch.stack([y0, x0, torch.full_like(y0, Ho), torch.full_like(x0, Wo)],
+                       dim=1).to(torch.int32)
+
+
+def center_boxes(Hs, Ws, fraction=0.875):
+    """The evaluation transform: the central ``fraction`` of each side -> int32 [1, 4]."""
+    h = min(max(int(math.floor(Hs * fraction + 0.5)), 1), Hs)
+    w = min(max(int(math.floor(Ws * fraction + 0.5)), 1), Ws)
+    return torch.tensor([[(Hs - h) // 2, (Ws - w) // 2, h, w]], dtype=torch.int32)
+
+
+# ----------------------------------------------------------------------------- the dataset
+
+class ImageAugment:
+    """The transform of a :class:`DeviceImageDataset`.
+
+    ``out_size``: int or (Ho, Wo).  ``mode``: "random_resized_crop" (``scale``, ``ratio``),
+    "pad_crop" (``pad``; the output must not exceed the padded image) or "none" (the whole
+    image, resized).  ``flip``: random horizontal flips in training.  ``mean`` / ``std``: per
+    channel, on the [0, 1] scale (default 0 / 1: plain x / 255).  ``eval_fraction``: the centre
+    crop of ``single_pass()`` (default 0.875 under random_resized_crop, else the whole image).
+    ``fill``: the byte read outside the image."""
+
+    MODES = ("random_resized_crop", "pad_crop", "none")
+
+    def __init__(self, out_size, mode="random_resized_crop", scale=(0.08, 1.0),
+                 ratio=(3.0 / 4.0, 4.0 / 3.0), pad=4, flip=True, mean=None, std=None,
+                 eval_fraction=None, fill=0):
+        if mode not in self.MODES:
+            raise ValueError(f"ImageAugment: mode {mode!r} not in {self.MODES}")
+        self.out_hw = (int(out_size),) * 2 if np.isscalar(out_size) else \
+            tuple(int(v) for v in out_size)
+        if len(self.out_hw) != 2 or min(self.out_hw) < 1:
+            raise ValueError(f"ImageAugment: out_size {out_size}")
+        self.out_size = self.out_hw
+        if not (0 < scale[0] <= scale[1] and 0 < ratio[0] <= ratio[1]):
+            raise ValueError("ImageAugment: scale and ratio must be positive increasing pairs")
+        self.mode, self.scale, self.ratio = mode, tuple(scale), tuple(ratio)
+        self.pad, self.flip, self.fill = int(pad), bool(flip), int(fill)
+        self.mean, self.std = mean, std
+        if eval_fraction is None:
+            eval_fraction = 0.875 if mode == "random_resized_crop" else 1.0
+        if not 0 < eval_fraction <= 1:
+            raise ValueError("ImageAugment: eval_fraction must be in (0, 1]")
+        self.eval_fraction = float(eval_fraction)
+
+    def lut(self, channels, dtype, device):
+        """[C, 256] table of (v / 255 - mean_c) / std_c, built in float64 and cast once."""
+        mean = (0.0,) * channels if self.mean is None else tuple(self.mean)
+        std = (1.0,) * channels if self.std is None else tuple(self.std)
+        if len(mean) != channels or len(std) != channels:
+            raise ValueError(f"ImageAugment: mean / std need {channels} entries")
+        v = torch.arange(256, dtype=torch.float64, device="cpu").unsqueeze(0) / 255.0
+        t = (v - torch.tensor(mean, dtype=torch.float64, device="cpu").unsqueeze(1)) / \
+            torch.tensor(std, dtype=torch.float64, device="cpu").unsqueeze(1)
+        return t.to(dtype).to(device).contiguous()
+
+
+class DeviceImageDataset(DeviceArrayDataset):
+    """A :class:`DeviceArrayDataset` of uint8 NHWC images whose batches are augmented on the
+    device by one kernel.  ``__next__`` applies the training transform of ``augment``;
+    ``single_pass()`` applies the centre crop without a flip and touches neither generator, so
+    an evaluation between two steps leaves training bit-identical.  Example order, epochs,
+    sharding and the shuffle generator are the parent's; crop and flip uniforms come from a
+    second, CPU generator (``aug_seed``), so the order is the same with and without augmentation
+    and the same seeds give the same batches on the CPU and on the GPU.
+
+    Upload: the (possibly memory-mapped) array is copied ``chunk_bytes`` at a time into a
+    preallocated device tensor, the shard selection applied per chunk, so the host never holds
+    a second copy of the set.  ``flatten``: batches are [B, Ho * Wo * C] (the MLP's input)."""
+
+    def __init__(self, images, labels, batch_size, device, augment, dtype=None, shuffle=False,
+                 seed=0, aug_seed=0, num_shards=1, shard_index=0, drop_remainder=True,
+                 chunk_bytes=256 << 20, flatten=False):
+        device = torch.device(device)
+        if images.dtype != np.uint8 or images.ndim != 4 or images.shape[3] not in (1, 3):
+            raise ValueError("DeviceImageDataset: images must be uint8 [N, H, W, C], C in (1, 3)")
+        if len(labels) != len(images):
+            raise ValueError(f"DeviceImageDataset: {len(labels)} labels for {len(images)} images")
+        if not 0 <= shard_index < num_shards:
+            raise ValueError(f"DeviceImageDataset: shard {shard_index} of {num_shards}")
+        self.images = self._upload(images, device, num_shards, shard_index, int(chunk_bytes))
+        labs = torch.as_tensor(np.ascontiguousarray(labels)).long()
+        self.labels = labs[shard_index::num_shards].to(device)
+        self.n = len(self.labels)
+        self.batch_size = batch_size
+        self.device = device
+        self.dtype = dtype or (torch.bfloat16 if device.type == "cuda" else torch.float32)
+        self.scale = 1.0 / 255.0
+        self.shuffle = shuffle
+        self.drop_remainder = drop_remainder
+        self._gen = torch.Generator(device=device)
+        self._gen.manual_seed(seed)
+        self._order = None
+        self._pos = 0
+        self.epoch = 0
+        if self.n < batch_size:
+            raise ValueError(f"dataset of {self.n} examples < batch size {batch_size}")
+        self.augment = augment
+        self.flatten = bool(flatten)
+        Hs, Ws, C = self.images.shape[1:]
+        if augment.mode == "pad_crop":
+            pad_crop_boxes(torch.zeros(1, 2, device="cpu"), Hs, Ws, augment.out_hw, augment.pad)   # validates
+        self._lut = augment.lut(C, self.dtype, device)
+        self._aug_gen = torch.Generator(device="cpu")
+        self._aug_gen.manual_seed(aug_seed)
+        self._eval_box = center_boxes(Hs, Ws, augment.eval_fraction).to(device)
+        self._whole_box = torch.tensor([[0, 0, Hs, Ws]], dtype=torch.int32, device=device)
+
+    @staticmethod
+    def _upload(images, device, num_shards, shard_index, chunk_bytes):
+        N = len(images)
+        n = len(range(shard_index, N, num_shards))
+        out = torch.empty((n,) + tuple(images.shape[1:]), dtype=torch.uint8, device=device)
+        row_bytes = int(np.prod(images.shape[1:]))
+        rows = max(1, chunk_bytes // max(1, row_bytes))          # source rows per chunk
+        pos = 0
+        for s in range(0, N, rows):
+            e = min(s + rows, N)
+            first = s + (shard_index - s) % num_shards           # this shard's first row in [s, e)
+            if first >= e:
+                continue
+            part = torch.from_numpy(np.array(images[first:e:num_shards]))   # one chunk's copy
+            out[pos:pos + len(part)].copy_(part)
+            pos += len(part)
+        assert pos == n, (pos, n)
+        return out
+
+    def _uniforms(self, B, k):
+        """[B, k] float64 uniforms of the augmentation generator (host)."""
+        return torch.rand(B, k, generator=self._aug_gen, dtype=torch.float64, device="cpu")
+
+    def _to_device(self, t):
+        if self.device.type == "cuda":
+            return t.pin_memory().to(self.device, non_blocking=True)
+        return t
+
+    def _train_boxes(self, B):
+        """-> (boxes int32 [B, 4], flip u8 [B]) of one training batch, on the dataset's device.
+        The boxes are B-sized, so they are formed on the host, where the uniforms are drawn (a few
+        dozen small device launches per step would cost more than the augmentation kernel
+        itself), and reach the device as one int32 [B, 5] copy: (y0, x0, h, w, flip)."""
+        a = self.augment
+        Hs, Ws = self.images.shape[1:3]
+        if a.mode == "random_resized_crop":
+            r = self._uniforms(B, RRC_ATTEMPTS * 4 + 1)
+            boxes = rrc_boxes(r[:, :-1].reshape(B, RRC_ATTEMPTS, 4), Hs, Ws, a.scale, a.ratio)
+        elif a.mode == "pad_crop":
+            r = self._uniforms(B, 3)
+            boxes = pad_crop_boxes(r[:, :2], Hs, Ws, a.out_hw, a.pad)
+        elif a.flip:
+            r = self._uniforms(B, 1)
+            boxes = torch.tensor([[0, 0, Hs, Ws]], dtype=torch.int32, device="cpu").expand(B, 4)
+        else:                                   # nothing random: no draw, no copy
+            return (self._whole_box.expand(B, 4).contiguous(),
+                    torch.zeros(B, dtype=torch.uint8, device=self.device))
+        flip = (r[:, -1] < 0.5) if a.flip else torch.zeros(B, dtype=torch.bool, device="cpu")
+        both = self._to_device(torch.cat([boxes, flip.to(torch.int32).unsqueeze(1)], dim=1))
+        return both[:, :4].contiguous(), both[:, 4].to(torch.uint8)
+
+    def single_pass(self, batch_size=None):
+        """This shard's examples in order, once, the remainder batch included, under the
+        evaluation transform (centre crop, no flip).  Touches neither generator nor the
+        training position."""
+        bs = int(batch_size or self.batch_size)
+        for pos in range(0, self.n, bs):
+            idx = torch.arange(pos, min(pos + bs, self.n), device=self.device)
+            yield self._gather(idx, train=False)
+
+    def _gather(self, idx, train=True):
+        from .. import ops
+        B = idx.numel()
+        if train:
+            boxes, flip = self._train_boxes(B)
+        else:
+            boxes = self._eval_box.expand(B, 4).contiguous()
+            flip = torch.zeros(B, dtype=torch.uint8, device=self.device)
+        x = ops.augment_images(self.images, idx.contiguous(), boxes, flip, self._lut,
+                               self.augment.out_hw, self.augment.fill)
+        if self.flatten:
+            x = x.reshape(B, -1)
+        return x, self.labels.index_select(0, idx)

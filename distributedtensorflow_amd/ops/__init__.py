@@ -317,6 +317,17 @@ def in_top_k(logits, labels, k):
     return (rank >= 0) & (rank < int(k))
 
 
+def augment_images(images, idx, boxes, flip, lut, out_hw, fill=0):
+    """One batch of an HBM-resident uint8 image set -> the model's input: gather ``idx``, crop
+    ``boxes`` (y0, x0, h, w; may reach outside the image, where ``fill`` is read), bilinear
+    resize to ``out_hw``, flip, and normalise through ``lut`` [C, 256] (whose dtype is the
+    output's).  Integer arithmetic, so both backends give the same bits; the rule is spelled out
+    in :func:`reference.augment_images`."""
+    if _use_native(images):
+        return _native().augment_images(images, idx, boxes, flip, lut, out_hw, fill)
+    return reference.augment_images(images, idx, boxes, flip, lut, out_hw, fill)
+
+
 # ----------------------------------------------------------------------------- variable fence
 # A colocated parameter server gathers the updated variable shards AFTER the optimizer step,
 # asynchronously, bucket by bucket, while the next forward already runs (parallel/ps_strategy.py).
@@ -360,7 +371,7 @@ _OPS = ("conv2d", "conv2d_bias_relu", "batch_norm", "batch_norm_add_batch_norm",
         "bias_dropout_add_layer_norm", "embedding_layer_norm", "bias_gelu", "bias_gelu_dense",
         "dense_gelu_dense", "relu", "max_pool2d", "global_avg_pool", "sparse_softmax_cross_entropy",
         "softmax_cross_entropy_clipped_sum", "gelu", "attention", "dropout", "attention_qkv",
-        "mlm_loss", "eval_rows", "in_top_k")
+        "mlm_loss", "eval_rows", "in_top_k", "augment_images")
 _FENCED = _OPS
 for _name in _OPS:
     globals()[_name] = _dispatch(_name, globals()[_name], True)
@@ -372,5 +383,5 @@ __all__ = [
     "max_pool2d", "global_avg_pool", "dense", "sparse_softmax_cross_entropy",
     "softmax_cross_entropy_clipped_sum", "layer_norm", "gelu", "attention", "dropout",
     "bias_dropout_add_layer_norm", "embedding_layer_norm", "bias_gelu", "bias_gelu_dense",
-    "dense_gelu_dense", "attention_qkv", "mlm_loss", "eval_rows", "in_top_k",
+    "dense_gelu_dense", "attention_qkv", "mlm_loss", "eval_rows", "in_top_k", "augment_images",
 ]

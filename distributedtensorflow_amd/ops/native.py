@@ -2011,6 +2011,26 @@ def metrics_accumulate(state, loss_rows, rank, weights, k):
     return state
 
 
+# ----------------------------------------------------------------------------- input pipeline
+
+def augment_images(images, idx, boxes, flip, lut, out_hw, fill=0, max_blocks=0):
+    """Gather + crop + bilinear resize + flip + normalise of one batch in ONE launch
+    (csrc/kernels/augment.hip; the rule: ops/reference.py augment_images, bit for bit).  An index
+    outside the set yields ``fill`` pixels rather than a read past the array (no device sync to
+    check it here).  ``max_blocks``: grid cap of this call (0 = the launcher's default)."""
+    from .reference import _augment_check
+    if not images.is_cuda:
+        raise ValueError("native augment_images needs GPU tensors")
+    B, Ho, Wo = _augment_check(images, idx, boxes, flip, lut, out_hw, fill)
+    N, Hs, Ws, C = images.shape
+    out = torch.empty(B, Ho, Wo, C, device=images.device, dtype=lut.dtype)
+    _K.augment_images(images.data_ptr(), idx.contiguous().data_ptr(),
+                      boxes.contiguous().data_ptr(), flip.contiguous().data_ptr(),
+                      lut.contiguous().data_ptr(), out.data_ptr(), N, B, Hs, Ws, C, Ho, Wo,
+                      int(fill), int(lut.dtype == _BF16), int(max_blocks), _st())
+    return out
+
+
 # ----------------------------------------------------------------------------- transformer ops
 # (LayerNorm / GELU / attention for BERT live in .native_nlp to keep this file focused)
 

@@ -323,6 +323,89 @@ def eval_rows(logits, labels, vocab=None, loss_dtype=torch.float32):
     return loss.to(loss_dtype), rank
 
 
+def _augment_check(images, idx, boxes, flip, lut, out_hw, fill):
+    """Shared argument validation of ``augment_images`` (both backends) -> (B, Ho, Wo)."""
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] not in (1, 3):
+        raise ValueError("augment_images: images must be uint8 [N, Hs, Ws, C] with C in {1, 3}")
+    if not images.is_contiguous() or images.shape[0] < 1:
+        raise ValueError("augment_images: images must be contiguous and non-empty")
+    C = images.shape[3]
+    Ho, Wo = (int(v) for v in out_hw)
+    if Ho < 1 or Wo < 1:
+        raise ValueError(f"augment_images: output size {out_hw}")
+    B = idx.numel()
+    if idx.dtype != torch.int64 or idx.dim() != 1:
+        raise ValueError("augment_images: idx must be int64 [B]")
+    if boxes.dtype != torch.int32 or tuple(boxes.shape) != (B, 4):
+        raise ValueError("augment_images: boxes must be int32 [B, 4] = (y0, x0, h, w)")
+    if flip.dtype != torch.uint8 or tuple(flip.shape) != (B,):
+        raise ValueError("augment_images: flip must be uint8 [B]")
+    if tuple(lut.shape) != (C, 256) or lut.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError("augment_images: lut must be bf16 / fp32 [C, 256]")
+    if not 0 <= int(fill) <= 255:
+        raise ValueError("augment_images: fill must be one byte")
+    for t in (idx, boxes, flip, lut):
+        if t.device != images.device:
+            raise ValueError("augment_images: every argument lives on the images' device")
+    return B, Ho, Wo
+
+
+def _augment_axis(o, O, side):
+    """Source position of output coordinates ``o`` [B, O] over box sides ``side`` [B] (int64):
+    half-pixel centres with 8 fractional bits -> (i0, i1, f), each [B, O]."""
+    side = side.unsqueeze(1)
+    pos = torch.div((2 * o + 1) * side * 256, 2 * O, rounding_mode="floor") - 128
+    pos = torch.minimum(pos.clamp(min=0), (side - 1) * 256)
+    i0 = pos >> 8
+    return i0, torch.minimum(i0 + 1, side - 1), pos & 255
+
+
+def augment_images(images, idx, boxes, flip, lut, out_hw, fill=0):
+    """Crop + bilinear resize + flip + per-channel normalisation of a gathered batch, in integer
+    arithmetic: the oracle of the ``augment_images`` kernel (csrc/kernels/augment.hip) and the
+    CPU path; both produce the same bits.
+
+    ``images`` u8 [N, Hs, Ws, C]; ``idx`` int64 [B]; ``boxes`` int32 [B, 4] = (y0, x0, h, w) in
+    source pixels, h, w >= 1, possibly reaching outside the image; ``flip`` u8 [B]; ``lut``
+    [C, 256] in the output dtype.  Output [B, Ho, Wo, C].  For output pixel (b, oy, ox):
+
+        ox' = Wo - 1 - ox if flip[b] else ox
+        per axis: pos = floor((2 o + 1) * side * 256 / (2 O)) - 128 in [0, (side - 1) * 256],
+                  i0 = pos >> 8, f = pos & 255, i1 = min(i0 + 1, side - 1)
+        taps (y0 + iy, x0 + ix); a tap outside the image reads ``fill``
+        v = ((256 - fy) ((256 - fx) p00 + fx p01) + fy ((256 - fx) p10 + fx p11) + 32768) >> 16
+        out = lut[c][v]
+
+    i.e. TF's ``resize_bilinear(half_pixel_centers=True)`` without antialiasing, weights
+    quantised to 1/256; a box of the output's size is an exact copy through the table."""
+    B, Ho, Wo = _augment_check(images, idx, boxes, flip, lut, out_hw, fill)
+    N, Hs, Ws, C = images.shape
+    dev = images.device
+    if B and (int(idx.min()) < 0 or int(idx.max()) >= N):
+        raise ValueError("augment_images: index outside the image set")
+    bx = boxes.long()
+    y0, x0, bh, bw = bx[:, 0:1], bx[:, 1:2], bx[:, 2], bx[:, 3]
+    oy = torch.arange(Ho, device=dev).unsqueeze(0).expand(B, Ho)
+    ox = torch.arange(Wo, device=dev).unsqueeze(0).expand(B, Wo)
+    ox = torch.where(flip.bool().unsqueeze(1), Wo - 1 - ox, ox)
+    iy0, iy1, fy = _augment_axis(oy, Ho, bh)
+    ix0, ix1, fx = _augment_axis(ox, Wo, bw)
+    n = idx.view(B, 1, 1)
+
+    def tap(iy, ix):
+        ty, tx = (y0 + iy).unsqueeze(2), (x0 + ix).unsqueeze(1)           # [B, Ho, 1], [B, 1, Wo]
+        ok = (ty >= 0) & (ty < Hs) & (tx >= 0) & (tx < Ws)
+        p = images[n, ty.clamp(0, Hs - 1), tx.clamp(0, Ws - 1)]           # [B, Ho, Wo, C]
+        return torch.where(ok.unsqueeze(3), p, p.new_tensor(int(fill))).to(torch.int32)
+
+    fy = fy.to(torch.int32).view(B, Ho, 1, 1)
+    fx = fx.to(torch.int32).view(B, 1, Wo, 1)
+    top = (256 - fx) * tap(iy0, ix0) + fx * tap(iy0, ix1)
+    bot = (256 - fx) * tap(iy1, ix0) + fx * tap(iy1, ix1)
+    v = ((256 - fy) * top + fy * bot + 32768) >> 16
+    return lut[torch.arange(C, device=dev).view(1, 1, 1, C), v.long()]
+
+
 def space_to_depth_operands(x, w, stride, pad, want_x=True):
     """Rewrite a strided conv (the ResNet stem: 7x7 / 2, pad 3, C = 3) as a stride-1 VALID conv
     on the space-to-depth input.  Output pixel p reads padded input rows s*p + r, r < R; with
