@@ -288,6 +288,19 @@ void dtf_augment_images(const uint8_t* images, const int64_t* idx, const int* bo
                         int Ws, int C, int Ho, int Wo, int fill, int out_bf16, int max_blocks,
                         hipStream_t st);
 
+// ---- mlm_mask.hip
+// the masking settings (data.TokenMasking), a kernel argument by value
+struct MlmMaskRule {
+  uint32_t vocab_size, pad_id, cls_id, sep_id, mask_id;
+  uint32_t random_low;      // random replacements are drawn from [random_low, vocab_size)
+  uint32_t prob_q16;        // round(prob * 65536)
+};
+void dtf_mlm_mask_tokens(const void* tokens, int token_bytes, const int64_t* idx,
+                         int64_t* input_ids, int64_t* segment_ids, int64_t* input_mask,
+                         int64_t* positions, int64_t* ids, float* weights, long N, int B, int S,
+                         int P, uint32_t seed, long ex_stride, long ex_offset,
+                         const MlmMaskRule& rule, int max_blocks, hipStream_t st);
+
 // ---- loss.hip
 void dtf_softmax_xent(const float* logits, const void* labels, int label_bytes, int B, int V,
                       float* loss_rows, float* grad, float grad_scale, hipStream_t st);
@@ -312,7 +325,8 @@ void dtf_adagrad(float* p, const float* g, float* acc, bf16_t* shadow, long n, c
                  float gscale, int* nonfinite, hipStream_t st);
 void dtf_lamb(float* p, float* g, float* m, float* v, bf16_t* shadow, const void* chunks,
               int nchunks, const float* hyper, const float* lr_ptr, float b1, float b2, float eps,
-              const float* wd_seg, float gscale, float* norms, int* nonfinite, hipStream_t st);
+              const float* wd_seg, float gscale, float* norms, float* partial, int* nonfinite,
+              hipStream_t st);
 int dtf_lamb_chunk_bytes();
 void dtf_lars(float* p, const float* g, float* a, bf16_t* shadow, const void* chunks, int nchunks,
               const void* segs, const float* lr_ptr, float momentum, float wd, float eeta,

@@ -1305,9 +1305,35 @@ segment_sum_kernel(const int64_t* __restrict__ sorted_ids, const int64_t* __rest
   if (i >= T) return;
   const int64_t id = sorted_ids[i];
   if (i > 0 && sorted_ids[i - 1] == id) return;
+  // The run's end first (gallop, then bisect: one load for a run of one), so that the row loop
+  // has no load in its condition and kSegAhead rows are in flight at once: real token sets repeat
+  // a few ids ([MASK], [PAD], [SEP]) thousands of times per batch, and a run walked one dependent
+  // load at a time took 11.7 ms of a 58 ms BERT-base step.  The rows are still added in run
+  // order, so the sums keep their bits.
+  constexpr int kSegAhead = 16;
+  int last = i, hi = T;                        // last: known in the run; hi: known past it (or T)
+  for (int step = 1; last + step < T; step <<= 1) {
+    if (sorted_ids[last + step] != id) { hi = last + step; break; }
+    last += step;
+  }
+  int end = last + 1;
+  while (end < hi) {
+    const int mid = end + ((hi - end) >> 1);
+    if (sorted_ids[mid] == id) end = mid + 1; else hi = mid;
+  }
   for (int c0 = lane * 4; c0 < H; c0 += 256) {
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int j = i; j < T && sorted_ids[j] == id; ++j) {
+    int j = i;
+    for (; j + kSegAhead <= end; j += kSegAhead) {
+      float v[kSegAhead][4];
+#pragma unroll
+      for (int k = 0; k < kSegAhead; ++k) load4(src + perm[j + k] * (long)H + c0, v[k]);
+#pragma unroll
+      for (int k = 0; k < kSegAhead; ++k)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc[e] += v[k][e];
+    }
+    for (; j < end; ++j) {
       float v[4];
       load4(src + perm[j] * (long)H + c0, v);
 #pragma unroll

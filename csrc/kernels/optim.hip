@@ -15,7 +15,7 @@
 //                                           others: g2 = g, s = lr;
 //                                           a = mu*a + s*g2;  p -= a
 //                                           (nesterov: p -= s*g2 + mu*a)
-//            Its norms are slab-reduced (bitwise reproducible); LAMB's use float atomics.
+//            Its norms and LAMB's are slab-reduced in a fixed order (bitwise reproducible).
 // Every kernel optionally writes the bf16 compute shadow of p in the same pass (saves the
 // separate cast of the fp32 master every step) and flags non-finite gradients.
 // Hyper-parameters that change per step (lr, lr_t) are read from DEVICE memory so a captured
@@ -106,7 +106,11 @@ adagrad_kernel(float* __restrict__ p, const float* __restrict__ g, float* __rest
   }
 }
 
-// ---- LAMB: chunk table entries {segment, start, len}; norms[seg] = {sum p^2, sum u^2}
+// ---- LAMB: chunk table entries {segment, start, len}; norms[seg] = {sum p^2, sum u^2}.
+// Phase 1 stores one partial {sum p^2, sum u^2} per chunk into a slab (plain stores); the norm
+// pass gives each tensor -- a run of rows with one segment in the table -- to the block of its
+// first row, which adds the rows in one fixed order; phase 2 reads the finished norms.  No float
+// atomics: the trust ratio and with it the whole update are bitwise reproducible.
 struct Chunk { int seg; int len; long start; };
 
 __global__ void __launch_bounds__(kT)
@@ -114,7 +118,7 @@ lamb_phase1_kernel(const float* __restrict__ p, float* __restrict__ g, float* __
                    float* __restrict__ v, const Chunk* __restrict__ chunks,
                    const float* __restrict__ hyper, float b1, float b2, float eps,
                    const float* __restrict__ wd_seg, float gscale,
-                   float* __restrict__ norms, int* nonfinite) {
+                   float2* __restrict__ partial, int* nonfinite) {
   // hyper[0] = 1/(1-b1^t), hyper[1] = 1/(1-b2^t)
   __shared__ float red[2][kT / 64];
   const Chunk c = chunks[blockIdx.x];
@@ -144,8 +148,34 @@ lamb_phase1_kernel(const float* __restrict__ p, float* __restrict__ g, float* __
   if (threadIdx.x == 0) {
     float a = 0.f, b = 0.f;
     for (int k = 0; k < kT / 64; ++k) { a += red[0][k]; b += red[1][k]; }
-    atomicAdd(&norms[2 * c.seg], a);
-    atomicAdd(&norms[2 * c.seg + 1], b);
+    partial[blockIdx.x] = make_float2(a, b);
+  }
+}
+
+__global__ void __launch_bounds__(kT)
+lamb_norm_kernel(const Chunk* __restrict__ chunks, int nchunks,
+                 const float2* __restrict__ partial, float* __restrict__ norms) {
+  __shared__ float red[2][kT / 64];
+  const int r0 = blockIdx.x;
+  const int seg = chunks[r0].seg;
+  if (r0 > 0 && chunks[r0 - 1].seg == seg) return;   // block-uniform: not the tensor's first row
+  // thread t adds rows r0 + t, r0 + t + kT, ... of the run in that order, then one wave / block
+  // tree; a tensor's rows are contiguous in the table, so a thread stops at the first other one
+  float sp = 0.f, su = 0.f;
+  for (int r = r0 + threadIdx.x; r < nchunks && chunks[r].seg == seg; r += kT) {
+    const float2 v = partial[r];
+    sp += v.x;
+    su += v.y;
+  }
+  sp = wave_sum(sp);
+  su = wave_sum(su);
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sp; red[1][threadIdx.x >> 6] = su; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float a = 0.f, b = 0.f;
+    for (int k = 0; k < kT / 64; ++k) { a += red[0][k]; b += red[1][k]; }
+    norms[2 * seg] = a;
+    norms[2 * seg + 1] = b;
   }
 }
 
@@ -337,10 +367,13 @@ void dtf_adagrad(float* p, const float* g, float* acc, bf16_t* shadow, long n,
 
 void dtf_lamb(float* p, float* g, float* m, float* v, bf16_t* shadow, const void* chunks,
               int nchunks, const float* hyper, const float* lr_ptr, float b1, float b2,
-              float eps, const float* wd_seg, float gscale, float* norms, int* nonfinite,
-              hipStream_t st) {
+              float eps, const float* wd_seg, float gscale, float* norms, float* partial,
+              int* nonfinite, hipStream_t st) {
   hipLaunchKernelGGL(lamb_phase1_kernel, dim3(nchunks), dim3(kT), 0, st, p, g, m, v,
-                     (const Chunk*)chunks, hyper, b1, b2, eps, wd_seg, gscale, norms, nonfinite);
+                     (const Chunk*)chunks, hyper, b1, b2, eps, wd_seg, gscale, (float2*)partial,
+                     nonfinite);
+  hipLaunchKernelGGL(lamb_norm_kernel, dim3(nchunks), dim3(kT), 0, st, (const Chunk*)chunks,
+                     nchunks, (const float2*)partial, norms);
   hipLaunchKernelGGL(lamb_phase2_kernel, dim3(nchunks), dim3(kT), 0, st, p, g, shadow,
                      (const Chunk*)chunks, lr_ptr, norms);
 }

@@ -99,7 +99,28 @@ def build_parser():
     p.add_argument("--num_classes", type=int, default=None,
                    help="classes of the --image_data set (default: 1000 for ResNet, 10 for MNIST "
                         "models)")
+    p.add_argument("--text_data", default=None, metavar="DIR",
+                   help="train a BERT model on DIR/train_tokens.npy (uint16 / int32 [N, S]), kept "
+                        "in device memory and masked on the device; the sequence length is the "
+                        "file's; --eval / --eval_every then evaluate on DIR/val_tokens.npy")
+    p.add_argument("--mlm_prob", type=float, default=0.15,
+                   help="share of a row's tokens chosen for prediction with --text_data")
+    p.add_argument("--max_predictions", type=int, default=20,
+                   help="masked positions per example with --text_data")
     return p
+
+
+def check_data_args(args):
+    """The data flags that cannot go together: a SystemExit names the offender."""
+    if args.text_data:
+        if args.image_data:
+            raise SystemExit("--text_data and --image_data cannot be combined")
+        if not args.model.startswith("bert"):
+            raise SystemExit(f"--text_data needs a BERT model, not {args.model}")
+        if not 0.0 <= args.mlm_prob <= 1.0:
+            raise SystemExit(f"--mlm_prob {args.mlm_prob} outside [0, 1]")
+        if args.max_predictions < 1:
+            raise SystemExit(f"--max_predictions {args.max_predictions} must be at least 1")
 
 
 DEFAULTS = {   # (batch, optimizer, learning rate) per model
@@ -171,6 +192,7 @@ def run(args):
                         get_or_create_global_step)
 
     print("run main with args =", args, flush=True)
+    check_data_args(args)
     batch, opt_name, lr = DEFAULTS[args.model]
     batch = args.batch_size or batch
     opt_name = args.optimizer or opt_name
@@ -227,6 +249,10 @@ def run(args):
         data = _image_dataset(args, "train", num_classes, batch, device, dtype, shards,
                               rid if shards > 1 else 0)
         batch = data.batch_size
+    elif args.text_data:
+        shards = nrep if server is None else 1
+        data = _token_dataset(args, "train", batch, device, shards, rid if shards > 1 else 0)
+        batch = data.batch_size
     elif args.model.startswith("mnist"):
         from .data import DeviceArrayDataset, mnist
         imgs, labels = mnist.load_arrays(args.data_dir, "train")
@@ -255,6 +281,9 @@ def run(args):
             model = dtf.models.MnistMLP(args.hidden_units)
         elif args.model.startswith("resnet"):
             model = getattr(dtf.models, args.model)()
+        elif args.text_data:
+            from .models import bert
+            model = getattr(bert, args.model)(vocab_size=data.masking.vocab_size)
         else:
             from .models import bert
             model = getattr(bert, args.model)()
@@ -270,7 +299,9 @@ def run(args):
     def train_op():
         if args.model.startswith("bert"):
             b = next(data)
-            w = torch.ones_like(b["masked_lm_ids"], dtype=torch.float32)
+            w = b.get("masked_lm_weights")
+            if w is None:                      # the synthetic set predicts every slot
+                w = torch.ones_like(b["masked_lm_ids"], dtype=torch.float32)
             loss = model(b["input_ids"], b["segment_ids"], b["input_mask"],
                          b["masked_lm_positions"], b["masked_lm_ids"], w)
         else:
@@ -344,7 +375,7 @@ def run(args):
         result["eval_loss"] = round(ev["loss"], 4)
         result["eval_top_1"] = round(ev["top_1"], 4)
         result["eval_top_k"] = round(ev["top_k"], 4)
-        if args.image_data:
+        if args.image_data or args.text_data:
             result["eval_count"] = int(ev["count"])
         elif args.model.startswith("mnist"):
             result["test_accuracy"] = round(ev["top_1"], 4)
@@ -383,6 +414,29 @@ def _image_dataset(args, split, num_classes, batch, device, dtype, shards, shard
                               flatten=args.model == "mnist_mlp")
 
 
+def _token_dataset(args, split, batch, device, shards, shard_index):
+    """--text_data: the HBM-resident ``split`` of DIR as a DeviceTokenDataset under --mlm_prob /
+    --max_predictions (and DIR/meta.json, where present); the batch shrinks to the shard where
+    that is smaller."""
+    from .data import DeviceTokenDataset, TokenMasking, load_token_arrays
+    tokens, masking = load_token_arrays(args.text_data, split, TokenMasking(prob=args.mlm_prob))
+    S = tokens.shape[1]
+    if S > 512 or args.max_predictions > S:
+        raise SystemExit(f"{args.text_data}: rows of {S} tokens; the sequence length is at most "
+                         f"512 and at least --max_predictions ({args.max_predictions})")
+    if device.type == "cuda" and S % 64:
+        raise SystemExit(f"{args.text_data}: rows of {S} tokens; the attention kernel needs a "
+                         "sequence length that is a multiple of 64")
+    batch = max(1, min(batch, len(range(shard_index, len(tokens), shards))))
+    # between-graph workers all hold the whole set: each shuffles and masks on its own stream
+    stream = args.task_index if args.job_name else shard_index
+    return DeviceTokenDataset(tokens, batch, device, masking, args.max_predictions,
+                              shuffle=split == "train", seed=args.seed + stream,
+                              mask_seed=args.seed + 1000003 * (stream + 1),
+                              eval_seed=args.seed & 0xFFFFFFFF, num_shards=shards,
+                              shard_index=shard_index)
+
+
 def _make_eval_fn(args, model, opt, strategy, device, dtype, batch, shards, shard_index):
     """-> eval_fn() -> {"loss", "top_1", "top_k", "count"}: one pass of this replica's shard of
     the evaluation set through ``train.evaluate`` (collective under a collective strategy)."""
@@ -391,6 +445,11 @@ def _make_eval_fn(args, model, opt, strategy, device, dtype, batch, shards, shar
     if args.image_data:
         num_classes = args.num_classes or (10 if args.model.startswith("mnist") else 1000)
         data = _image_dataset(args, "val", num_classes, batch, device, dtype, shards, shard_index)
+
+        def batches():
+            return data.single_pass()
+    elif args.text_data:
+        data = _token_dataset(args, "val", batch, device, shards, shard_index)
 
         def batches():
             return data.single_pass()
@@ -431,6 +490,7 @@ def main(argv=None):
     if args.optimizer == "lars" and args.learning_rate is None:
         # no LARS learning rate has been validated on real data: there is no default to fall to
         parser.error("--optimizer lars requires --learning_rate")
+    check_data_args(args)
     if (args.num_gpus or 0) > 1 and "WORLD_SIZE" not in os.environ and not args.job_name:
         return _spawn_local(args, argv)
     return run(args)

@@ -1,11 +1,13 @@
 """Input pipelines: tf.data-style Dataset, MNIST idx (offline synthetic fallback), HBM-resident
-array / image sets (the latter with fused on-device augmentation), synthetic ImageNet / MLM
-generators for benchmarks."""
-from . import images, mnist
+array / image / token sets (images with fused on-device augmentation, tokens with fused
+on-device masked-LM example creation), synthetic ImageNet / MLM generators for benchmarks."""
+from . import images, mnist, tokens
 from .dataset import Dataset, Iterator, NativeBatchDataset
 from .device import DeviceArrayDataset
 from .images import DeviceImageDataset, ImageAugment
 from .synthetic import SyntheticImageNet, SyntheticMLM
+from .tokens import DeviceTokenDataset, TokenMasking, load_token_arrays
 
-__all__ = ["images", "mnist", "Dataset", "DeviceArrayDataset", "DeviceImageDataset",
-           "ImageAugment", "Iterator", "NativeBatchDataset", "SyntheticImageNet", "SyntheticMLM"]
+__all__ = ["images", "mnist", "tokens", "Dataset", "DeviceArrayDataset", "DeviceImageDataset",
+           "DeviceTokenDataset", "ImageAugment", "Iterator", "NativeBatchDataset",
+           "SyntheticImageNet", "SyntheticMLM", "TokenMasking", "load_token_arrays"]

@@ -13,6 +13,32 @@ import numpy as np
 import torch
 
 
+def upload_sharded(array, device, num_shards=1, shard_index=0, chunk_bytes=256 << 20, view=None):
+    """Rows ``shard_index::num_shards`` of the (possibly memory-mapped) numpy ``array`` as one
+    device tensor.  The array is copied ``chunk_bytes`` at a time into a preallocated tensor, the
+    shard selection applied per chunk, so the host never holds a second copy of the set.
+    ``view``: a numpy dtype of the same width to reinterpret each chunk as (uint16 -> int16)."""
+    N = len(array)
+    n = len(range(shard_index, N, num_shards))
+    np_dtype = np.dtype(view) if view is not None else array.dtype
+    out = torch.empty((n,) + tuple(array.shape[1:]), device=device,
+                      dtype=torch.from_numpy(np.empty(0, np_dtype)).dtype)
+    row_bytes = int(np.prod(array.shape[1:])) * array.dtype.itemsize
+    rows = max(1, chunk_bytes // max(1, row_bytes))              # source rows per chunk
+    pos = 0
+    for s in range(0, N, rows):
+        e = min(s + rows, N)
+        first = s + (shard_index - s) % num_shards               # this shard's first row in [s, e)
+        if first >= e:
+            continue
+        part = np.array(array[first:e:num_shards])               # one chunk's copy
+        part = torch.from_numpy(part.view(np_dtype) if view is not None else part)
+        out[pos:pos + len(part)].copy_(part)
+        pos += len(part)
+    assert pos == n, (pos, n)
+    return out
+
+
 class DeviceArrayDataset:
     def __init__(self, images, labels, batch_size, device, dtype=None, shuffle=False, seed=0,
                  num_shards=1, shard_index=0, scale=1.0 / 255.0, drop_remainder=True):

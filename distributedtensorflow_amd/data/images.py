@@ -25,7 +25,7 @@ import os
 import numpy as np
 import torch
 
-from .device import DeviceArrayDataset
+from .device import DeviceArrayDataset, upload_sharded
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -223,22 +223,7 @@ class DeviceImageDataset(DeviceArrayDataset):
 
     @staticmethod
     def _upload(images, device, num_shards, shard_index, chunk_bytes):
-        N = len(images)
-        n = len(range(shard_index, N, num_shards))
-        out = torch.empty((n,) + tuple(images.shape[1:]), dtype=torch.uint8, device=device)
-        row_bytes = int(np.prod(images.shape[1:]))
-        rows = max(1, chunk_bytes // max(1, row_bytes))          # source rows per chunk
-        pos = 0
-        for s in range(0, N, rows):
-            e = min(s + rows, N)
-            first = s + (shard_index - s) % num_shards           # this shard's first row in [s, e)
-            if first >= e:
-                continue
-            part = torch.from_numpy(np.array(images[first:e:num_shards]))   # one chunk's copy
-            out[pos:pos + len(part)].copy_(part)
-            pos += len(part)
-        assert pos == n, (pos, n)
-        return out
+        return upload_sharded(images, device, num_shards, shard_index, chunk_bytes)
 
     def _uniforms(self, B, k):
         """[B, k] float64 uniforms of the augmentation generator (host)."""

@@ -1,0 +1,167 @@
+"""HBM-resident token sets with fused on-device masked-LM example creation.
+
+A tokenised pre-training corpus fits the device whole (English Wikipedia + BooksCorpus is about
+3.3 G tokens: 6.6 GB as uint16, of 288 GB of HBM3E), so it is uploaded once and every BERT batch
+is ONE kernel (``ops.mlm_mask_tokens``): gather, input mask and segment ids, the choice of the
+positions to predict and the 80 / 10 / 10 replacement.  That is dynamic masking -- a fresh mask
+each time an example is seen -- with no host pipeline and no per-step copy: the only per-step
+host work is drawing one 32-bit seed, which reaches the kernel by value.
+
+On disk a set is one array per split in one directory (:func:`load_token_arrays`):
+
+    {split}_tokens.npy   uint16 or int32 [N, S], S <= 512   (memory-mapped, never copied whole)
+    meta.json            optional: vocab_size, pad_id, cls_id, sep_id, mask_id
+
+A row is one packed example, ``[CLS] a ... [SEP] b ... [SEP] pad ...``; segment ids and the input
+mask are derived from it, so nothing else is stored.
+"""
+from __future__ import annotations
+
+import json
+import os
+
+import numpy as np
+import torch
+
+from .device import DeviceArrayDataset, upload_sharded
+
+META_KEYS = ("vocab_size", "pad_id", "cls_id", "sep_id", "mask_id")
+
+
+class TokenMasking:
+    """The settings of the masking rule (``ops.reference.mlm_mask_tokens``): the vocabulary and
+    its special ids (BERT's uncased WordPiece defaults), the masking probability ``prob`` and
+    ``random_low``, the smallest id a random replacement may take.  ``prob_q16`` is
+    ``round(prob * 65536)``, the form the integer rule uses."""
+
+    def __init__(self, vocab_size=30522, pad_id=0, cls_id=101, sep_id=102, mask_id=103, prob=0.15,
+                 random_low=0):
+        self.vocab_size, self.random_low = int(vocab_size), int(random_low)
+        self.pad_id, self.cls_id, self.sep_id, self.mask_id = (int(pad_id), int(cls_id),
+                                                               int(sep_id), int(mask_id))
+        self.prob = float(prob)
+        if self.vocab_size < 1:
+            raise ValueError(f"TokenMasking: vocab_size {vocab_size}")
+        for name in ("pad_id", "cls_id", "sep_id", "mask_id", "random_low"):
+            if not 0 <= getattr(self, name) < self.vocab_size:
+                raise ValueError(f"TokenMasking: {name} {getattr(self, name)} outside the "
+                                 f"vocabulary of {self.vocab_size}")
+        if not 0.0 <= self.prob <= 1.0:
+            raise ValueError(f"TokenMasking: prob {prob} outside [0, 1]")
+        self.prob_q16 = int(round(self.prob * 65536))
+
+    def replace(self, **kw):
+        """A copy with some settings changed."""
+        cur = {k: getattr(self, k) for k in META_KEYS + ("prob", "random_low")}
+        cur.update(kw)
+        return TokenMasking(**cur)
+
+    def __repr__(self):
+        return "TokenMasking({})".format(", ".join(
+            f"{k}={getattr(self, k)}" for k in META_KEYS + ("prob", "random_low")))
+
+
+def load_token_arrays(data_dir, split, masking=None):
+    """-> (tokens, masking): ``{split}_tokens.npy`` (uint16 or int32 [N, S], memory-mapped) and
+    the :class:`TokenMasking` it is read under -- ``masking`` (default: BERT's) with the settings
+    of an optional ``meta.json`` laid over it.  Raises ValueError on a wrong dtype or rank, a
+    negative id, an id ``>= vocab_size``, or an unknown meta.json key."""
+    masking = masking or TokenMasking()
+    mpath = os.path.join(data_dir, "meta.json")
+    if os.path.exists(mpath):
+        with open(mpath) as f:
+            meta = json.load(f)
+        unknown = sorted(set(meta) - set(META_KEYS)) if isinstance(meta, dict) else ["<not a map>"]
+        if unknown:
+            raise ValueError(f"{mpath}: unknown settings {unknown}; expected some of {META_KEYS}")
+        masking = masking.replace(**meta)
+    path = os.path.join(data_dir, f"{split}_tokens.npy")
+    tokens = np.load(path, mmap_mode="r")
+    if tokens.dtype not in (np.uint16, np.int32):
+        raise ValueError(f"{path}: dtype {tokens.dtype}, expected uint16 or int32")
+    if tokens.ndim != 2 or tokens.shape[1] < 1:
+        raise ValueError(f"{path}: shape {tokens.shape}, expected [N, S]")
+    if tokens.dtype == np.uint16 and masking.vocab_size > 65536:
+        raise ValueError(f"{path}: uint16 tokens cannot hold a vocabulary of {masking.vocab_size}")
+    step = max(1, (64 << 20) // (tokens.shape[1] * tokens.dtype.itemsize))
+    for s in range(0, len(tokens), step):                 # bounded working set over the map
+        part = tokens[s:s + step]
+        lo, hi = int(part.min()), int(part.max())
+        if lo < 0:
+            raise ValueError(f"{path}: negative id {lo}")
+        if hi >= masking.vocab_size:
+            raise ValueError(f"{path}: id {hi} >= vocab_size {masking.vocab_size}")
+    return tokens, masking
+
+
+class DeviceTokenDataset(DeviceArrayDataset):
+    """A :class:`DeviceArrayDataset` of token rows whose batches are masked-LM examples made on
+    the device by one kernel; a batch is the dict :class:`SyntheticMLM` yields plus
+    ``masked_lm_weights``.  Example order, epochs, sharding and the shuffle generator are the
+    parent's.  ``__next__`` draws one 32-bit seed per batch from a CPU generator of its own
+    (``mask_seed``), so an example gets a fresh mask each time it is seen and the same seeds give
+    the same batches on the CPU and on the GPU.  ``single_pass()`` uses the fixed ``eval_seed``
+    and touches no generator: the rule keys on the GLOBAL example number (``shard_index +
+    k * num_shards`` for local row k), so evaluation masks depend on (``eval_seed``, example)
+    alone -- not on the batch size, the sharding or how often evaluation runs -- and an evaluation
+    between two steps leaves training bit-identical.
+
+    ``tokens``: uint16 or int32 [N, S] (numpy, possibly memory-mapped); 16-bit sets are held as
+    their int16 reinterpretation and read unsigned.  Upload: chunked and shard-strided
+    (:func:`upload_sharded`)."""
+
+    def __init__(self, tokens, batch_size, device, masking=None, max_predictions=20,
+                 shuffle=False, seed=0, mask_seed=0, eval_seed=0, num_shards=1, shard_index=0,
+                 drop_remainder=True, chunk_bytes=256 << 20):
+        device = torch.device(device)
+        masking = masking or TokenMasking()
+        if tokens.dtype not in (np.uint16, np.int32) or tokens.ndim != 2:
+            raise ValueError("DeviceTokenDataset: tokens must be uint16 or int32 [N, S]")
+        if not 0 <= shard_index < num_shards:
+            raise ValueError(f"DeviceTokenDataset: shard {shard_index} of {num_shards}")
+        if not 0 <= int(eval_seed) < (1 << 32):
+            raise ValueError("DeviceTokenDataset: eval_seed must be in [0, 2^32)")
+        self.tokens = upload_sharded(tokens, device, num_shards, shard_index, int(chunk_bytes),
+                                     view=np.int16 if tokens.dtype == np.uint16 else None)
+        self.n = len(self.tokens)
+        self.batch_size = batch_size
+        self.device = device
+        self.masking = masking
+        self.max_predictions = int(max_predictions)
+        self.num_shards, self.shard_index = int(num_shards), int(shard_index)
+        self.shuffle = shuffle
+        self.drop_remainder = drop_remainder
+        self._gen = torch.Generator(device=device)
+        self._gen.manual_seed(seed)
+        self._order = None
+        self._pos = 0
+        self.epoch = 0
+        if self.n < batch_size:
+            raise ValueError(f"dataset of {self.n} examples < batch size {batch_size}")
+        self._mask_gen = torch.Generator(device="cpu")
+        self._mask_gen.manual_seed(mask_seed)
+        self.eval_seed = int(eval_seed)
+        from ..ops.reference import _mlm_check            # validates S, P and the ids now
+        _mlm_check(self.tokens, torch.zeros(0, dtype=torch.int64, device=device), 0,
+                   self.max_predictions, masking)
+
+    @property
+    def seq_len(self):
+        return self.tokens.shape[1]
+
+    def single_pass(self, batch_size=None):
+        """This shard's examples in order, once, the remainder batch included, masked under
+        ``eval_seed``.  Touches neither generator nor the training position."""
+        bs = int(batch_size or self.batch_size)
+        for pos in range(0, self.n, bs):
+            idx = torch.arange(pos, min(pos + bs, self.n), device=self.device)
+            yield self._gather(idx, seed=self.eval_seed)
+
+    def _gather(self, idx, seed=None):
+        from .. import ops
+        if seed is None:                                   # a training batch: a fresh seed
+            seed = int(torch.randint(0, 1 << 32, (1,), generator=self._mask_gen,
+                                     dtype=torch.int64, device="cpu"))
+        return ops.mlm_mask_tokens(self.tokens, idx.contiguous(), seed, self.max_predictions,
+                                   self.masking, example_stride=self.num_shards,
+                                   example_offset=self.shard_index)

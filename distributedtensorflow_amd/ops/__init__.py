@@ -328,6 +328,22 @@ def augment_images(images, idx, boxes, flip, lut, out_hw, fill=0):
     return reference.augment_images(images, idx, boxes, flip, lut, out_hw, fill)
 
 
+def mlm_mask_tokens(tokens, idx, seed, max_predictions, masking, example_stride=1,
+                    example_offset=0):
+    """One batch of an HBM-resident token set -> BERT's masked-LM inputs: gather ``idx`` from
+    ``tokens`` [N, S] (16-bit or int32 storage, read unsigned), derive ``input_mask`` and
+    ``segment_ids``, choose up to ``max_predictions`` positions and apply the 80 / 10 / 10
+    replacement under ``masking`` (a :class:`data.TokenMasking`).  Everything random is a
+    counter-based hash of (``seed``, example number, position), the example number being
+    ``example_offset + idx * example_stride``; integer arithmetic, so both backends give the same
+    bits.  The rule is spelled out in :func:`reference.mlm_mask_tokens`."""
+    if _use_native(tokens):
+        return _native().mlm_mask_tokens(tokens, idx, seed, max_predictions, masking,
+                                         example_stride, example_offset)
+    return reference.mlm_mask_tokens(tokens, idx, seed, max_predictions, masking, example_stride,
+                                     example_offset)
+
+
 # ----------------------------------------------------------------------------- variable fence
 # A colocated parameter server gathers the updated variable shards AFTER the optimizer step,
 # asynchronously, bucket by bucket, while the next forward already runs (parallel/ps_strategy.py).
@@ -371,7 +387,7 @@ _OPS = ("conv2d", "conv2d_bias_relu", "batch_norm", "batch_norm_add_batch_norm",
         "bias_dropout_add_layer_norm", "embedding_layer_norm", "bias_gelu", "bias_gelu_dense",
         "dense_gelu_dense", "relu", "max_pool2d", "global_avg_pool", "sparse_softmax_cross_entropy",
         "softmax_cross_entropy_clipped_sum", "gelu", "attention", "dropout", "attention_qkv",
-        "mlm_loss", "eval_rows", "in_top_k", "augment_images")
+        "mlm_loss", "eval_rows", "in_top_k", "augment_images", "mlm_mask_tokens")
 _FENCED = _OPS
 for _name in _OPS:
     globals()[_name] = _dispatch(_name, globals()[_name], True)
@@ -384,4 +400,5 @@ __all__ = [
     "softmax_cross_entropy_clipped_sum", "layer_norm", "gelu", "attention", "dropout",
     "bias_dropout_add_layer_norm", "embedding_layer_norm", "bias_gelu", "bias_gelu_dense",
     "dense_gelu_dense", "attention_qkv", "mlm_loss", "eval_rows", "in_top_k", "augment_images",
+    "mlm_mask_tokens",
 ]

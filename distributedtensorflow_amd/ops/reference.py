@@ -406,6 +406,111 @@ def augment_images(images, idx, boxes, flip, lut, out_hw, fill=0):
     return lut[torch.arange(C, device=dev).view(1, 1, 1, C), v.long()]
 
 
+MLM_MAX_SEQ = 512
+
+
+def _mlm_check(tokens, idx, seed, max_predictions, masking):
+    """Shared argument validation of ``mlm_mask_tokens`` (both backends) -> (B, S, P, rule) with
+    ``rule = [vocab_size, pad_id, cls_id, sep_id, mask_id, random_low, prob_q16]``."""
+    if tokens.dim() != 2 or tokens.dtype not in (torch.uint16, torch.int16, torch.int32):
+        raise ValueError("mlm_mask_tokens: tokens must be [N, S], 16-bit or int32 storage")
+    if not tokens.is_contiguous() or tokens.shape[0] < 1:
+        raise ValueError("mlm_mask_tokens: tokens must be contiguous and non-empty")
+    S, P = tokens.shape[1], int(max_predictions)
+    if not 1 <= S <= MLM_MAX_SEQ:
+        raise ValueError(f"mlm_mask_tokens: sequence length {S} outside [1, {MLM_MAX_SEQ}]")
+    if not 1 <= P <= S:
+        raise ValueError(f"mlm_mask_tokens: max_predictions {P} outside [1, {S}]")
+    if idx.dtype != torch.int64 or idx.dim() != 1:
+        raise ValueError("mlm_mask_tokens: idx must be int64 [B]")
+    if idx.device != tokens.device:
+        raise ValueError("mlm_mask_tokens: idx lives on the tokens' device")
+    if not 0 <= int(seed) < (1 << 32):
+        raise ValueError("mlm_mask_tokens: seed must be in [0, 2^32)")
+    V = int(masking.vocab_size)
+    if V < 1 or V > (1 << 31) or (tokens.element_size() == 2 and V > 65536):
+        raise ValueError(f"mlm_mask_tokens: vocab_size {V} does not fit the token storage")
+    for name in ("pad_id", "cls_id", "sep_id", "mask_id", "random_low"):
+        if not 0 <= int(getattr(masking, name)) < V:
+            raise ValueError(f"mlm_mask_tokens: {name} outside the vocabulary")
+    q = int(masking.prob_q16)
+    if not 0 <= q <= 65536:
+        raise ValueError("mlm_mask_tokens: prob must be in [0, 1]")
+    rule = [V, int(masking.pad_id), int(masking.cls_id), int(masking.sep_id),
+            int(masking.mask_id), int(masking.random_low), q]
+    return idx.numel(), S, P, rule
+
+
+def mlm_mask_tokens(tokens, idx, seed, max_predictions, masking, example_stride=1,
+                    example_offset=0):
+    """Masked-LM example creation for a gathered batch of token rows, in integer arithmetic: the
+    oracle of the ``mlm_mask_tokens`` kernel (csrc/kernels/mlm_mask.hip) and the CPU path; both
+    produce the same bits.
+
+    ``tokens`` [N, S] (uint16 / int16 / int32 storage, read unsigned); ``idx`` int64 [B];
+    ``seed`` in [0, 2^32); ``masking`` a :class:`data.TokenMasking`.  -> dict of ``input_ids``,
+    ``segment_ids``, ``input_mask`` (int64 [B, S]), ``masked_lm_positions``, ``masked_lm_ids``
+    (int64 [B, P]) and ``masked_lm_weights`` (fp32 [B, P]).  Row b reads example ``idx[b]`` and
+    keys its hashes on the example number ``n = example_offset + idx[b] * example_stride`` (a
+    shard of a set passes its global numbers).  All hashes are uint32, ``t[j]`` the stored token:
+
+        row_seed = fmix32(lo32(n) * 0x9E3779B1 + seed) ^ hi32(n)
+        key[j]   = fmix32(j * 0x9E3779B1 + row_seed)
+        input_mask[j]  = t[j] != pad_id
+        segment_ids[j] = input_mask[j] and j > (index of the first sep_id); no sep_id: all 0
+        candidates: t[j] not in {pad_id, cls_id, sep_id}; nc of them
+        T = 0 if nc == 0 else min(P, nc, max(1, (nc * prob_q16 + 32768) >> 16))
+        selected: the T candidates with the smallest (key[j], j), listed in ascending j:
+            slot s < T: positions = j, ids = t[j], weights = 1;  slots s >= T: 0, 0, 0.0
+        at a selected j: h2 = fmix32(key[j] + 0x85EBCA6B), d = ((h2 & 0xFFFF) * 10) >> 16
+            d < 8: mask_id;  d == 8: t[j];
+            d == 9: random_low + ((fmix32(h2 + 0x9E3779B1) * (vocab_size - random_low)) >> 32)
+        every other position copies t[j]
+
+    An ``idx[b]`` outside [0, N) yields an all-pad row with weights 0."""
+    B, S, P, rule = _mlm_check(tokens, idx, seed, max_predictions, masking)
+    V, pad, cls, sep, mask_id, low, q = rule
+    N, dev = tokens.shape[0], tokens.device
+    store = tokens.view(torch.int16) if tokens.dtype == torch.uint16 else tokens
+    ok = (idx >= 0) & (idx < N)
+    t = store.index_select(0, idx.clamp(0, N - 1)).long() & ((1 << (8 * store.element_size())) - 1)
+    t = torch.where(ok.unsqueeze(1), t, torch.full_like(t, pad))
+    n = idx * int(example_stride) + int(example_offset)                 # wraps like uint64
+    row_seed = _fmix32(((n & _M32) * 0x9E3779B1 + int(seed)) & _M32) ^ ((n >> 32) & _M32)
+    j = torch.arange(S, device=dev).unsqueeze(0)
+    key = _fmix32((j * 0x9E3779B1 + row_seed.unsqueeze(1)) & _M32)       # [B, S]
+
+    real = t != pad
+    is_sep = t == sep
+    first = torch.where(is_sep.any(1), torch.argmax(is_sep.to(torch.uint8), 1),
+                        torch.full_like(idx, S))
+    segment = real & (j > first.unsqueeze(1))
+    cand = real & (t != cls) & (t != sep)
+    nc = cand.sum(1)
+    T = torch.minimum(torch.clamp((nc * q + 32768) >> 16, min=1), nc).clamp(max=P)
+    # (key, j) pairs as one integer; no candidate ranks below nc, so none is ever selected
+    pair = torch.where(cand, key * 1024 + j, torch.full_like(key, 1 << 62))
+    rank = torch.empty_like(pair)
+    rank.scatter_(1, pair.argsort(1), j.expand(B, S).contiguous())
+    sel = cand & (rank < T.unsqueeze(1))
+
+    h2 = _fmix32((key + 0x85EBCA6B) & _M32)
+    d = ((h2 & 0xFFFF) * 10) >> 16
+    rnd = low + ((_fmix32((h2 + 0x9E3779B1) & _M32) * (V - low)) >> 32)
+    new = torch.where(d < 8, torch.full_like(t, mask_id), torch.where(d == 8, t, rnd))
+    input_ids = torch.where(sel, new, t)
+
+    # slot of a selected position: the selected positions below it; the rest land in a spare column
+    slot = torch.where(sel, sel.cumsum(1) - 1, torch.full_like(t, P))
+    positions = torch.zeros(B, P + 1, dtype=torch.int64, device=dev)
+    positions.scatter_(1, slot, j.expand(B, S).contiguous())
+    ids = torch.zeros(B, P + 1, dtype=torch.int64, device=dev).scatter_(1, slot, t)
+    weights = (torch.arange(P, device=dev).unsqueeze(0) < T.unsqueeze(1)).float()
+    return {"input_ids": input_ids, "segment_ids": segment.long(), "input_mask": real.long(),
+            "masked_lm_positions": positions[:, :P].contiguous(),
+            "masked_lm_ids": ids[:, :P].contiguous(), "masked_lm_weights": weights}
+
+
 def space_to_depth_operands(x, w, stride, pad, want_x=True):
     """Rewrite a strided conv (the ResNet stem: 7x7 / 2, pad 3, C = 3) as a stride-1 VALID conv
     on the space-to-depth input.  Output pixel p reads padded input rows s*p + r, r < R; with

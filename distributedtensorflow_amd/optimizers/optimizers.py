@@ -193,7 +193,12 @@ class AdagradOptimizer(Optimizer):
 
 class LAMBOptimizer(Optimizer):
     """LAMB (layer-wise adaptive moments, You et al. 2019) for BERT pre-training
-    (BASELINE.json config 5): per-variable trust ratio |p|/|u|."""
+    (BASELINE.json config 5): per-variable trust ratio |p|/|u|.
+
+    GPU: three launches over the chunk table.  Phase 1 updates m and v, leaves the update
+    direction in the gradient buffer and stores one partial {sum p^2, sum u^2} per chunk into a
+    slab; a small norm pass adds each tensor's rows in one fixed order; phase 2 applies the step.
+    No float atomics, so results are bitwise reproducible."""
 
     slot_names = ("adam_m", "adam_v")     # google-research/bert optimization.py slot names
     elementwise = False
@@ -222,7 +227,11 @@ class LAMBOptimizer(Optimizer):
         self._rows = rows
         self._tables = {}
         self._wd_seg = torch.tensor(wd, dtype=torch.float32, device=sp.device)
-        self._norms = torch.zeros(2 * self._nseg, dtype=torch.float32, device=sp.device)
+        # {sum p^2, sum u^2} per variable, then the slab of per-row partials they are summed from
+        # in a fixed order (one tensor: a parameter-server shard that applies concurrently on
+        # several streams gives every stream its own copy)
+        self._norms = torch.zeros(2 * self._nseg + 2 * max(1, len(rows)), dtype=torch.float32,
+                                  device=sp.device)
         self._hyper = torch.zeros(4, dtype=torch.float32, device=sp.device)
 
     def _chunk_table(self):
@@ -256,7 +265,7 @@ class LAMBOptimizer(Optimizer):
                   _sh(sp, 0), chunks.data_ptr(), nchunks, self._hyper.data_ptr(),
                   self._lr_dev.data_ptr(), float(self.beta1), float(self.beta2),
                   float(self.epsilon), self._wd_seg.data_ptr(), gscale, self._norms.data_ptr(),
-                  self._nonfinite.data_ptr(), _st())
+                  self._norms.data_ptr() + 8 * self._nseg, self._nonfinite.data_ptr(), _st())
 
     def _apply_reference(self, gscale):
         t = self.iterations
