@@ -125,7 +125,12 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(const LnArgs g) {
   for (int i = 0; i < NV; ++i)
 #pragma unroll
     for (int e = 0; e < 4; ++e) sum += v[i][e];
-  const float mean = wave_sum(sum) * (1.f / H);
+  // The backward reads this ROUNDED product, so the forward must subtract the same value: keep
+  // the compiler from fusing the multiply into v - mean (the fma subtracts the unrounded product;
+  // at H = 768, where fl(1/H) is inexact, a constant row came out as d = 1.5e-8 instead of 0,
+  // which rstd = rsqrt(eps) = 1e6 turned into 1.5e-2 of y)
+  float mean = wave_sum(sum) * (1.f / H);
+  asm volatile("" : "+v"(mean));   // opaque: -ffp-contract=fast fuses across a contract(off) pragma
   float sq = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i)
@@ -312,7 +317,8 @@ __global__ void __launch_bounds__(256) ln_fwd_wide_kernel(const LnArgs g) {
   for (int i = 0; i < NC; ++i)
 #pragma unroll
     for (int e = 0; e < 8; ++e) sum += v[i][e];
-  const float mean = half_sum(sum) * (1.f / H);
+  float mean = half_sum(sum) * (1.f / H);
+  asm volatile("" : "+v"(mean));   // rounded before it is subtracted (see ln_fwd_kernel)
   float sq = 0.f;
 #pragma unroll
   for (int i = 0; i < NC; ++i)
@@ -1350,7 +1356,7 @@ segment_sum_kernel(const int64_t* __restrict__ sorted_ids, const int64_t* __rest
 // One wave per masked position.  Rows are `ld` elements apart (ld >= V): the tied MLM decoder runs
 // on a vocabulary padded to a multiple of 64 (30528 for BERT's 30522), whose last ld - V logits
 // are not classes -- they are left out of the softmax and their gradient is written as exact 0.
-// With ld == V (rows only 4-B aligned) the row is swept in 16-B chunks from the 16-B-aligned
+// With ld == V (rows only 2-B aligned) the row is swept in 16-B chunks from the 16-B-aligned
 // address below its start with raw buffer loads (range-checked: the chunk before row 0 / past the
 // last row reads zeros), elements outside the row masked.
 // Online (max, sum) with one rescale per 8 elements; the gradient pass stores whole 16-B chunks
@@ -1362,7 +1368,12 @@ mlm_xent_kernel(const bf16_t* __restrict__ logits, const int64_t* __restrict__ l
   const int row = (blockIdx.x * 256 + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
   if (row >= N) return;
-  const auto rl = buffer_rsrc(logits, (uint32_t)N * ld * 2u);
+  // The range check of a raw buffer load is per dword: with N * ld odd the last logit shares its
+  // dword with 2 bytes past the tensor, and a range that ends at the tensor's last byte made that
+  // dword read as zero (the last class of the last row entered the softmax as logit 0).  The
+  // range therefore ends at the dword boundary; the 2 bytes beyond are masked like any slot
+  // outside the row.
+  const auto rl = buffer_rsrc(logits, ((uint32_t)N * ld * 2u + 3u) & ~3u);
   const uint32_t b0 = (uint32_t)row * ld * 2u;
   const uint32_t a0 = b0 & ~15u;
   const int head = (int)(b0 - a0) >> 1;

@@ -280,7 +280,12 @@ def dense_gelu_dense(x, w1, b1, w2):
 
 
 def attention_qkv(qkv, mask, batch, seq_len, heads, p=0.0, training=True, scale=None):
-    """Multi-head self-attention straight from the fused QKV projection output."""
+    """Multi-head self-attention straight from the fused QKV projection output.
+
+    ``mask`` is an additive fp32 ``[batch, seq_len]`` key mask and must be FINITE (BERT passes
+    -10000 for padding).  The native kernels keep a running row maximum per 64 keys: with
+    ``-inf`` over a whole first 64-key chunk the rescale evaluates ``exp2(-inf - -inf)`` and the
+    row becomes NaN."""
     if _use_native(qkv):
         return _nlp().attention_qkv(qkv, mask, batch, seq_len, heads, p, training, scale)
     return reference.attention_qkv(qkv, mask, batch, seq_len, heads, p, training, scale)
