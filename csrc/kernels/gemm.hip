@@ -46,6 +46,11 @@ struct GemmArgs {
   // tap table; row m = output pixel (n, p, q), K index = tap * C + channel (C % 64 == 0)
   int H, W, Cc, P, Q, sh, sw, ntaps;
   int tdh[9], tdw[9];
+  // the persistent kernel's per-tap pair: [0] the byte offset of tap t from the receptive field's
+  // corner, (dh W + dw) C 2; [1] its validity selector, bit (dh - dh0) | bit (8 + dw - dw0), with
+  // dh0 / dw0 the smallest deltas of the table (the kernel takes tables spanning < 8 each way)
+  int tsel[9][2];
+  int dh0, dw0;
   int Ho, Wo, osh, osw, oh0, ow0;   // output rows: (n, p*osh + oh0, q*osw + ow0) of [N][Ho][Wo]
   int nt;                           // non-temporal C stores
   int dbg;                          // timing probes (tools/gemm_overhead.py): 1 = skip epilogue
@@ -1097,7 +1102,10 @@ gemm_pp_kernel(const GemmArgs g) {
 //   * the buffer descriptors span the WHOLE operands (host: < 2^31 bytes), built once;
 //   * every piece's per-lane source offset (dense) or image pixel / receptive-field corner (CONV)
 //     is computed ONCE per tile for the current AND the next tile; a look-ahead issue selects
-//     between the two sets with a wave-uniform condition (v_cndmask), nothing else;
+//     between the two sets with a wave-uniform condition (v_cndmask), nothing else -- the CONV
+//     form adds the K-step's scalar tap + channel offset, carried in a cursor per look-ahead
+//     distance, and tests the tap's validity bits (no division, table load or bounds test in
+//     the issue: profiles/CONV_GEMM_ISSUE.md);
 //   * K % 64 == 0 (no K-tail test in the issue).
 // The epilogue (bias / ReLU / BN statistics / Cin / masked acc, strided dgrad phases) and the
 // counted waits around the stores are gemm_pp's.
@@ -1105,7 +1113,9 @@ gemm_pp_kernel(const GemmArgs g) {
 // 1 BN statistics, 2 accumulate (Cin / masked acc), 4 strided (dgrad phase) output rows,
 // 8 / 16 GELU forward / backward (below), 32 ReLU (a compile-time bit: as the runtime flag it
 // cost a v_max + v_cndmask per output element in every epilogue, ReLU or not)
-template <int CONV, int EPI>
+// TAP0 (probe builds only, wrong results): every CONV A piece reads tap 0 / channel block 0 --
+// the issue path with no per-step state at all, the ceiling of what the tap cursors can reach
+template <int CONV, int EPI, bool TAP0 = false>
 __global__ void __launch_bounds__(512, 1)
 gemm_pp2_kernel(const GemmArgs g) {
   using Cf = GCfg<256, 256, 64, 2, 8>;
@@ -1123,7 +1133,6 @@ gemm_pp2_kernel(const GemmArgs g) {
   const int frow = lane & 15, fq = lane >> 4;
   const int PQc = CONV ? g.P * g.Q : 1;
   constexpr bool strided = CONV && (EPI & 4);
-  const int cb = CONV ? g.Cc / BK : 1;
 
   auto prow = [&](int pc, int j) {
     const int r0 = pc == 0 ? j * 128 + 8 * wave
@@ -1159,10 +1168,16 @@ gemm_pp2_kernel(const GemmArgs g) {
     n0 = (bid % tiles_n) * BN;
     return true;
   };
-  // per-tile piece operands: dense -> byte offset (2^31 = out of range); CONV A pieces -> ONE
-  // packed int per piece: image n (bits 20+), top-left h (bits 10-19), w (bits 0-9) of the
-  // receptive field (invalid rows: h = 1023, beyond every image; host: N < 2048, H, W < 1000)
-  auto tile_offsets = [&](bool valid, int m0, int n0, uint32_t (&o)[4][2], int (&pk)[2][2]) {
+  // per-tile piece operands: dense -> byte offset (2^31 = out of range); CONV A pieces -> per
+  // row the byte offset of its receptive field's top-left corner (tap offsets, which may be
+  // negative, are added to it mod 2^32) and, per piece, the two rows' validity bit fields (row
+  // j at bits 16 j: bit i set when image row h0 + dh0 + i exists, bit 8 + i when image column
+  // w0 + dw0 + i does; 0 for rows past M and for an invalid tile).  The K loop adds the step's
+  // scalar (tap offset + channel offset) and tests the tap's two bits (GemmArgs::tsel): no
+  // decode, no bounds test and no multiply per issue.
+  auto tile_offsets = [&](bool valid, int m0, int n0, uint32_t (&o)[4][2], uint32_t (&pb)[2][2],
+                          uint32_t (&pv)[2]) {
+    if constexpr (CONV) pv[0] = pv[1] = 0u;
 #pragma unroll
     for (int pc = 0; pc < 4; ++pc)
 #pragma unroll
@@ -1176,7 +1191,13 @@ gemm_pp2_kernel(const GemmArgs g) {
             const int mm = ok ? m : 0;
             const int q = mm % g.Q, t = mm / g.Q;
             const int p = t % g.P, n = t / g.P;
-            pk[pc == 3][j] = (n << 20) | ((ok ? p * g.sh : 1023) << 10) | (q * g.sw);
+            const int h0 = p * g.sh, w0 = q * g.sw;
+            pb[pc == 3][j] = (uint32_t)((((n * g.H + h0) * g.W + w0) * g.Cc + pch) * 2);
+            // i in [lo, hi) of 0 .. 8 are inside the image: bits (1 << hi) - (1 << lo)
+            const int hlo = min(max(-(h0 + g.dh0), 0), 8), hhi = min(max(g.H - (h0 + g.dh0), hlo), 8);
+            const int wlo = min(max(-(w0 + g.dw0), 0), 8), whi = min(max(g.W - (w0 + g.dw0), wlo), 8);
+            const uint32_t bits = ((1u << hhi) - (1u << hlo)) | ((1u << whi) - (1u << wlo)) << 8;
+            pv[pc == 3] |= (ok ? bits : 0u) << (16 * j);
             o[pc][j] = 0x80000000u;
           } else {
             o[pc][j] = ok ? (uint32_t)(m * g.lda + pch) * 2u : 0x80000000u;
@@ -1200,29 +1221,41 @@ gemm_pp2_kernel(const GemmArgs g) {
   if (!tile_mn(0, cm0, cn0)) return;
   bool nxt_valid = tile_mn(1, xm0, xn0);
   uint32_t ocur[4][2], onxt[4][2];
-  int pcur[2][2], pnxt[2][2];
-  tile_offsets(true, cm0, cn0, ocur, pcur);
-  tile_offsets(nxt_valid, xm0, xn0, onxt, pnxt);
+  uint32_t pbcur[2][2], pbnxt[2][2], pvcur[2], pvnxt[2];
+  tile_offsets(true, cm0, cn0, ocur, pbcur, pvcur);
+  tile_offsets(nxt_valid, xm0, xn0, onxt, pbnxt, pvnxt);
   int gstep0 = 0;
 
-  // piece pc of step kt of the current tile (kt >= nk: the next tile's step kt - nk)
-  auto issue_piece = [&](int kt, int pc) {
+  // CONV: where a K-step's A pieces read, as wave-uniform carried state -- the tap, the channel
+  // block's byte offset cs = c0 * 2, koff = tsel[tap][0] + cs and sel = tsel[tap][1].  One cursor
+  // per look-ahead distance (steps kt + 1 and kt + 2), stepped once per K-step by add / compare /
+  // select; the step after a tile's last is the next tile's step 0 (tap 0, cs 0).
+  struct TapCur { int tap, cs; uint32_t koff, sel; };
+  const int cc2 = CONV ? g.Cc * 2 : 0;
+  auto cur_step = [&](TapCur& c) {
+    if constexpr (TAP0) return;              // probe: every step reads tap 0, channel block 0
+    c.cs += BK * 2;
+    const bool wrap = c.cs == cc2;
+    c.cs = wrap ? 0 : c.cs;
+    c.tap += wrap ? 1 : 0;
+    c.tap = c.tap == g.ntaps ? 0 : c.tap;
+  };
+
+  // piece pc of step kt of the current tile (kt >= nk: the next tile's step kt - nk); ac: the
+  // step's cursor (CONV A pieces)
+  auto issue_piece = [&](int kt, int pc, const TapCur& ac) {
     const bool nx = kt >= nk;
     const int kk = nx ? kt - nk : kt;
     const uint32_t base = lds0 + (uint32_t)(((gstep0 + kt) & 1) * Cf::STAGE) * 2u;
     const bool isA = pc == 0 || pc == 3;
     if constexpr (CONV) {
       if (isA) {
-        const int tap = kk / cb, c0 = (kk % cb) * BK;
-        const int dh = g.tdh[tap], dw = g.tdw[tap];
-        const bool live = !nx || nxt_valid;
+        const uint32_t v = nx ? pvnxt[pc == 3] : pvcur[pc == 3];
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          const int v = nx ? pnxt[pc == 3][j] : pcur[pc == 3][j];
-          const int h = ((v >> 10) & 1023) + dh, w = (v & 1023) + dw;
-          const bool ok = live && (unsigned)h < (unsigned)g.H && (unsigned)w < (unsigned)g.W;
-          dma16(ra, base + plds(pc, j),
-                ok ? (uint32_t)((((v >> 20) * g.H + h) * g.W + w) * g.Cc + c0 + pch) * 2u : kGOOB);
+          const uint32_t b = nx ? pbnxt[pc == 3][j] : pbcur[pc == 3][j];
+          const uint32_t s = ac.sel << (16 * j);
+          dma16(ra, base + plds(pc, j), (v & s) == s ? b + ac.koff : kGOOB);
         }
         return;
       }
@@ -1303,8 +1336,20 @@ gemm_pp2_kernel(const GemmArgs g) {
   constexpr bool relu = (EPI & 32) != 0;
   static_assert(!relu || !(EPI & (1 | 4 | 8 | 16)), "ReLU: the plain / accumulate dense epilogues");
 
-  issue_piece(0, 0); issue_piece(0, 1); issue_piece(0, 2); issue_piece(0, 3);
-  issue_piece(1, 0); issue_piece(1, 1);
+  // c1 / c2: the cursors of steps kt + 1 / kt + 2 (nk >= 2: steps 0 and 1 are this tile's)
+  TapCur c1{0, 0, 0u, 0u}, c2{0, 0, 0u, 0u};
+  if constexpr (CONV) {
+    c1.koff = (uint32_t)g.tsel[0][0];
+    c1.sel = (uint32_t)g.tsel[0][1];
+    issue_piece(0, 0, c1); issue_piece(0, 1, c1); issue_piece(0, 2, c1); issue_piece(0, 3, c1);
+    cur_step(c1);
+    c1.koff = (uint32_t)(g.tsel[c1.tap][0] + c1.cs);
+    c1.sel = (uint32_t)g.tsel[c1.tap][1];
+    c2 = c1;
+  } else {
+    issue_piece(0, 0, c1); issue_piece(0, 1, c1); issue_piece(0, 2, c1); issue_piece(0, 3, c1);
+  }
+  issue_piece(1, 0, c1); issue_piece(1, 1, c1);
   DTF_WAIT_VM(8);
   bool first = true;
   for (;; ++seq) {
@@ -1312,23 +1357,38 @@ gemm_pp2_kernel(const GemmArgs g) {
     if (wm == 1) sync();                       // the one-barrier stagger
     for (int kt = 0; kt < nk; ++kt) {
       const bf16_t* cur_lds = lds + ((gstep0 + kt) & 1) * Cf::STAGE;
+      // step kt + 2's tap pair: the scalar load is issued here, two phases (each with its
+      // lgkmcnt(0)) before the cursor takes it at the top of the third load section, where no
+      // LDS read of that section has been issued yet
+      int toff2 = 0, tsel2 = 0;
+      if constexpr (CONV) {
+        cur_step(c2);
+        toff2 = g.tsel[c2.tap][0];
+        tsel2 = g.tsel[c2.tap][1];
+      }
       rdB(fBl, cur_lds, 0);
       __builtin_amdgcn_sched_barrier(0);
       rdA(cur_lds, 0);
-      issue_piece(kt + 1, 2);
+      issue_piece(kt + 1, 2, c1);
       if (!first && kt == 0) wait_after_stores(); else DTF_WAIT_VM(8);
       mfma_phase(fBl, 0, 0);
       rdB(fBr, cur_lds, 1);
-      issue_piece(kt + 1, 3);
+      issue_piece(kt + 1, 3, c1);
       if (!first && kt == 0) wait_after_stores(); else DTF_WAIT_VM(8);
       mfma_phase(fBr, 0, 1);
+      if constexpr (CONV) {
+        c2.koff = (uint32_t)(toff2 + c2.cs);
+        c2.sel = (uint32_t)tsel2;
+        __builtin_amdgcn_sched_barrier(0);
+      }
       rdA(cur_lds, 1);
-      issue_piece(kt + 2, 0);
+      issue_piece(kt + 2, 0, c2);
       DTF_WAIT_VM(8);
       mfma_phase(fBr, 1, 1);
-      issue_piece(kt + 2, 1);
+      issue_piece(kt + 2, 1, c2);
       DTF_WAIT_VM(8);
       mfma_phase(fBl, 1, 0);
+      c1 = c2;
     }
     if (wm == 0) sync();
 
@@ -1339,8 +1399,12 @@ gemm_pp2_kernel(const GemmArgs g) {
     uint32_t cbytes;
     if (strided) {
       const int n_hi = (cm0 + rows_a - 1) / PQc;
-      cbase = (long)n_lo * g.Ho * g.Wo * g.ldc;
-      cbytes = (uint32_t)((long)(n_hi - n_lo + 1) * g.Ho * g.Wo * g.ldc * 2);
+      // opaque: as closed forms the image-size products are hoisted above the tile loop and
+      // held (64-bit, spilled) across every K loop; here they cost three s_mul per tile
+      int ho = g.Ho;
+      asm volatile("" : "+s"(ho));
+      cbase = (long)n_lo * ho * g.Wo * g.ldc;
+      cbytes = (uint32_t)((long)(n_hi - n_lo + 1) * ho * g.Wo * g.ldc * 2);
     } else {
       cbase = (long)cm0 * g.ldc;
       cbytes = (uint32_t)(((long)(rows_a - 1) * g.ldc + g.N) * 2);
@@ -1396,23 +1460,24 @@ gemm_pp2_kernel(const GemmArgs g) {
       auto rows4 = [&](int i) -> i32x4_t {        // strided: fragment row i's 4 row offsets
         return *reinterpret_cast<const i32x4_t*>(rtab + 16 * i + 4 * fq);
       };
-      // accumulate operands (the unused one points at C with zero size)
+      // accumulate operands (the unused one points at C with zero size); the strided rows
+      // accumulate from Cin only (launcher), so their kernels carry no mask operands
+      const bool masked = has_acc && !strided && !g.Cin;
       const __amdgpu_buffer_rsrc_t rcin = __builtin_amdgcn_make_buffer_rsrc(
-          has_acc ? const_cast<bf16_t*>(g.Cin ? g.Cin + cbase : g.acc_src + cbase) : g.C, 0,
+          has_acc ? const_cast<bf16_t*>(masked ? g.acc_src + cbase : g.Cin + cbase) : g.C, 0,
           has_acc ? (int)cbytes : 0, 0x00020000);
       const __amdgpu_buffer_rsrc_t rmask = __builtin_amdgcn_make_buffer_rsrc(
-          (has_acc && !g.Cin) ? const_cast<uint8_t*>(g.acc_mask + (cbase >> 3)) : (uint8_t*)g.C,
+          masked ? const_cast<uint8_t*>(g.acc_mask + (cbase >> 3)) : (uint8_t*)g.C,
           // exactly the mask bytes of the valid region (cbytes / 2 elements, 8 per byte): a
           // row past M must fall outside it (a +1 here let row M's first lanes read one byte past
           // the mask allocation -- a device fault when that byte was unmapped)
-          0, (has_acc && !g.Cin) ? (int)(cbytes / 16) : 0, 0x00020000);
+          0, masked ? (int)(cbytes / 16) : 0, 0x00020000);
       // the accumulate / GELU operands of fragment row i + 1 are loaded while row i is formed
       // (one fragment row = 4 output rows per lane): their latency hides under the conversions
       // and stores instead of stalling every row
       constexpr bool has_ld = has_acc || gelu_bwd;
       typedef uint32_t u32x2l_t __attribute__((ext_vector_type(2)));
       const __amdgpu_buffer_rsrc_t rld = gelu_bwd ? rg : rcin;
-      const bool masked = has_acc && !g.Cin;
       const int mshift = ncol & 7;                     // ldc % 8 == 0: the same for every row
       u32x2l_t pa[4], pn[4];
       uint32_t pm[4], pmn[4];
@@ -1652,18 +1717,20 @@ gemm_pp2_kernel(const GemmArgs g) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) ocur[pc][j] = onxt[pc][j];
 #pragma unroll
-    for (int a = 0; a < 2; ++a)
+    for (int a = 0; a < 2; ++a) {
+      pvcur[a] = pvnxt[a];
 #pragma unroll
-      for (int j = 0; j < 2; ++j) pcur[a][j] = pnxt[a][j];
+      for (int j = 0; j < 2; ++j) pbcur[a][j] = pbnxt[a][j];
+    }
     nxt_valid = tile_mn(seq + 2, xm0, xn0);
-    tile_offsets(nxt_valid, xm0, xn0, onxt, pnxt);
+    tile_offsets(nxt_valid, xm0, xn0, onxt, pbnxt, pvnxt);
     first = false;
     static_assert(NSTORE == 32, "the counted waits assume 32 stores per lane per tile");
   }
   DTF_WAIT_VM(0);       // the trailing look-ahead DMAs still target the ring
 }
 
-template <int CONV, int EPI>
+template <int CONV, int EPI, bool TAP0 = false>
 void launch_gemm_pp2_t(const GemmArgs& g0, long a_bytes, long b_bytes, hipStream_t st) {
   using Cf = GCfg<256, 256, 64, 2, 8>;
   // + the strided epilogue's per-wave row tables (8 waves x 128 ints)
@@ -1672,10 +1739,10 @@ void launch_gemm_pp2_t(const GemmArgs& g0, long a_bytes, long b_bytes, hipStream
   static bool attr = false;
   static int ncu = 0;
   if (!attr) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)gemm_pp2_kernel<CONV, EPI>,
+    HIP_CHECK(hipFuncSetAttribute((const void*)gemm_pp2_kernel<CONV, EPI, TAP0>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
     hipFuncAttributes fa{};
-    HIP_CHECK(hipFuncGetAttributes(&fa, (const void*)gemm_pp2_kernel<CONV, EPI>));
+    HIP_CHECK(hipFuncGetAttributes(&fa, (const void*)gemm_pp2_kernel<CONV, EPI, TAP0>));
     if (fa.localSizeBytes > 0)
       throw std::runtime_error("gemm_pp2_kernel was compiled with register spills (scratch " +
                                std::to_string(fa.localSizeBytes) + " B/lane)");
@@ -1693,8 +1760,21 @@ void launch_gemm_pp2_t(const GemmArgs& g0, long a_bytes, long b_bytes, hipStream
   const long tiles = (long)((g.M + 255) / 256) * ((g.N + 255) / 256);
   long grid = tiles < ncu ? tiles : (ncu / 8) * 8;
   if (grid < 1) grid = 1;
-  hipLaunchKernelGGL((gemm_pp2_kernel<CONV, EPI>), dim3((unsigned)grid), dim3(Cf::NT), LDS,
+  hipLaunchKernelGGL((gemm_pp2_kernel<CONV, EPI, TAP0>), dim3((unsigned)grid), dim3(Cf::NT), LDS,
                      st, g);
+}
+
+// one epilogue's instantiation; in a probe build GemmArgs::dbg bit 1 selects the CONV kernels'
+// tap-0 timing probe (wrong results)
+template <int CONV, int EPI>
+void launch_gemm_pp2_e(const GemmArgs& g, long a_bytes, long b_bytes, hipStream_t st) {
+#ifdef DTF_PROBES
+  if (CONV && (g.dbg & 2)) {
+    launch_gemm_pp2_t<CONV, EPI, CONV != 0>(g, a_bytes, b_bytes, st);
+    return;
+  }
+#endif
+  launch_gemm_pp2_t<CONV, EPI>(g, a_bytes, b_bytes, st);
 }
 
 template <int CONV>
@@ -1703,6 +1783,8 @@ void launch_gemm_pp2(const GemmArgs& g, long a_bytes, long b_bytes, hipStream_t 
   const bool strided = CONV && (g.osh != 1 || g.osw != 1);
   if (g.relu && (CONV || stats || strided || g.gelu_out || g.gelu_a))
     throw std::runtime_error("gemm_pp2: ReLU only on the plain / accumulate dense epilogues");
+  if (strided && acc && !g.Cin)
+    throw std::runtime_error("gemm_pp2: strided output rows accumulate from Cin only");
   if constexpr (!CONV) {
     if (g.gelu_out) { launch_gemm_pp2_t<0, 8>(g, a_bytes, b_bytes, st); return; }
     if (g.gelu_a) { launch_gemm_pp2_t<0, 16>(g, a_bytes, b_bytes, st); return; }
@@ -1713,14 +1795,14 @@ void launch_gemm_pp2(const GemmArgs& g, long a_bytes, long b_bytes, hipStream_t 
     }
   }
   if (strided) {
-    if (acc) launch_gemm_pp2_t<CONV, 6>(g, a_bytes, b_bytes, st);
-    else launch_gemm_pp2_t<CONV, 4>(g, a_bytes, b_bytes, st);
+    if (acc) launch_gemm_pp2_e<CONV, 6>(g, a_bytes, b_bytes, st);
+    else launch_gemm_pp2_e<CONV, 4>(g, a_bytes, b_bytes, st);
   } else if (stats) {
-    launch_gemm_pp2_t<CONV, 1>(g, a_bytes, b_bytes, st);
+    launch_gemm_pp2_e<CONV, 1>(g, a_bytes, b_bytes, st);
   } else if (acc) {
-    launch_gemm_pp2_t<CONV, 2>(g, a_bytes, b_bytes, st);
+    launch_gemm_pp2_e<CONV, 2>(g, a_bytes, b_bytes, st);
   } else {
-    launch_gemm_pp2_t<CONV, 0>(g, a_bytes, b_bytes, st);
+    launch_gemm_pp2_e<CONV, 0>(g, a_bytes, b_bytes, st);
   }
 }
 
@@ -1848,9 +1930,18 @@ void dtf_gemm_conv(const bf16_t* X, const bf16_t* Wt, bf16_t* Y, int N, int H, i
   g.acc_mask = acc_mask;
   g.M = (int)M; g.N = Kout; g.K = ntaps * C; g.lda = C; g.ldb = ntaps * C; g.ldc = Kout;
   g.H = H; g.W = W; g.Cc = C; g.P = P; g.Q = Q; g.sh = sh; g.sw = sw; g.ntaps = ntaps;
-  for (int t = 0; t < ntaps; ++t) { g.tdh[t] = dh[t]; g.tdw[t] = dw[t]; }
+  g.dh0 = *std::min_element(dh, dh + ntaps);
+  g.dw0 = *std::min_element(dw, dw + ntaps);
+  bool tap_span = true;              // the persistent kernel: 8 validity bits each way per row
+  for (int t = 0; t < ntaps; ++t) {
+    g.tdh[t] = dh[t]; g.tdw[t] = dw[t];
+    tap_span = tap_span && dh[t] - g.dh0 < 8 && dw[t] - g.dw0 < 8;
+    g.tsel[t][0] = (int)(((long)dh[t] * W + dw[t]) * C * 2);   // added mod 2^32 in the kernel
+    g.tsel[t][1] = tap_span ? 1 << (dh[t] - g.dh0) | 1 << (8 + dw[t] - g.dw0) : 0;
+  }
   g.Ho = Ho; g.Wo = Wo; g.osh = osh; g.osw = osw; g.oh0 = oh0; g.ow0 = ow0;
   g.nt = g_gemm_nt;
+  g.dbg = g_gemm_dbg & 2;          // probe builds: the persistent kernel's tap-0 probe
   if ((osh != 1 || osw != 1) && (stats || acc_mask))
     throw std::runtime_error("gemm_conv: strided outputs take no BN statistics / masked acc");
   if ((long)256 * g.ldb * 2 + 2L * g.K >= (1L << 31))
@@ -1881,7 +1972,7 @@ void dtf_gemm_conv(const bf16_t* X, const bf16_t* Wt, bf16_t* Y, int N, int H, i
   // (profiles/measurements/r5_conv_pp2_per_layer_b1984.jsonl)
   else if ((g_gemm_pp2 & 2) && (g_gemm_pp2_strided || (osh == 1 && osw == 1)) && g.K >= 128 &&
            x_bytes < 0x7FFFFF00L && w_bytes < 0x7FFFFF00L && N < 2048 && H < 1000 && W < 1000 &&
-           pp_span)
+           pp_span && tap_span)
     launch_gemm_pp2<1>(g, x_bytes, w_bytes, st);
   else if ((g_gemm_pp & 2) && (g.K + 63) / 64 >= 2 && pp_span) launch_gemm_pp<1>(g, st);
   else launch_gemm<256, 256, 64, 2, 2, 8, 1, 1>(g, st);
