@@ -448,45 +448,91 @@ PYBIND11_MODULE(_dtf_hip, m) {
                             P<float>(loss_rows), P<float>(grad), gscale, smoothing, S(st));
     check_launch("softmax_xent_smooth");
   });
+  // the update kernels: ``gmul`` (trailing keyword, 0 = none) is the device address of the clip
+  // multiplier a grad_norm pass wrote; when set it replaces ``gscale``
   m.def("sgd_momentum", [](uintptr_t p, uintptr_t g, uintptr_t a, uintptr_t shadow, long n,
                            uintptr_t lr, float mom, float wd, float gscale, int nesterov,
-                           uintptr_t nonfinite, uintptr_t st) {
+                           uintptr_t nonfinite, uintptr_t st, uintptr_t gmul) {
     dtf_sgd_momentum(P<float>(p), P<const float>(g), P<float>(a), P<bf16_t>(shadow), n,
-                     P<const float>(lr), mom, wd, gscale, nesterov, P<int>(nonfinite), S(st));
+                     P<const float>(lr), mom, wd, gscale, nesterov, P<int>(nonfinite),
+                     P<const float>(gmul), S(st));
     check_launch("sgd_momentum");
-  });
+  }, py::arg("p"), py::arg("g"), py::arg("a"), py::arg("shadow"), py::arg("n"), py::arg("lr"),
+     py::arg("momentum"), py::arg("wd"), py::arg("gscale"), py::arg("nesterov"),
+     py::arg("nonfinite"), py::arg("stream"), py::arg("gmul") = (uintptr_t)0);
   m.def("adam", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t shadow, long n,
                    uintptr_t lr_t, float b1, float b2, float eps, float wd, float gscale,
-                   uintptr_t nonfinite, uintptr_t st) {
+                   uintptr_t nonfinite, uintptr_t st, uintptr_t gmul) {
     dtf_adam(P<float>(p), P<const float>(g), P<float>(mm), P<float>(v), P<bf16_t>(shadow), n,
-             P<const float>(lr_t), b1, b2, eps, wd, gscale, P<int>(nonfinite), S(st));
+             P<const float>(lr_t), b1, b2, eps, wd, gscale, P<int>(nonfinite),
+             P<const float>(gmul), S(st));
     check_launch("adam");
-  });
+  }, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("n"),
+     py::arg("lr_t"), py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("wd"),
+     py::arg("gscale"), py::arg("nonfinite"), py::arg("stream"), py::arg("gmul") = (uintptr_t)0);
   m.def("adagrad", [](uintptr_t p, uintptr_t g, uintptr_t acc, uintptr_t shadow, long n,
-                      uintptr_t lr, float gscale, uintptr_t nonfinite, uintptr_t st) {
+                      uintptr_t lr, float gscale, uintptr_t nonfinite, uintptr_t st,
+                      uintptr_t gmul) {
     dtf_adagrad(P<float>(p), P<const float>(g), P<float>(acc), P<bf16_t>(shadow), n,
-                P<const float>(lr), gscale, P<int>(nonfinite), S(st));
+                P<const float>(lr), gscale, P<int>(nonfinite), P<const float>(gmul), S(st));
     check_launch("adagrad");
-  });
+  }, py::arg("p"), py::arg("g"), py::arg("acc"), py::arg("shadow"), py::arg("n"), py::arg("lr"),
+     py::arg("gscale"), py::arg("nonfinite"), py::arg("stream"), py::arg("gmul") = (uintptr_t)0);
   m.def("lamb", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t shadow,
                    uintptr_t chunks, int nchunks, uintptr_t hyper, uintptr_t lr, float b1,
                    float b2, float eps, uintptr_t wd_seg, float gscale, uintptr_t norms,
-                   uintptr_t partial, uintptr_t nonfinite, uintptr_t st) {
+                   uintptr_t partial, uintptr_t nonfinite, uintptr_t st, uintptr_t gmul) {
     dtf_lamb(P<float>(p), P<float>(g), P<float>(mm), P<float>(v), P<bf16_t>(shadow),
              P<const void>(chunks), nchunks, P<const float>(hyper), P<const float>(lr), b1, b2,
              eps, P<const float>(wd_seg), gscale, P<float>(norms), P<float>(partial),
-             P<int>(nonfinite), S(st));
+             P<int>(nonfinite), P<const float>(gmul), S(st));
     check_launch("lamb");
-  });
+  }, py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"), py::arg("shadow"),
+     py::arg("chunks"), py::arg("nchunks"), py::arg("hyper"), py::arg("lr"), py::arg("b1"),
+     py::arg("b2"), py::arg("eps"), py::arg("wd_seg"), py::arg("gscale"), py::arg("norms"),
+     py::arg("partial"), py::arg("nonfinite"), py::arg("stream"),
+     py::arg("gmul") = (uintptr_t)0);
   m.def("lamb_chunk_bytes", &dtf_lamb_chunk_bytes);
   m.def("lars", [](uintptr_t p, uintptr_t g, uintptr_t a, uintptr_t shadow, uintptr_t chunks,
                    int nchunks, uintptr_t segs, uintptr_t lr, float mom, float wd, float eeta,
                    float eps, float gscale, int nesterov, uintptr_t partial, uintptr_t nonfinite,
-                   uintptr_t st) {
+                   uintptr_t st, uintptr_t gmul) {
     dtf_lars(P<float>(p), P<const float>(g), P<float>(a), P<bf16_t>(shadow),
              P<const void>(chunks), nchunks, P<const void>(segs), P<const float>(lr), mom, wd,
-             eeta, eps, gscale, nesterov, P<float>(partial), P<int>(nonfinite), S(st));
+             eeta, eps, gscale, nesterov, P<float>(partial), P<int>(nonfinite),
+             P<const float>(gmul), S(st));
     check_launch("lars");
+  }, py::arg("p"), py::arg("g"), py::arg("a"), py::arg("shadow"), py::arg("chunks"),
+     py::arg("nchunks"), py::arg("segs"), py::arg("lr"), py::arg("momentum"), py::arg("wd"),
+     py::arg("eeta"), py::arg("eps"), py::arg("gscale"), py::arg("nesterov"),
+     py::arg("partial"), py::arg("nonfinite"), py::arg("stream"),
+     py::arg("gmul") = (uintptr_t)0);
+  // deterministic global gradient norm: ``partial`` holds one fp64 per grad_norm_chunk()
+  // elements of g, ``rec`` is the 16-byte record {S: f64, norm: f32, gmul: f32}
+  m.def("grad_norm_chunk", &dtf_grad_norm_chunk);
+  m.def("grad_norm_record_bytes", []() { return (int)sizeof(GradNormRecord); });
+  m.def("grad_norm", [](uintptr_t g, long n, uintptr_t partial, int max_blocks, uintptr_t extra,
+                        int nextra, float gscale, float clip, uintptr_t rec, uintptr_t st) {
+    if (n < 0 || nextra < 0 || !partial || !rec || (nextra > 0 && !extra))
+      throw std::invalid_argument("grad_norm: bad arguments");
+    dtf_grad_norm(P<const float>(g), n, P<double>(partial), max_blocks, P<const double>(extra),
+                  nextra, gscale, clip, P<GradNormRecord>(rec), S(st));
+    check_launch("grad_norm");
+  }, py::arg("g"), py::arg("n"), py::arg("partial"), py::arg("max_blocks"), py::arg("extra"),
+     py::arg("nextra"), py::arg("gscale"), py::arg("clip"), py::arg("rec"), py::arg("stream"));
+  m.def("grad_norm_partial", [](uintptr_t g, long n, uintptr_t partial, int max_blocks,
+                                uintptr_t st) {
+    if (n < 0 || !partial) throw std::invalid_argument("grad_norm_partial: bad arguments");
+    dtf_grad_norm_partial(P<const float>(g), n, P<double>(partial), max_blocks, S(st));
+    check_launch("grad_norm_partial");
+  });
+  m.def("grad_norm_finish", [](uintptr_t partial, long nchunks, uintptr_t extra, int nextra,
+                               float gscale, float clip, uintptr_t rec, uintptr_t st) {
+    if (nchunks < 0 || nextra < 0 || !rec || (nchunks > 0 && !partial) || (nextra > 0 && !extra))
+      throw std::invalid_argument("grad_norm_finish: bad arguments");
+    dtf_grad_norm_finish(P<const double>(partial), nchunks, P<const double>(extra), nextra,
+                         gscale, clip, P<GradNormRecord>(rec), S(st));
+    check_launch("grad_norm_finish");
   });
   m.def("sumsq", [](uintptr_t x, long n, uintptr_t out, uintptr_t st) {
     dtf_sumsq(P<const float>(x), n, P<float>(out), S(st));

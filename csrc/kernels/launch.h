@@ -317,22 +317,34 @@ void dtf_metrics_accumulate(const float* loss_rows, const int* rank, const float
 // ---- optim.hip
 void dtf_sgd_momentum(float* p, const float* g, float* a, bf16_t* shadow, long n,
                       const float* lr_ptr, float momentum, float wd, float gscale, int nesterov,
-                      int* nonfinite, hipStream_t st);
+                      int* nonfinite, const float* gmul, hipStream_t st);
 void dtf_adam(float* p, const float* g, float* m, float* v, bf16_t* shadow, long n,
               const float* lr_t_ptr, float b1, float b2, float eps, float wd, float gscale,
-              int* nonfinite, hipStream_t st);
+              int* nonfinite, const float* gmul, hipStream_t st);
 void dtf_adagrad(float* p, const float* g, float* acc, bf16_t* shadow, long n, const float* lr_ptr,
-                 float gscale, int* nonfinite, hipStream_t st);
+                 float gscale, int* nonfinite, const float* gmul, hipStream_t st);
 void dtf_lamb(float* p, float* g, float* m, float* v, bf16_t* shadow, const void* chunks,
               int nchunks, const float* hyper, const float* lr_ptr, float b1, float b2, float eps,
               const float* wd_seg, float gscale, float* norms, float* partial, int* nonfinite,
-              hipStream_t st);
+              const float* gmul, hipStream_t st);
 int dtf_lamb_chunk_bytes();
 void dtf_lars(float* p, const float* g, float* a, bf16_t* shadow, const void* chunks, int nchunks,
               const void* segs, const float* lr_ptr, float momentum, float wd, float eeta,
               float eps, float gscale, int nesterov, float* partial, int* nonfinite,
-              hipStream_t st);
+              const float* gmul, hipStream_t st);
 void dtf_sumsq(const float* x, long n, float* out, hipStream_t st);
+// Deterministic global gradient norm.  The partial pass stores one fp64 sum of squares per
+// dtf_grad_norm_chunk()-element chunk of g into partial[]; the finish pass adds partial[0..nchunks)
+// and extra[0..nextra) (other ranks' sums; may be null) in a fixed order and writes
+// GradNormRecord{S, norm = gscale sqrt(S), gmul = gscale clip / max(norm, clip)}.  gmul (when
+// non-null above) replaces gscale in the update kernels.  max_blocks: grid cap, 0 = default.
+struct GradNormRecord { double S; float norm; float gmul; };
+int dtf_grad_norm_chunk();
+void dtf_grad_norm_partial(const float* g, long n, double* partial, int max_blocks, hipStream_t st);
+void dtf_grad_norm_finish(const double* partial, long nchunks, const double* extra, int nextra,
+                          float gscale, float clip, GradNormRecord* rec, hipStream_t st);
+void dtf_grad_norm(const float* g, long n, double* partial, int max_blocks, const double* extra,
+                   int nextra, float gscale, float clip, GradNormRecord* rec, hipStream_t st);
 void dtf_cast_f32_bf16(const float* x, bf16_t* y, long n, hipStream_t st);
 
 // ---- nlp.hip

@@ -20,6 +20,9 @@
 // separate cast of the fp32 master every step) and flags non-finite gradients.
 // Hyper-parameters that change per step (lr, lr_t) are read from DEVICE memory so a captured
 // hipGraph replays correctly.
+// Global-norm clip (tf.clip_by_global_norm, then the optimizer): every update kernel multiplies g
+// by `gscale`, or -- when `gmul` is non-null -- by the multiplier the grad_norm pass below left on
+// the device, in the same single fp32 multiply.
 #include "launch.h"
 
 namespace {
@@ -32,8 +35,10 @@ DTF_DEV void flag_nonfinite(int* flag, float g) {
 __global__ void __launch_bounds__(kT)
 sgd_momentum_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ a,
                     bf16_t* __restrict__ shadow, long n, const float* __restrict__ lr_ptr,
-                    float momentum, float wd, float gscale, int nesterov, int* nonfinite) {
+                    float momentum, float wd, float gscale_v, const float* __restrict__ gmul,
+                    int nesterov, int* nonfinite) {
   const float lr = *lr_ptr;
+  const float gscale = gmul ? *gmul : gscale_v;
   const long n4 = n >> 2;
   for (long i = (long)blockIdx.x * kT + threadIdx.x; i < n4; i += (long)gridDim.x * kT) {
     float4 pv = reinterpret_cast<float4*>(p)[i];
@@ -72,8 +77,9 @@ __global__ void __launch_bounds__(kT)
 adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
             float* __restrict__ v, bf16_t* __restrict__ shadow, long n,
             const float* __restrict__ lr_t_ptr, float b1, float b2, float eps, float wd,
-            float gscale, int* nonfinite) {
+            float gscale_v, const float* __restrict__ gmul, int* nonfinite) {
   const float lr_t = *lr_t_ptr;
+  const float gscale = gmul ? *gmul : gscale_v;
   for (long i = (long)blockIdx.x * kT + threadIdx.x; i < n; i += (long)gridDim.x * kT) {
     const float gr0 = g[i];
     flag_nonfinite(nonfinite, gr0);
@@ -92,8 +98,9 @@ adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restric
 __global__ void __launch_bounds__(kT)
 adagrad_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ acc,
                bf16_t* __restrict__ shadow, long n, const float* __restrict__ lr_ptr,
-               float gscale, int* nonfinite) {
+               float gscale_v, const float* __restrict__ gmul, int* nonfinite) {
   const float lr = *lr_ptr;
+  const float gscale = gmul ? *gmul : gscale_v;
   for (long i = (long)blockIdx.x * kT + threadIdx.x; i < n; i += (long)gridDim.x * kT) {
     const float gr0 = g[i];
     flag_nonfinite(nonfinite, gr0);
@@ -117,10 +124,11 @@ __global__ void __launch_bounds__(kT)
 lamb_phase1_kernel(const float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                    float* __restrict__ v, const Chunk* __restrict__ chunks,
                    const float* __restrict__ hyper, float b1, float b2, float eps,
-                   const float* __restrict__ wd_seg, float gscale,
-                   float2* __restrict__ partial, int* nonfinite) {
+                   const float* __restrict__ wd_seg, float gscale_v,
+                   const float* __restrict__ gmul, float2* __restrict__ partial, int* nonfinite) {
   // hyper[0] = 1/(1-b1^t), hyper[1] = 1/(1-b2^t)
   __shared__ float red[2][kT / 64];
+  const float gscale = gmul ? *gmul : gscale_v;
   const Chunk c = chunks[blockIdx.x];
   const float bc1 = hyper[0], bc2 = hyper[1];
   const float wd = wd_seg[c.seg];
@@ -202,9 +210,10 @@ lamb_phase2_kernel(float* __restrict__ p, const float* __restrict__ u,
 // segs[seg] = {first_row, row_count, decayed, 0}: the tensor's rows in THIS chunk table.
 __global__ void __launch_bounds__(kT)
 lars_norm_kernel(const float* __restrict__ p, const float* __restrict__ g,
-                 const Chunk* __restrict__ chunks, const int4* __restrict__ segs, float gscale,
-                 float2* __restrict__ partial, int* nonfinite) {
+                 const Chunk* __restrict__ chunks, const int4* __restrict__ segs, float gscale_v,
+                 const float* __restrict__ gmul, float2* __restrict__ partial, int* nonfinite) {
   __shared__ float red[2][kT / 64];
+  const float gscale = gmul ? *gmul : gscale_v;
   const Chunk c = chunks[blockIdx.x];
   if (!segs[c.seg].z) return;   // no trust ratio: the update pass flags this tensor's gradients
   const float* pw = p + c.start;
@@ -247,8 +256,10 @@ lars_update_kernel(float* __restrict__ p, const float* __restrict__ g, float* __
                    bf16_t* __restrict__ shadow, const Chunk* __restrict__ chunks,
                    const int4* __restrict__ segs, const float* __restrict__ lr_ptr,
                    const float2* __restrict__ partial, float momentum, float wd, float eeta,
-                   float eps, float gscale, int nesterov, int* nonfinite) {
+                   float eps, float gscale_v, const float* __restrict__ gmul, int nesterov,
+                   int* nonfinite) {
   __shared__ float red[2][kT / 64];
+  const float gscale = gmul ? *gmul : gscale_v;
   const Chunk c = chunks[blockIdx.x];
   const int4 seg = segs[c.seg];
   const bool decayed = seg.z != 0;
@@ -332,6 +343,89 @@ sumsq_kernel(const float* __restrict__ x, long n, float* __restrict__ out) {
   }
 }
 
+// ---- Deterministic global gradient norm (clip_by_global_norm inside the fused update).
+// Partial pass: the buffer is cut into chunks of kNormChunk elements counted from g; chunk k is
+// summed by exactly one block in an order that depends on nothing but the chunk's length, and its
+// fp32 sum goes to partial[k] as fp64 with a plain store.  A block walks chunks b, b + G, ...:
+// the grid size G decides who adds a chunk, never how.  Finish pass: one block adds the partials
+// (and the caller's extra sums) in fp64 in a fixed order and forms the clip multiplier.  No
+// atomics, no host read: bit-identical run to run.
+//
+// Longest chain of fp32 additions a square passes through inside a block, d = 20: 8 into its
+// thread's per-component accumulator (kNormChunk / 4 / kT float4 per thread), 2 to combine the
+// four accumulators, 1 for the scalar tail, 6 butterfly levels of wave_sum, 3 across the waves.
+constexpr int kNormChunk = 8192;
+constexpr int kNormBlocks = 2048;
+static_assert(kNormChunk % (4 * kT) == 0, "a whole number of float4 per thread");
+
+template <bool kAligned>
+__global__ void __launch_bounds__(kT)
+grad_norm_partial_kernel(const float* __restrict__ g, long n, long nchunks,
+                         double* __restrict__ partial) {
+  __shared__ float red[kT / 64];
+  for (long k = blockIdx.x; k < nchunks; k += gridDim.x) {
+    const float* gc = g + k * kNormChunk;
+    const long left = n - k * kNormChunk;
+    const int len = left < kNormChunk ? (int)left : kNormChunk;
+    const int n4 = len >> 2;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+#pragma unroll
+    for (int u = 0; u < kNormChunk / 4 / kT; ++u) {
+      const int j = u * kT + threadIdx.x;
+      if (j < n4) {
+        float4 v;
+        if (kAligned) v = reinterpret_cast<const float4*>(gc)[j];
+        else v = make_float4(gc[4 * j], gc[4 * j + 1], gc[4 * j + 2], gc[4 * j + 3]);
+        s0 += v.x * v.x;
+        s1 += v.y * v.y;
+        s2 += v.z * v.z;
+        s3 += v.w * v.w;
+      }
+    }
+    float s = (s0 + s1) + (s2 + s3);
+    // scalar tail: n % 4 != 0 or a short last chunk
+    const int jt = n4 * 4 + threadIdx.x;
+    if (jt < len) s += gc[jt] * gc[jt];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float t = red[0];
+      for (int w = 1; w < kT / 64; ++w) t += red[w];
+      partial[k] = (double)t;
+    }
+    __syncthreads();   // red is rewritten on the next trip
+  }
+}
+
+__global__ void __launch_bounds__(kT)
+grad_norm_finish_kernel(const double* __restrict__ partial, long nchunks,
+                        const double* __restrict__ extra, int nextra, float gscale, float clip,
+                        GradNormRecord* __restrict__ rec) {
+  __shared__ double red[kT];
+  // thread t adds partials t, t + kT, ... in that order, then a fixed tree over the threads
+  double s = 0.0;
+  for (long k = threadIdx.x; k < nchunks; k += kT) s += partial[k];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = kT / 2; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double S = red[0];
+    for (int r = 0; r < nextra; ++r) S += extra[r];   // rank order
+    const double gs = gscale, c = clip;
+    const double norm = gs * sqrt(S);
+    // not clipped (and S == 0): gs * c / c == gs exactly -- gs * c is exact in fp64
+    double gm = gs * c / (norm > c ? norm : c);
+    if (!isfinite(S)) gm = __builtin_nan("");
+    rec->S = S;
+    rec->norm = (float)norm;
+    rec->gmul = (float)gm;
+  }
+}
+
 __global__ void __launch_bounds__(kT)
 cast_f32_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, long n) {
   for (long i = (long)blockIdx.x * kT + threadIdx.x; i < n; i += (long)gridDim.x * kT)
@@ -347,31 +441,32 @@ inline int grid_for(long n, int per_thread = 1) {
 
 void dtf_sgd_momentum(float* p, const float* g, float* a, bf16_t* shadow, long n,
                       const float* lr_ptr, float momentum, float wd, float gscale, int nesterov,
-                      int* nonfinite, hipStream_t st) {
+                      int* nonfinite, const float* gmul, hipStream_t st) {
   hipLaunchKernelGGL(sgd_momentum_kernel, dim3(grid_for(n, 4)), dim3(kT), 0, st, p, g, a, shadow, n,
-                     lr_ptr, momentum, wd, gscale, nesterov, nonfinite);
+                     lr_ptr, momentum, wd, gscale, gmul, nesterov, nonfinite);
 }
 
 void dtf_adam(float* p, const float* g, float* m, float* v, bf16_t* shadow, long n,
               const float* lr_t_ptr, float b1, float b2, float eps, float wd, float gscale,
-              int* nonfinite, hipStream_t st) {
+              int* nonfinite, const float* gmul, hipStream_t st) {
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(kT), 0, st, p, g, m, v, shadow, n,
-                     lr_t_ptr, b1, b2, eps, wd, gscale, nonfinite);
+                     lr_t_ptr, b1, b2, eps, wd, gscale, gmul, nonfinite);
 }
 
 void dtf_adagrad(float* p, const float* g, float* acc, bf16_t* shadow, long n,
-                 const float* lr_ptr, float gscale, int* nonfinite, hipStream_t st) {
+                 const float* lr_ptr, float gscale, int* nonfinite, const float* gmul,
+                 hipStream_t st) {
   hipLaunchKernelGGL(adagrad_kernel, dim3(grid_for(n)), dim3(kT), 0, st, p, g, acc, shadow, n,
-                     lr_ptr, gscale, nonfinite);
+                     lr_ptr, gscale, gmul, nonfinite);
 }
 
 void dtf_lamb(float* p, float* g, float* m, float* v, bf16_t* shadow, const void* chunks,
               int nchunks, const float* hyper, const float* lr_ptr, float b1, float b2,
               float eps, const float* wd_seg, float gscale, float* norms, float* partial,
-              int* nonfinite, hipStream_t st) {
+              int* nonfinite, const float* gmul, hipStream_t st) {
   hipLaunchKernelGGL(lamb_phase1_kernel, dim3(nchunks), dim3(kT), 0, st, p, g, m, v,
-                     (const Chunk*)chunks, hyper, b1, b2, eps, wd_seg, gscale, (float2*)partial,
-                     nonfinite);
+                     (const Chunk*)chunks, hyper, b1, b2, eps, wd_seg, gscale, gmul,
+                     (float2*)partial, nonfinite);
   hipLaunchKernelGGL(lamb_norm_kernel, dim3(nchunks), dim3(kT), 0, st, (const Chunk*)chunks,
                      nchunks, (const float2*)partial, norms);
   hipLaunchKernelGGL(lamb_phase2_kernel, dim3(nchunks), dim3(kT), 0, st, p, g, shadow,
@@ -385,16 +480,46 @@ int dtf_lamb_chunk_bytes() { return (int)sizeof(Chunk); }
 void dtf_lars(float* p, const float* g, float* a, bf16_t* shadow, const void* chunks, int nchunks,
               const void* segs, const float* lr_ptr, float momentum, float wd, float eeta,
               float eps, float gscale, int nesterov, float* partial, int* nonfinite,
-              hipStream_t st) {
+              const float* gmul, hipStream_t st) {
   hipLaunchKernelGGL(lars_norm_kernel, dim3(nchunks), dim3(kT), 0, st, p, g,
-                     (const Chunk*)chunks, (const int4*)segs, gscale, (float2*)partial, nonfinite);
+                     (const Chunk*)chunks, (const int4*)segs, gscale, gmul, (float2*)partial,
+                     nonfinite);
   hipLaunchKernelGGL(lars_update_kernel, dim3(nchunks), dim3(kT), 0, st, p, g, a, shadow,
                      (const Chunk*)chunks, (const int4*)segs, lr_ptr, (const float2*)partial,
-                     momentum, wd, eeta, eps, gscale, nesterov, nonfinite);
+                     momentum, wd, eeta, eps, gscale, gmul, nesterov, nonfinite);
 }
 
 void dtf_sumsq(const float* x, long n, float* out, hipStream_t st) {
   hipLaunchKernelGGL(sumsq_kernel, dim3(grid_for(n)), dim3(kT), 0, st, x, n, out);
+}
+
+int dtf_grad_norm_chunk() { return kNormChunk; }
+
+void dtf_grad_norm_partial(const float* g, long n, double* partial, int max_blocks,
+                           hipStream_t st) {
+  if (n <= 0) return;
+  const long nchunks = (n + kNormChunk - 1) / kNormChunk;
+  const long cap = max_blocks > 0 ? max_blocks : kNormBlocks;
+  const dim3 grid((unsigned)(nchunks < cap ? nchunks : cap));
+  if ((reinterpret_cast<uintptr_t>(g) & 15) == 0)
+    hipLaunchKernelGGL(grad_norm_partial_kernel<true>, grid, dim3(kT), 0, st, g, n, nchunks,
+                       partial);
+  else   // same chunks, same order, 4-byte loads
+    hipLaunchKernelGGL(grad_norm_partial_kernel<false>, grid, dim3(kT), 0, st, g, n, nchunks,
+                       partial);
+}
+
+void dtf_grad_norm_finish(const double* partial, long nchunks, const double* extra, int nextra,
+                          float gscale, float clip, GradNormRecord* rec, hipStream_t st) {
+  hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(kT), 0, st, partial,
+                     nchunks > 0 ? nchunks : 0, extra, nextra > 0 ? nextra : 0, gscale, clip, rec);
+}
+
+void dtf_grad_norm(const float* g, long n, double* partial, int max_blocks, const double* extra,
+                   int nextra, float gscale, float clip, GradNormRecord* rec, hipStream_t st) {
+  dtf_grad_norm_partial(g, n, partial, max_blocks, st);
+  dtf_grad_norm_finish(partial, n > 0 ? (n + kNormChunk - 1) / kNormChunk : 0, extra, nextra,
+                       gscale, clip, rec, st);
 }
 
 void dtf_cast_f32_bf16(const float* x, bf16_t* y, long n, hipStream_t st) {

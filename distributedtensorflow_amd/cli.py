@@ -30,6 +30,7 @@ from __future__ import annotations
 import argparse
 import datetime
 import json
+import math
 import os
 import subprocess
 import sys
@@ -64,9 +65,13 @@ def build_parser():
     p.add_argument("--model", choices=MODELS, default="mnist_cnn")
     p.add_argument("--strategy", choices=STRATEGIES, default=None)
     p.add_argument("--device", choices=("auto", "cpu", "gpu"), default="auto")
-    p.add_argument("--optimizer", choices=("adam", "adagrad", "momentum", "sgd", "lamb", "lars"),
+    p.add_argument("--optimizer",
+                   choices=("adam", "adagrad", "momentum", "sgd", "lamb", "lars", "adamw"),
                    default=None,
-                   help="lars: the large-batch ResNet recipe (needs --learning_rate)")
+                   help="lars: the large-batch ResNet recipe (needs --learning_rate); adamw: "
+                        "BERT's AdamWeightDecayOptimizer (with --clip_norm 1.0 the BERT recipe)")
+    p.add_argument("--clip_norm", type=float, default=None,
+                   help="clip every step's gradient to this global norm, inside the fused update")
     p.add_argument("--label_smoothing", type=float, default=0.0,
                    help="label smoothing of the sparse softmax cross-entropy loss")
     p.add_argument("--num_ps", type=int, default=None, help="colocated PS owners (strategy ps)")
@@ -146,28 +151,36 @@ def _spawn_local(args, argv):
     return subprocess.call(cmd)
 
 
-def _make_optimizer(name, lr, model_name, batch_global, max_steps=None):
+def _make_optimizer(name, lr, model_name, batch_global, max_steps=None, clip_norm=None):
     from . import optimizers as O
     from .optimizers.optimizers import cosine_decay, polynomial_decay
+    kw = {} if clip_norm is None else {"clip_norm": clip_norm}
     if name == "adam":
-        return O.AdamOptimizer(lr)
+        return O.AdamOptimizer(lr, **kw)
     if name == "adagrad":
-        return O.AdagradOptimizer(lr)
+        return O.AdagradOptimizer(lr, **kw)
     if name == "sgd":
-        return O.GradientDescentOptimizer(lr)
+        return O.GradientDescentOptimizer(lr, **kw)
     if name == "momentum":
         if model_name.startswith("resnet"):
             return O.MomentumOptimizer(cosine_decay(lr * batch_global / 256, 90 * 5000,
-                                                    warmup_steps=500), 0.9, weight_decay=1e-4)
-        return O.MomentumOptimizer(lr, 0.9)
+                                                    warmup_steps=500), 0.9, weight_decay=1e-4,
+                                       **kw)
+        return O.MomentumOptimizer(lr, 0.9, **kw)
     if name == "lamb":
-        return O.LAMBOptimizer(polynomial_decay(lr, 10000, warmup_steps=100), weight_decay=0.01)
+        return O.LAMBOptimizer(polynomial_decay(lr, 10000, warmup_steps=100), weight_decay=0.01,
+                               **kw)
     if name == "lars":
         # large-batch recipe: warm-up over the first 5% of the run, then polynomial (power 2)
         # decay to zero at the last step
         return O.LARSOptimizer(polynomial_decay(lr, max_steps, power=2,
                                                 warmup_steps=max(1, max_steps // 20)),
-                               0.9, weight_decay=1e-4)
+                               0.9, weight_decay=1e-4, **kw)
+    if name == "adamw":
+        # google-research/bert: linear warm-up over the first 1% of the run, then linear decay
+        # to zero at the last step
+        return O.AdamWeightDecayOptimizer(
+            polynomial_decay(lr, max_steps, warmup_steps=math.ceil(0.01 * max_steps)), **kw)
     raise ValueError(name)
 
 
@@ -196,7 +209,12 @@ def run(args):
     batch, opt_name, lr = DEFAULTS[args.model]
     batch = args.batch_size or batch
     opt_name = args.optimizer or opt_name
+    if opt_name == "adamw":
+        lr = 1e-4                      # the BERT paper's; image models must name theirs (main)
     lr = args.learning_rate if args.learning_rate is not None else lr
+    if args.clip_norm is not None and args.job_name:
+        from .optimizers.base import CLIP_BETWEEN_GRAPH
+        raise SystemExit(CLIP_BETWEEN_GRAPH)
     want_gpu = (args.device == "gpu" or
                 (args.device == "auto" and torch.cuda.is_available() and args.num_gpus != 0))
 
@@ -288,7 +306,8 @@ def run(args):
             from .models import bert
             model = getattr(bert, args.model)()
         model.train()
-        opt = _make_optimizer(opt_name, lr, args.model, batch * nrep, args.max_steps)
+        opt = _make_optimizer(opt_name, lr, args.model, batch * nrep, args.max_steps,
+                              args.clip_norm)
         if args.sync_replicas and server is not None:
             nw = len(server.worker_ranks())
             opt = dtf.train.SyncReplicasOptimizer(
@@ -363,6 +382,9 @@ def run(args):
     result = {"model": args.model, "strategy": type(strategy).__name__, "replicas": nrep,
               "global_step": global_step.value(), "elapsed_s": round(elapsed, 2),
               "final_loss": None if last is None else round(float(last[0]), 4)}
+    if args.clip_norm is not None and last is not None:
+        # the last step's pre-clip norm: the one host read of it
+        result["grad_norm"] = round(float(opt.last_grad_norm.item()), 6)
     steps_done = global_step.value() - (first_step or 0)
     if steps_done > 0 and server is None:
         result["examples_per_sec"] = round(steps_done * batch * nrep / elapsed, 1)
@@ -490,6 +512,9 @@ def main(argv=None):
     if args.optimizer == "lars" and args.learning_rate is None:
         # no LARS learning rate has been validated on real data: there is no default to fall to
         parser.error("--optimizer lars requires --learning_rate")
+    if args.optimizer == "adamw" and args.learning_rate is None and \
+            not args.model.startswith("bert"):
+        parser.error("--optimizer adamw requires --learning_rate with an image model")
     check_data_args(args)
     if (args.num_gpus or 0) > 1 and "WORLD_SIZE" not in os.environ and not args.job_name:
         return _spawn_local(args, argv)

@@ -99,8 +99,19 @@ def default_decay_filter(v):
     return not (re.search(r"(batch_norm|_bn/|/gamma|/beta|/bias)", name) or v.dim() <= 1)
 
 
+CLIP_BETWEEN_GRAPH = ("clip_norm is not available in the between-graph parameter-server mode: "
+                      "gradient buckets leave the worker from the backward hooks before the "
+                      "global norm is known")
+
+
 class Optimizer:
-    """Base class.  Subclasses implement ``_build_slots`` and ``_apply_native/_apply_reference``."""
+    """Base class.  Subclasses implement ``_build_slots`` and ``_apply_native/_apply_reference``.
+
+    ``clip_norm``: clip every step's gradient to this global L2 norm (``tf.clip_by_global_norm``
+    of ``grad_scale * g``, then the update).  One deterministic norm pass over the gradient
+    writes the multiplier to the device and the fused update reads it from there: no pass that
+    rewrites the gradient, no host sync.  ``last_grad_norm`` (a one-element device tensor) holds
+    the step's pre-clip norm."""
 
     slot_names: tuple = ()
     # the update of each element depends only on that element's gradient / slots (a sharded
@@ -109,7 +120,16 @@ class Optimizer:
     elementwise: bool = True
 
     def __init__(self, learning_rate, name, weight_decay=0.0, decay_filter=None,
-                 use_locking=False):
+                 use_locking=False, clip_norm=None):
+        if clip_norm is not None:
+            clip_norm = float(clip_norm)
+            if not clip_norm > 0.0:
+                raise ValueError(f"clip_norm must be positive, got {clip_norm}")
+        self.clip_norm = clip_norm
+        self.last_grad_norm = None   # [1] fp32 on the device once built with clip_norm
+        self._clip_rec = None        # {S: f64 | norm: f32, gmul: f32}, the norm pass's record
+        self._clip_slab = None       # one fp64 partial sum per chunk of the norm pass
+        self._clip_held = False      # a reducer formed this step's record: _apply keeps it
         self._lr_value = learning_rate
         self.name = name
         self.weight_decay = weight_decay
@@ -138,6 +158,9 @@ class Optimizer:
             return self.space
         from ..parallel import strategy as _strat
         variables = list(variables)
+        strat = _strat.get_strategy()
+        if self.clip_norm is not None and getattr(strat, "mode", None) == "between_graph":
+            raise ValueError(CLIP_BETWEEN_GRAPH)
         dev = variables[0].device
         shadow = (torch.bfloat16 if dev.type == "cuda" else None) if self.shadow_dtype == "auto" \
             else self.shadow_dtype
@@ -146,7 +169,7 @@ class Optimizer:
         self._build_slots()
         self._lr_dev = torch.zeros(4, device=dev, dtype=torch.float32)
         self._nonfinite = torch.zeros(1, device=dev, dtype=torch.int32)
-        strat = _strat.get_strategy()
+        self._build_clip()
         self._reducer = strat.make_gradient_reducer(self.space)
         strat.broadcast_space(self.space)
         return self.space
@@ -196,6 +219,12 @@ class Optimizer:
         """Serializable description (shipped to parameter-server tasks)."""
         raise NotImplementedError
 
+    def _cfg(self, cfg):
+        # only when set: the configurations of unclipped optimizers stay what they were
+        if self.clip_norm is not None:
+            cfg["clip_norm"] = self.clip_norm
+        return cfg
+
     def minimize(self, loss, global_step=None, var_list=None):
         """backward -> (cross-replica reduce, overlapped) -> fused update -> global_step += 1."""
         if var_list is None:
@@ -215,9 +244,79 @@ class Optimizer:
         if not self._capturing:
             self._refresh_hyper()
 
-    def _apply(self, gscale, rng=None):
+    # ------------------------------------------------------------------ global-norm clip
+    def _build_clip(self):
+        if self.clip_norm is None:
+            return
+        sp = self.space
+        self._clip_rec = torch.zeros(2, device=sp.device, dtype=torch.float64)
+        f32 = self._clip_rec.view(torch.float32)
+        self.last_grad_norm, self._gmul = f32[2:3], f32[3:4]
+        if sp.device.type == "cuda":
+            from ..ops import native
+            K = native.kernels()
+            assert K.grad_norm_record_bytes() == 16
+            self._clip_chunk = K.grad_norm_chunk()
+            # any split of the space into ranges needs at most one short chunk per range more
+            self._clip_slab = torch.zeros(sp.numel // self._clip_chunk + 64, device=sp.device,
+                                          dtype=torch.float64)
+
+    def _gfactor(self, gscale):
+        """What the reference update multiplies g by: ``gscale``, or the record's multiplier."""
+        return gscale if self.clip_norm is None else self._gmul[0]
+
+    def _gmul_ptr(self):
+        """Device address of the clip multiplier for the fused update kernels (0: use gscale)."""
+        return 0 if self.clip_norm is None else self._gmul.data_ptr()
+
+    def _grad_norm_pass(self, gscale, ranges, extra=None):
+        """Form the record from S = sum of g^2 over ``ranges`` [(start, end)] plus the fp64
+        sums in ``extra`` (other ranks', added in index order): norm = gscale * sqrt(S),
+        gmul = gscale * clip / max(norm, clip) in fp64, rounded once to fp32; NaN for a
+        non-finite S.  ``_clip_rec[0]`` is S."""
+        sp, rec = self.space, self._clip_rec
+        if sp.device.type == "cuda":
+            from ..ops import native
+            K, ch = native.kernels(), self._clip_chunk
+            st = torch.cuda.current_stream().cuda_stream
+            need = sum(-(-(e - s) // ch) for s, e in ranges)
+            if need > self._clip_slab.numel():
+                self._clip_slab = torch.zeros(need, device=sp.device, dtype=torch.float64)
+            off = 0
+            for s, e in ranges:
+                K.grad_norm_partial(sp.grad.data_ptr() + 4 * s, e - s,
+                                    self._clip_slab.data_ptr() + 8 * off, 0, st)
+                off += -(-(e - s) // ch)
+            K.grad_norm_finish(self._clip_slab.data_ptr(), off,
+                               0 if extra is None else extra.data_ptr(),
+                               0 if extra is None else extra.numel(), gscale, self.clip_norm,
+                               rec.data_ptr(), st)
+            return
+        with torch.no_grad():
+            S = torch.zeros((), dtype=torch.float64)
+            for s, e in ranges:
+                S = S + sp.grad[s:e].double().square().sum()
+            if extra is not None:
+                for x in extra.double():
+                    S = S + x
+            # the kernels take gscale and clip as fp32
+            gs = float(torch.tensor(gscale, dtype=torch.float32))
+            c = float(torch.tensor(self.clip_norm, dtype=torch.float32))
+            norm = gs * S.sqrt()
+            gm = gs * c / torch.clamp(norm, min=c)
+            gm = torch.where(torch.isfinite(S), gm, torch.full_like(gm, float("nan")))
+            rec[0] = S
+            self.last_grad_norm[0] = norm.float()
+            self._gmul[0] = gm.float()
+
+    def _apply(self, gscale, rng=None, extra=None):
         """Run the update over the whole flat buffer, or only over ``rng = (start, end)`` (the
-        slice a parameter-server shard owns)."""
+        slice a parameter-server shard owns).  With ``clip_norm`` the norm is that of the range
+        plus ``extra`` (fp64 sums of squares held elsewhere), unless a reducer has already
+        formed this step's record (``_clip_held``)."""
+        if self.clip_norm is not None and not self._clip_held:
+            self._grad_norm_pass(gscale, [rng if rng is not None else (0, self.space.numel)],
+                                 extra)
         self._range = rng
         try:
             if self.space.device.type == "cuda":

@@ -7,6 +7,7 @@ CPU: the same math in PyTorch (OneDeviceStrategy("/cpu:0"), BASELINE config 1).
 from __future__ import annotations
 
 import math
+import re
 
 import torch
 
@@ -36,8 +37,8 @@ class GradientDescentOptimizer(Optimizer):
         self._dummy = self.space.new_slot()
 
     def get_config(self):
-        return {"type": "sgd", "learning_rate": self.learning_rate(),
-                "weight_decay": self.weight_decay}
+        return self._cfg({"type": "sgd", "learning_rate": self.learning_rate(),
+                          "weight_decay": self.weight_decay})
 
     def _apply_native(self, gscale):
         self._maybe_refresh_hyper()
@@ -46,9 +47,10 @@ class GradientDescentOptimizer(Optimizer):
             K.sgd_momentum(sp.master.data_ptr() + 4 * s, sp.grad.data_ptr() + 4 * s,
                            self._dummy.data_ptr() + 4 * s, _sh(sp, s), e - s,
                            self._lr_dev.data_ptr(), 0.0, self.weight_decay if dec else 0.0,
-                           gscale, 0, self._nonfinite.data_ptr(), _st())
+                           gscale, 0, self._nonfinite.data_ptr(), _st(), gmul=self._gmul_ptr())
 
     def _apply_reference(self, gscale):
+        gscale = self._gfactor(gscale)
         lr = self.learning_rate()
         sp = self.space
         with torch.no_grad():
@@ -74,9 +76,9 @@ class MomentumOptimizer(Optimizer):
         self.slots = [FlatSlot("Momentum", self.space.new_slot())]
 
     def get_config(self):
-        return {"type": "momentum", "learning_rate": self.learning_rate(),
-                "momentum": self.momentum, "use_nesterov": self.use_nesterov,
-                "weight_decay": self.weight_decay}
+        return self._cfg({"type": "momentum", "learning_rate": self.learning_rate(),
+                          "momentum": self.momentum, "use_nesterov": self.use_nesterov,
+                          "weight_decay": self.weight_decay})
 
     def _apply_native(self, gscale):
         self._maybe_refresh_hyper()
@@ -85,9 +87,11 @@ class MomentumOptimizer(Optimizer):
             K.sgd_momentum(sp.master.data_ptr() + 4 * s, sp.grad.data_ptr() + 4 * s,
                            a.data_ptr() + 4 * s, _sh(sp, s), e - s, self._lr_dev.data_ptr(),
                            float(self.momentum), self.weight_decay if dec else 0.0, gscale,
-                           int(self.use_nesterov), self._nonfinite.data_ptr(), _st())
+                           int(self.use_nesterov), self._nonfinite.data_ptr(), _st(),
+                           gmul=self._gmul_ptr())
 
     def _apply_reference(self, gscale):
+        gscale = self._gfactor(gscale)
         lr, mu = self.learning_rate(), self.momentum
         sp, a = self.space, self.slots[0].buf
         with torch.no_grad():
@@ -117,8 +121,8 @@ class AdamOptimizer(Optimizer):
                       FlatSlot("Adam_1", self.space.new_slot())]
 
     def get_config(self):
-        return {"type": "adam", "learning_rate": self.learning_rate(), "beta1": self.beta1,
-                "beta2": self.beta2, "epsilon": self.epsilon}
+        return self._cfg({"type": "adam", "learning_rate": self.learning_rate(),
+                          "beta1": self.beta1, "beta2": self.beta2, "epsilon": self.epsilon})
 
     def lr_t(self):
         return tf_adam_lr_t(self.learning_rate(), self.beta1, self.beta2, self.iterations)
@@ -134,9 +138,11 @@ class AdamOptimizer(Optimizer):
             K.adam(sp.master.data_ptr() + 4 * s, sp.grad.data_ptr() + 4 * s, m.data_ptr() + 4 * s,
                    v.data_ptr() + 4 * s, _sh(sp, s), e - s, self._lr_dev.data_ptr(),
                    float(self.beta1), float(self.beta2), float(self.epsilon),
-                   self.weight_decay if dec else 0.0, gscale, self._nonfinite.data_ptr(), _st())
+                   self.weight_decay if dec else 0.0, gscale, self._nonfinite.data_ptr(), _st(),
+                   gmul=self._gmul_ptr())
 
     def _apply_reference(self, gscale):
+        gscale = self._gfactor(gscale)
         lr_t = self.lr_t()
         sp = self.space
         m, v = self.slots[0].buf, self.slots[1].buf
@@ -157,6 +163,53 @@ class AdamOptimizer(Optimizer):
                 "beta2_power": torch.tensor(self.beta2 ** (t + 1))}
 
 
+class AdamWeightDecayOptimizer(AdamOptimizer):
+    """google-research/bert's ``AdamWeightDecayOptimizer``: Adam without bias correction and
+    with decoupled weight decay,
+
+        m = b1 m + (1-b1) g;  v = b2 v + (1-b2) g^2;  p -= lr * (m / (sqrt(v) + eps) + wd * p)
+
+    where wd is ``weight_decay_rate``, or 0 for a variable whose name matches
+    (``re.search``) an entry of ``exclude_from_weight_decay``.  This is the fused Adam kernel
+    with lr_t = lr.  Slots are BERT's ``adam_m`` / ``adam_v``; there are no beta-power
+    variables.  The BERT recipe is this optimizer with ``clip_norm=1.0``."""
+
+    slot_names = ("adam_m", "adam_v")
+    # no variable carries the update count: a restore takes it from the global step, the
+    # variable BERT's learning-rate schedule is a function of
+    iterations_from_global_step = True
+
+    def __init__(self, learning_rate, weight_decay_rate=0.01, beta_1=0.9, beta_2=0.999,
+                 epsilon=1e-6, exclude_from_weight_decay=("LayerNorm", "layer_norm", "bias"),
+                 clip_norm=None, name="AdamWeightDecayOptimizer", **kw):
+        self.exclude_from_weight_decay = tuple(exclude_from_weight_decay or ())
+        kw.setdefault("decay_filter", self._decays)
+        super().__init__(learning_rate, beta_1, beta_2, epsilon, name=name,
+                         weight_decay=weight_decay_rate, clip_norm=clip_norm, **kw)
+
+    def _decays(self, v):
+        name = getattr(v, "_dtf_name", "")
+        return not any(re.search(r, name) for r in self.exclude_from_weight_decay)
+
+    def _build_slots(self):
+        self.slots = [FlatSlot("adam_m", self.space.new_slot()),
+                      FlatSlot("adam_v", self.space.new_slot())]
+
+    def get_config(self):
+        return self._cfg({"type": "adamw", "learning_rate": self.learning_rate(),
+                          "weight_decay_rate": self.weight_decay, "beta_1": self.beta1,
+                          "beta_2": self.beta2, "epsilon": self.epsilon})
+
+    def lr_t(self):
+        return self.learning_rate()          # no bias correction
+
+    def _refresh_hyper(self):
+        self._lr_dev[0].fill_(self.learning_rate())
+
+    def non_slot_variables(self):
+        return {}
+
+
 class AdagradOptimizer(Optimizer):
     """tf.train.AdagradOptimizer: acc += g^2; p -= lr * g / sqrt(acc); acc0 = 0.1."""
 
@@ -170,8 +223,8 @@ class AdagradOptimizer(Optimizer):
         self.slots = [FlatSlot("Adagrad", self.space.new_slot(self.initial_accumulator_value))]
 
     def get_config(self):
-        return {"type": "adagrad", "learning_rate": self.learning_rate(),
-                "initial_accumulator_value": self.initial_accumulator_value}
+        return self._cfg({"type": "adagrad", "learning_rate": self.learning_rate(),
+                          "initial_accumulator_value": self.initial_accumulator_value})
 
     def _apply_native(self, gscale):
         self._maybe_refresh_hyper()
@@ -179,9 +232,10 @@ class AdagradOptimizer(Optimizer):
         for s, e, _ in self._regions():
             K.adagrad(sp.master.data_ptr() + 4 * s, sp.grad.data_ptr() + 4 * s,
                       acc.data_ptr() + 4 * s, _sh(sp, s), e - s, self._lr_dev.data_ptr(), gscale,
-                      self._nonfinite.data_ptr(), _st())
+                      self._nonfinite.data_ptr(), _st(), gmul=self._gmul_ptr())
 
     def _apply_reference(self, gscale):
+        gscale = self._gfactor(gscale)
         lr = self.learning_rate()
         sp, acc = self.space, self.slots[0].buf
         with torch.no_grad():
@@ -209,8 +263,9 @@ class LAMBOptimizer(Optimizer):
         self.beta1, self.beta2, self.epsilon, self.chunk = beta1, beta2, epsilon, chunk
 
     def get_config(self):
-        return {"type": "lamb", "learning_rate": self.learning_rate(), "beta1": self.beta1,
-                "beta2": self.beta2, "epsilon": self.epsilon, "weight_decay": self.weight_decay}
+        return self._cfg({"type": "lamb", "learning_rate": self.learning_rate(),
+                          "beta1": self.beta1, "beta2": self.beta2, "epsilon": self.epsilon,
+                          "weight_decay": self.weight_decay})
 
     def _build_slots(self):
         sp = self.space
@@ -265,9 +320,11 @@ class LAMBOptimizer(Optimizer):
                   _sh(sp, 0), chunks.data_ptr(), nchunks, self._hyper.data_ptr(),
                   self._lr_dev.data_ptr(), float(self.beta1), float(self.beta2),
                   float(self.epsilon), self._wd_seg.data_ptr(), gscale, self._norms.data_ptr(),
-                  self._norms.data_ptr() + 8 * self._nseg, self._nonfinite.data_ptr(), _st())
+                  self._norms.data_ptr() + 8 * self._nseg, self._nonfinite.data_ptr(), _st(),
+                  gmul=self._gmul_ptr())
 
     def _apply_reference(self, gscale):
+        gscale = self._gfactor(gscale)
         t = self.iterations
         lr = self.learning_rate()
         sp, m, v = self.space, self.slots[0].buf, self.slots[1].buf
@@ -327,9 +384,11 @@ class LARSOptimizer(Optimizer):
         self.slot_names = (name,)
 
     def get_config(self):
-        return {"type": "lars", "learning_rate": self.learning_rate(), "momentum": self.momentum,
-                "weight_decay": self.weight_decay, "eeta": self.eeta, "epsilon": self.epsilon,
-                "use_nesterov": self.use_nesterov, "name": self.name, "chunk": self.chunk}
+        return self._cfg({"type": "lars", "learning_rate": self.learning_rate(),
+                          "momentum": self.momentum, "weight_decay": self.weight_decay,
+                          "eeta": self.eeta, "epsilon": self.epsilon,
+                          "use_nesterov": self.use_nesterov, "name": self.name,
+                          "chunk": self.chunk})
 
     def _build_slots(self):
         sp = self.space
@@ -380,9 +439,10 @@ class LARSOptimizer(Optimizer):
                   chunks.data_ptr(), nchunks, segs.data_ptr(), self._lr_dev.data_ptr(),
                   float(self.momentum), float(self.weight_decay), float(self.eeta),
                   float(self.epsilon), gscale, int(self.use_nesterov), self._norms.data_ptr(),
-                  self._nonfinite.data_ptr(), _st())
+                  self._nonfinite.data_ptr(), _st(), gmul=self._gmul_ptr())
 
     def _apply_reference(self, gscale):
+        gscale = self._gfactor(gscale)
         lr, mu, wd = self.learning_rate(), self.momentum, self.weight_decay
         sp, a = self.space, self.slots[0].buf
         lo, hi = getattr(self, "_range", None) or (0, sp.numel)

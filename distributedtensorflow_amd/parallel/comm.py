@@ -24,8 +24,8 @@ import torch
 import torch.distributed as dist
 
 _OPS = {"sum": 0, "prod": 1, "max": 2, "min": 3, "avg": 4}
-_DTYPES = {torch.float32: 7, torch.bfloat16: 9, torch.float16: 6, torch.int64: 4,
-           torch.int32: 2, torch.uint8: 1}
+_DTYPES = {torch.float32: 7, torch.float64: 8, torch.bfloat16: 9, torch.float16: 6,
+           torch.int64: 4, torch.int32: 2, torch.uint8: 1}
 # RCCL unique-id store keys: "dtf/rccl_uid/<n>" under the process group's store, which the
 # launcher scopes per cluster epoch (PrefixStore "g<epoch>").  ``n`` counts communicators created
 # in THIS world and restarts at 0 whenever a world is formed (reset_uid_index, called by

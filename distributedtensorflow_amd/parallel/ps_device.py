@@ -197,14 +197,18 @@ class LayoutSpace:
 
 
 def _make_optimizer(cfg, space):
-    from ..optimizers import (AdagradOptimizer, AdamOptimizer, GradientDescentOptimizer,
-                              LAMBOptimizer, LARSOptimizer, MomentumOptimizer)
+    from ..optimizers import (AdagradOptimizer, AdamOptimizer, AdamWeightDecayOptimizer,
+                              GradientDescentOptimizer, LAMBOptimizer, LARSOptimizer,
+                              MomentumOptimizer)
+    from ..optimizers.base import CLIP_BETWEEN_GRAPH
     from .strategy import _NullReducer
     cfg = dict(cfg)
+    if cfg.get("clip_norm") is not None:
+        raise ValueError(CLIP_BETWEEN_GRAPH)
     kind = cfg.pop("type")
     cls = {"adam": AdamOptimizer, "adagrad": AdagradOptimizer, "momentum": MomentumOptimizer,
            "sgd": GradientDescentOptimizer, "lamb": LAMBOptimizer,
-           "lars": LARSOptimizer}[kind]
+           "lars": LARSOptimizer, "adamw": AdamWeightDecayOptimizer}[kind]
     opt = cls(**cfg)
     opt.decay_filter = lambda v: getattr(v, "_dtf_decay", True)
     opt.space = space

@@ -103,17 +103,21 @@ def choose_plane(requested, ps_device):
 
 class _Shard:
     def __init__(self, spec, values, device):
-        from ..optimizers import (AdagradOptimizer, AdamOptimizer, GradientDescentOptimizer,
-                                  LAMBOptimizer, LARSOptimizer, MomentumOptimizer)
+        from ..optimizers import (AdagradOptimizer, AdamOptimizer, AdamWeightDecayOptimizer,
+                                  GradientDescentOptimizer, LAMBOptimizer, LARSOptimizer,
+                                  MomentumOptimizer)
+        from ..optimizers.base import CLIP_BETWEEN_GRAPH
         self.names = spec["names"]
         self.shapes = [tuple(s) for s in spec["shapes"]]
         self.numel = int(values.numel())
         self.device = device
         opt = dict(spec["optimizer"])
+        if opt.get("clip_norm") is not None:
+            raise ValueError(CLIP_BETWEEN_GRAPH)
         kind = opt.pop("type")
         cls = {"adam": AdamOptimizer, "adagrad": AdagradOptimizer, "momentum": MomentumOptimizer,
                "sgd": GradientDescentOptimizer, "lamb": LAMBOptimizer,
-               "lars": LARSOptimizer}[kind]
+               "lars": LARSOptimizer, "adamw": AdamWeightDecayOptimizer}[kind]
         self.params = [torch.nn.Parameter(t.clone().to(device)) for t in
                        _split(values, self.shapes)]
         for p, n in zip(self.params, self.names):

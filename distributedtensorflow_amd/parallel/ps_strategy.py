@@ -469,6 +469,7 @@ class _ColocatedPSReducer(BucketedAllReduce):
         self.overlap_gather = overlap_gather
         self.gpending = [None] * len(self.buckets)
         self._n_pending = 0
+        self._norm_sums = None       # the owners' fp64 sums of squares (clip_norm)
         for b, (_, _, mem) in enumerate(self.buckets):
             for i in mem:
                 space.order[i]._dtf_gbucket = b
@@ -500,9 +501,16 @@ class _ColocatedPSReducer(BucketedAllReduce):
     @comm_call
     def apply_remote(self, optimizer):
         self.drain()
-        for o, s, e in self.ranges:
-            if o == self.rank and e > s:
+        mine = [(s, e) for o, s, e in self.ranges if o == self.rank and e > s]
+        clip = getattr(optimizer, "clip_norm", None) is not None
+        if clip:
+            self._global_norm(optimizer, mine)
+        optimizer._clip_held = clip
+        try:
+            for s, e in mine:
                 optimizer._apply(self.grad_scale(), (s, e))
+        finally:
+            optimizer._clip_held = False
         m = self.space.master
         # forward order: the non-decayed tail (BN / bias variables of every layer) first, then
         # the decayed buckets from the first layers (last bucket) to the last layers (bucket 0)
@@ -524,6 +532,19 @@ class _ColocatedPSReducer(BucketedAllReduce):
         else:
             self.drain()
         return None
+
+    def _global_norm(self, optimizer, mine):
+        """Every owner holds only its part of the reduced gradient: each sums the squares of the
+        ranges it owns (a rank that owns nothing contributes 0), the sums are all-gathered
+        (8 bytes per rank) and every rank adds them in rank order -- the same S, and with it
+        the same clip multiplier, on every rank."""
+        gs = self.grad_scale()
+        optimizer._grad_norm_pass(gs, mine)
+        if self._norm_sums is None:
+            self._norm_sums = torch.zeros(self.world, device=self.space.device,
+                                          dtype=torch.float64)
+        self.comm.all_gather(self._norm_sums, optimizer._clip_rec[0:1]).wait()
+        optimizer._grad_norm_pass(gs, [], self._norm_sums)
 
     @comm_call
     def _wait_gather(self, b):
