@@ -135,7 +135,6 @@ PYBIND11_MODULE(_dtf_hip, m) {
   });
   m.def("gemm_tile_rows", &dtf_gemm_tile_rows);
   m.def("gemm_set_variant", &dtf_gemm_set_variant);
-  m.def("gemm_set_pp", &dtf_gemm_set_pp);
   m.def("gemm_set_pp2", &dtf_gemm_set_pp2);
   m.def("gemm_get_pp2", &dtf_gemm_get_pp2);
   m.def("gemm_pp2_ok", &dtf_gemm_pp2_ok);
@@ -700,7 +699,6 @@ PYBIND11_MODULE(_dtf_hip, m) {
                              P<float>(part_p), S(stream));
     check_launch("gemm_stream_bnb_dual");
   });
-  m.def("gemm_set_stagger", &dtf_gemm_set_stagger);
   m.def("gemm_set_group", &dtf_gemm_set_group);
   m.def("wgrad_get_pipe", &dtf_wgrad_get_pipe);
   m.def("lds_probe", [](int bytes, int blocks, uintptr_t errors, int spin, uintptr_t st) {

@@ -22,6 +22,37 @@
 //   * XCD-aware bijective block remap, N-tile fastest: blocks sharing an A panel share an L2.
 //   * epilogue: accumulators (+bias, ReLU) -> bf16 -> LDS -> 16-B coalesced stores (+Cin: the
 //     beta = 1 accumulation used to fold a residual gradient into a data-gradient GEMM).
+//
+// The default dispatch reaches gemm_nt_kernel as the 256 x 128 tile (variant 1; its conv form is
+// the two-group SCHED 3) and the 256 x 256 ping-pong (variant 8), and the persistent
+// gemm_pp2_kernel (variant 15).  Variant 13 is gemm_stream.hip.  Two more instantiations of code
+// that those routes compile anyway stay behind gemm_set_variant as the references of
+// tests/test_dense_gpu.py (test_gemm_pingpong_schedule_bit_identical):
+//   * 0: 256 x 256 x 64, two LDS slots, one barrier per K-step (SCHED 0) -- the best of round 2's
+//     first five forms at 0.80-0.91x hipBLASLt on the BERT shapes; the ping-pong gained 10-19 %
+//     over it (profiles/measurements/r2_gemm_vs_hipblaslt.jsonl, r2_gemm_pingpong_setprio_ab.jsonl)
+//   * 10: the two-group 256 x 128 schedule (SCHED 3) on dense operands: 0.95-1.07x of variant 1
+//     on the ResNet 1x1 shapes and never made a route (r2_gemm_256x128_pingpong_resnet1x1.jsonl)
+// gemm_set_variant keeps these numbers because the records under profiles/ use them.  What was
+// tried, measured slower and deleted (the ids are what those records call them):
+//   * 2, 3: BK 32 with a four-slot ring (256 x 256, 256 x 128): 0.88-1.00x and 0.75-0.83x of 0 on
+//     the BERT shapes (r2_gemm_vs_hipblaslt.jsonl)
+//   * 4: SCHED 1, fragments double-buffered in registers and the barrier moved between the two
+//     32-deep halves of a step: 0.88-1.00x of 0 on the BERT shapes (r2_gemm_vs_hipblaslt.jsonl)
+//   * 5, 6, 7: NW 4, four waves of 128 x 128 with the accumulators in AGPRs (SCHED 0, SCHED 1,
+//     BK 32): 0.42-0.80x of the ping-pong -- one wave per SIMD leaves the matrix pipe idle during
+//     barriers and LDS waits (r3_gemm_occ2_and_epilogue_split.jsonl "r3_gemm_nw4";
+//     r3_gemm_4wave_vgpr_staged.jsonl for the VGPR-staged forms 14 / 15 of that round)
+//   * 9: the ping-pong without s_setprio around its MFMA sections: within noise of 8
+//     (r2_gemm_pingpong_setprio_ab.jsonl)
+//   * 11: gemm_pp_kernel, round 3's persistent kernel with 8-B register-direct stores: bit-identical
+//     to 8 but 0.86-1.03x of it -- the tile lookup, per-tile descriptors and conv geometry inside
+//     every look-ahead issue spilled SGPRs on the ping-pong's load sections
+//     (r3_gemm_persistent_register_epilogue.jsonl, r2_gemm_epilogue_probes.jsonl); gemm_pp2_kernel
+//     is its design with that fixed
+//   * 12: two 4-wave 256 x 128 blocks per CU (BK 32, three slots) with part of the first round
+//     started late: bit-identical to 8 but 0.65-0.9x of it under every stagger policy
+//     (r3_gemm_occ2_and_epilogue_split.jsonl)
 #include <algorithm>
 #include <stdexcept>
 #include <string>
@@ -63,9 +94,8 @@ struct GemmArgs {
   // bias + GELU forward epilogue (BERT's first FFN GEMM): C = z = acc + bias (bf16) and
   // gelu_out = gelu(z), the pre-activation for the GELU backward and the activation for FFN2
   bf16_t* gelu_out;
-  int ncu;                          // OCC 2 kernels: compute units (the first resident round)
+  int a_bytes, b_bytes;             // gemm_pp2_kernel: the whole-operand descriptor sizes
   int group_m;                      // > 0: grouped tile order (GM M-panels x all N per group)
-  int stagger_mode, stagger;        // OCC 2: which first-round blocks start late, by how much
 };
 
 // chunk swizzle of a [rows][BK] bf16 tile: 16-row ds_read_b128 fragment reads hit 16 slots
@@ -75,16 +105,13 @@ DTF_DEV int gswz(int row, int ch) {
   return ch ^ ((row / RPB) % CPR);
 }
 
-// BM x BN block tile, BK-deep K-steps, NS-slot LDS ring (DMAs issued NS-1 steps ahead), NW waves.
-//   NW 8: 2 (M) x BN/64 (N) waves, 64-column wave tiles, 2 waves per SIMD;
-//   NW 4: 2 x 2 waves of 128 x 128 -- ONE wave per SIMD whose 64 accumulator fragments live in
-//         the AGPR half of the unified register file (the per-wave tile hipBLASLt's fastest
-//         MI355X kernels use: 16 fragment reads per 64 MFMAs instead of 12 per 32, and no second
-//         wave competing for the SIMD's matrix pipe).
-template <int BM, int BN, int BK, int NS, int NW = 8>
+// BM x BN block tile, BK-deep K-steps, NS-slot LDS ring (DMAs issued NS-1 steps ahead); 8 waves
+// as 8 / (BN/64) (M) x BN/64 (N), 64-column wave tiles, 2 waves per SIMD.
+template <int BM, int BN, int BK, int NS>
 struct GCfg {
+  static constexpr int NW = 8;
   static constexpr int NT = NW * 64;
-  static constexpr int WN = NW == 8 ? BN / 64 : 2, WM = NW / WN;   // wave grid
+  static constexpr int WN = BN / 64, WM = NW / WN;                 // wave grid
   static constexpr int WTM = BM / WM, WTN = BN / WN;               // wave tile
   static constexpr int FM = WTM / 16, FN = WTN / 16;               // 16x16 fragments per wave
   static constexpr int CPR = BK / 8;                       // 16-B chunks per row
@@ -97,28 +124,16 @@ struct GCfg {
 };
 
 // SCHED 0: per K-step {wait; barrier; issue next; reads + MFMAs of both 32-deep halves}.
-// SCHED 1 (BK 64, NS 2): fragments double-buffered in registers and the barrier moved between
-// the two halves -- the reads of half 1 fly under the MFMAs of half 0, the reads of the next
-// step's half 0 under the MFMAs of half 1, so no wave waits on LDS latency at a phase start.
-//
-// OCC 2 (NW 4, 256 x 128 tiles, BK 32, three 24-KB slots; opt-in variant 12): TWO blocks per
-// CU, each of four 128 x 64 wave tiles -- the same per-wave MFMA / fragment-read work and the
-// same accumulator footprint per SIMD as the 8-wave 256 x 256 kernel, as two independent blocks
-// so that one block's C staging and stores overlap the other block's MFMAs.  A set of the
-// first-round blocks starts late by about half a tile (stagger_mode / stagger) so co-resident
-// blocks do not stay in lockstep.  Bit-identical to variant 8 (same MFMA order per accumulator)
-// but 0.65-0.9x of it: the one-barrier-per-32-deep-step schedule loses more in the main loop
-// than the overlap wins (profiles/measurements/r3_gemm_occ2_and_epilogue_split.jsonl).
-template <int BM, int BN, int BK, int NS, int SCHED = 0, int NW = 8, int PP_PRIO = 1,
-          int CONV = 0, int OCC = 1>
-__global__ void __launch_bounds__(NW * 64, OCC == 2 ? NW * 2 / 4 : 1)
+// SCHED 2 / 3: the ping-pong schedules of the 256 x 256 / 256 x 128 tile (below).
+template <int BM, int BN, int BK, int NS, int SCHED = 0, int CONV = 0>
+__global__ void __launch_bounds__(kGT, 1)
 gemm_nt_kernel(const GemmArgs g) {
-  using Cf = GCfg<BM, BN, BK, NS, NW>;
+  using Cf = GCfg<BM, BN, BK, NS>;
+  constexpr int NW = Cf::NW;
   extern __shared__ __attribute__((aligned(16))) bf16_t lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / Cf::WN, wn = wave % Cf::WN;
-  (void)kGT;
 
   const int tiles_n = (g.N + BN - 1) / BN;
   const int tiles_m = (g.M + BM - 1) / BM;
@@ -139,15 +154,6 @@ gemm_nt_kernel(const GemmArgs g) {
   }
   const int m0 = tm * BM, n0 = tn * BN;
   const int nk = (g.K + BK - 1) / BK;
-  if constexpr (OCC == 2) {
-    const int b = blockIdx.x;
-    const bool late = b < 2 * g.ncu &&
-        (g.stagger_mode == 1 ? b >= g.ncu
-         : g.stagger_mode == 2 ? ((b >> 3) & 1) != 0
-         : g.stagger_mode == 3 ? (b & 1) != 0 : false);
-    if (late)
-      for (int i = 0; i < g.stagger; ++i) __builtin_amdgcn_s_sleep(127);
-  }
 
   // descriptors based at this block's first row / column: 32-bit offsets span one panel only
   const int rows_a = min(BM, g.M - m0), rows_b = min(BN, g.N - n0);
@@ -246,7 +252,7 @@ gemm_nt_kernel(const GemmArgs g) {
     // every reader then passes a barrier that follows every issuer's wait.  WAR: a region is
     // restaged >= 2 phases after its last read (reads retire by lgkmcnt(0) right after the
     // reading phase's first barrier).
-    static_assert(BM == 256 && BN == 256 && BK == 64 && NS == 2 && NW == 8, "SCHED 2 geometry");
+    static_assert(BM == 256 && BN == 256 && BK == 64 && NS == 2, "SCHED 2 geometry");
     // piece p, instruction j: this wave's 8-row group (first row r0) of A top (p0) / B left (p1)
     // / B right (p2) / A bottom (p3)
     uint32_t poff[4][2], plds[4][2];
@@ -342,7 +348,7 @@ gemm_nt_kernel(const GemmArgs g) {
     auto mfma_phase = [&](const bf16x8_t* fb, int ah, int bh) {
       sync();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (PP_PRIO) __builtin_amdgcn_s_setprio(1);
+      __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -351,7 +357,7 @@ gemm_nt_kernel(const GemmArgs g) {
           for (int j = 0; j < 2; ++j)
             acc[ah * 4 + i][bh * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                 fA[ks * 4 + i], fb[ks * 2 + j], acc[ah * 4 + i][bh * 2 + j], 0, 0, 0);
-      if (PP_PRIO) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
       sync();
     };
     // prologue: step 0 whole + step 1's A-top / B-left; step 0's A-top / B-left landed
@@ -390,7 +396,7 @@ gemm_nt_kernel(const GemmArgs g) {
     // RAW: A-top/B of step t+1 are waited (vmcnt(8)) in t.q1, A-bottom of step t (vmcnt(10))
     // in t.q0 -- always the phase before the reader.  WAR: step t+2 reuses step t-1's slot,
     // whose regions were last read 2 phases before they are restaged.
-    static_assert(BM == 256 && BN == 128 && BK == 64 && NS == 3 && NW == 8, "SCHED 3 geometry");
+    static_assert(BM == 256 && BN == 128 && BK == 64 && NS == 3, "SCHED 3 geometry");
     const int grp = wave >> 2;
     uint32_t poff[3][2], plds[3][2];
     int pch[3][2], cpix[3][2], chw[3][2];
@@ -507,57 +513,17 @@ gemm_nt_kernel(const GemmArgs g) {
       mfma_phase(1);
     }
     if (grp == 0) sync();
-  } else if constexpr (SCHED == 1) {
-    static_assert(BK == 64 && NS == 2, "SCHED 1: two 32-deep halves per step, two slots");
-    bf16x8_t fa0[Cf::FM], fb0[Cf::FN], fa1[Cf::FM], fb1[Cf::FN];
-    auto rd = [&](bf16x8_t* fa, bf16x8_t* fb, const bf16_t* sa, int ks) {
-      const bf16_t* sb = sa + Cf::SA;
-      const int ch = ks * 4 + fq;
-#pragma unroll
-      for (int j = 0; j < Cf::FN; ++j) {
-        const int r = wn * Cf::WTN + j * 16 + frow;
-        fb[j] = *reinterpret_cast<const bf16x8_t*>(sb + r * BK + gswz<BK>(r, ch) * 8);
-      }
-#pragma unroll
-      for (int i = 0; i < Cf::FM; ++i) {
-        const int r = wm * Cf::WTM + i * 16 + frow;
-        fa[i] = *reinterpret_cast<const bf16x8_t*>(sa + r * BK + gswz<BK>(r, ch) * 8);
-      }
-    };
-    auto mm = [&](const bf16x8_t* fa, const bf16x8_t* fb) {
-#pragma unroll
-      for (int i = 0; i < Cf::FM; ++i)
-#pragma unroll
-        for (int j = 0; j < Cf::FN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-    };
-    issue(0, 0);
-    DTF_WAIT_VM(0);
-    raw_barrier();
-    issue(1, 1);
-    rd(fa0, fb0, lds, 0);
-    for (int kt = 0; kt < nk; ++kt) {
-      const bf16_t* cur = lds + (kt & 1) * Cf::STAGE;
-      rd(fa1, fb1, cur, 1);
-      mm(fa0, fb0);
-      DTF_WAIT_VM(0);                             // step kt+1 landed (this wave) ...
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      raw_barrier();                              // ... every wave's; step kt fully read
-      issue(kt + 2, kt & 1);
-      if (kt + 1 < nk) rd(fa0, fb0, lds + ((kt + 1) & 1) * Cf::STAGE, 0);
-      mm(fa1, fb1);
-    }
   } else {
 #pragma unroll
-  for (int s = 0; s < NS - 1; ++s) issue(s, s);
-  for (int kt = 0; kt < nk; ++kt) {
-    // this wave's DMAs of step kt landed (the NS-2 younger steps may still fly) ...
-    wait_vm<(NS - 2) * (Cf::DA + Cf::DB)>();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    raw_barrier();      // ... and every wave's; every wave finished reading step kt-1's slot
-    issue(kt + NS - 1, (kt + NS - 1) % NS);
-    compute(lds + (kt % NS) * Cf::STAGE);
-  }
+    for (int s = 0; s < NS - 1; ++s) issue(s, s);
+    for (int kt = 0; kt < nk; ++kt) {
+      // this wave's DMAs of step kt landed (the NS-2 younger steps may still fly) ...
+      wait_vm<(NS - 2) * (Cf::DA + Cf::DB)>();
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      raw_barrier();    // ... and every wave's; every wave finished reading step kt-1's slot
+      issue(kt + NS - 1, (kt + NS - 1) % NS);
+      compute(lds + (kt % NS) * Cf::STAGE);
+    }
   }
   DTF_WAIT_VM(0);       // the trailing no-op DMAs still target the ring
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -715,390 +681,16 @@ gemm_nt_kernel(const GemmArgs g) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Persistent ping-pong GEMM with a register-direct epilogue (gemm_pp_kernel).
-//
-// Same 256 x 256 x 64 ping-pong main loop as SCHED 2 above, with two changes aimed at the part
-// of the step the MFMA pipe idles in -- the epilogue, ~30 % of a K = 768 BERT GEMM
-// (profiles/measurements/r2_gemm_epilogue_probes.jsonl):
-//   * the MFMA operands are swapped (D = B . A^T per 16 x 16 fragment), so each lane holds FOUR
-//     CONSECUTIVE OUTPUT COLUMNS of one row: the epilogue stores 8 B per lane straight from the
-//     accumulators (16-lane groups write 32 contiguous bytes; the four fragments of a 64-column
-//     wave strip complete whole 128-B lines back to back in L2) -- no LDS staging, no barrier;
-//   * blocks are PERSISTENT (one per CU, tiles strided by the grid) and the LDS-DMA piece stream
-//     runs ACROSS tiles: the K-loop's look-ahead issues of "step nk, nk + 1" are the NEXT tile's
-//     steps 0 / 1, so while a block stores tile t's outputs the DMA engine is already filling the
-//     ring with tile t + 1.  The ring slot parity follows the block's global step count.
-// Every lane issues the same number of stores per tile (out-of-range ones carry an offset past
-// the C descriptor and are dropped by the hardware range check), so the counted vmcnt waits of
-// the next tile's first phases know exactly how many stores sit behind the pieces they need.
-template <int CONV>
-__global__ void __launch_bounds__(512, 1)
-gemm_pp_kernel(const GemmArgs g) {
-  using Cf = GCfg<256, 256, 64, 2, 8>;
-  constexpr int BM = 256, BN = 256, BK = 64;
-  constexpr int NSTORE = Cf::FM * Cf::FN;          // 8-B stores per lane per tile (32)
-  extern __shared__ __attribute__((aligned(16))) bf16_t lds[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / Cf::WN, wn = wave % Cf::WN;
-  const int tiles_n = (g.N + BN - 1) / BN, tiles_m = (g.M + BM - 1) / BM;
-  const int ntiles = tiles_n * tiles_m;
-  const int nk = (g.K + BK - 1) / BK;              // >= 2 (host)
-  const uint32_t lds0 = lds_addr(lds);
-  const int lrow = lane / Cf::CPR, slot = lane % Cf::CPR;
-  const int frow = lane & 15, fq = lane >> 4;
-  const bool ktail = (g.K % BK) != 0;
-  const int PQc = CONV ? g.P * g.Q : 1;
-  const long img = CONV ? (long)g.H * g.W * g.Cc : 0;
-  const bool strided = CONV && (g.osh != 1 || g.osw != 1);
-
-  // piece pc (0 A-top, 1 B-left, 2 B-right, 3 A-bottom), instruction j: the 8-row group of this
-  // wave inside the tile's A / B panel (see SCHED 2)
-  auto prow = [&](int pc, int j) {
-    const int r0 = pc == 0 ? j * 128 + 8 * wave
-                 : pc == 3 ? 64 + j * 128 + 8 * wave
-                           : (2 * j + (wave >> 2)) * 64 + (pc == 2 ? 32 : 0) + (wave & 3) * 8;
-    return r0 + lrow;
-  };
-  const int pch = gswz<BK>(prow(0, 0), slot) * 8;   // the same for every piece of this wave
-  auto plds = [&](int pc, int j) {
-    const bool isA = pc == 0 || pc == 3;
-    return (uint32_t)((isA ? 0 : Cf::SA) + (prow(pc, j) - lrow) * BK) * 2u;
-  };
-
-  struct Tile { int valid, m0, n0, rows_a, rows_b, n_lo; };
-  auto tile_of = [&](int seq) {
-    Tile t{};
-    const long phys = (long)blockIdx.x + (long)seq * gridDim.x;
-    if (phys >= ntiles) return t;
-    const int bid = xcd_remap((int)phys, ntiles);
-    const int tm = bid / tiles_n, tn = bid % tiles_n;
-    t.valid = 1;
-    t.m0 = tm * BM;
-    t.n0 = tn * BN;
-    t.rows_a = min(BM, g.M - t.m0);
-    t.rows_b = min(BN, g.N - t.n0);
-    t.n_lo = CONV ? t.m0 / PQc : 0;
-    return t;
-  };
-  auto desc_a = [&](const Tile& t) {
-    return CONV ? rsrc_quad(g.A + t.n_lo * img,
-                            (uint32_t)(((t.m0 + t.rows_a - 1) / PQc - t.n_lo + 1) * img * 2))
-                : rsrc_quad(g.A + (long)t.m0 * g.lda,
-                            (uint32_t)((long)(t.rows_a - 1) * g.lda + g.K) * 2u);
-  };
-  auto desc_b = [&](const Tile& t) {
-    return rsrc_quad(g.B + (long)t.n0 * g.ldb,
-                     (uint32_t)((long)(t.rows_b - 1) * g.ldb + g.K) * 2u);
-  };
-  // per-lane source offset of a B (or dense A) piece instruction of tile t: element offset of
-  // (row, chunk) in bytes, or 2^31 (past every descriptor) for rows past the operand
-  auto boff = [&](const Tile& t, int pc, int j) {
-    const bool isA = pc == 0 || pc == 3;
-    const int row = prow(pc, j);
-    const int rows = isA ? t.rows_a : t.rows_b;
-    const int ld = isA ? g.lda : g.ldb;
-    return row < rows ? (uint32_t)(row * ld + pch) * 2u : 0x80000000u;
-  };
-  // CONV A piece instruction: the image base pixel and the packed top-left (h | w) of the
-  // receptive field of output row m0 + row (invalid rows: h far out of range)
-  auto ageom = [&](const Tile& t, int pc, int j, int& pix, int& hw) {
-    const int m = t.m0 + prow(pc, j);
-    const bool ok = m < g.M;
-    const int mm = ok ? m : t.m0;
-    const int q = mm % g.Q, tt = mm / g.Q;
-    const int p = tt % g.P, n = tt / g.P;
-    pix = (n - t.n_lo) * g.H * g.W;
-    hw = ((ok ? p * g.sh : 0x7000) << 16) | (q * g.sw);
-  };
-
-  Tile cur = tile_of(0);
-  if (!cur.valid) return;
-  // experiment (g.dbg = d > 0): start the blocks staggered by (block % 4) * d * ~3.4 us, so the
-  // CUs' epilogues (all 256 writing their 128-KB tiles in the same few microseconds when the
-  // blocks run in lockstep) spread out in time
-  for (int i = 0; i < (int)(blockIdx.x & 3) * g.dbg; ++i) __builtin_amdgcn_s_sleep(127);
-  int seq = 0;
-  bool nxt_valid = tile_of(1).valid;
-  i32x4_t ra = desc_a(cur), rb = desc_b(cur);
-  // CONV: the current tile's A-piece geometry (integer divisions), cached per tile
-  int apix[2][2], ahw[2][2];
-  auto cache = [&]() {
-    if constexpr (CONV) {
-#pragma unroll
-      for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) ageom(cur, a ? 3 : 0, j, apix[a][j], ahw[a][j]);
-    }
-  };
-  cache();
-  int gstep0 = 0;                                  // this block's steps before the current tile
-
-  auto dma_a_conv = [&](const i32x4_t& rA, int kk, bool live, int pix, int hw, uint32_t dst) {
-    const int cb = g.Cc / BK;
-    const int tap = kk / cb, c0 = (kk % cb) * BK;
-    const int h = (hw >> 16) + g.tdh[tap], w = (hw & 0xFFFF) + g.tdw[tap];
-    const bool ok = live && (unsigned)h < (unsigned)g.H && (unsigned)w < (unsigned)g.W;
-    dma16(rA, dst, ok ? (uint32_t)(((pix + h * g.W + w) * g.Cc + c0 + pch) * 2) : kGOOB);
-  };
-  auto dma_dense = [&](const i32x4_t& r, int kk, bool live, uint32_t off, uint32_t dst) {
-    const int k0 = kk * BK;
-    uint32_t o = off + (uint32_t)k0 * 2u;
-    if (!live || (ktail && k0 + pch >= g.K)) o = kGOOB;
-    dma16(r, dst, o);
-  };
-  // piece pc of step kt (relative to the current tile; kt >= nk: the next tile's step kt - nk)
-  auto issue_piece = [&](int kt, int pc) {
-    const uint32_t base = lds0 + (uint32_t)(((gstep0 + kt) & 1) * Cf::STAGE) * 2u;
-    const bool isA = pc == 0 || pc == 3;
-    if (kt < nk) {
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        if (CONV && isA)
-          dma_a_conv(ra, kt, true, apix[pc == 3][j], ahw[pc == 3][j], base + plds(pc, j));
-        else
-          dma_dense(isA ? ra : rb, kt, true, boff(cur, pc, j), base + plds(pc, j));
-      }
-      return;
-    }
-    const Tile t = nxt_valid ? tile_of(seq + 1) : cur;
-    const i32x4_t r = isA ? desc_a(t) : desc_b(t);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      if (CONV && isA) {
-        int pix, hw;
-        ageom(t, pc, j, pix, hw);
-        dma_a_conv(r, nxt_valid ? kt - nk : 0, nxt_valid, pix, hw, base + plds(pc, j));
-      } else {
-        dma_dense(r, nxt_valid ? kt - nk : 0, nxt_valid, boff(t, pc, j), base + plds(pc, j));
-      }
-    }
-  };
-
-  f32x4_t acc[Cf::FM][Cf::FN];
-#pragma unroll
-  for (int i = 0; i < Cf::FM; ++i)
-#pragma unroll
-    for (int j = 0; j < Cf::FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-
-  bf16x8_t fA[8], fBl[4], fBr[4];
-  auto rdA = [&](const bf16_t* sa, int half) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int r = wm * 128 + half * 64 + i * 16 + frow, ch = ks * 4 + fq;
-        fA[ks * 4 + i] = *reinterpret_cast<const bf16x8_t*>(sa + r * BK + gswz<BK>(r, ch) * 8);
-      }
-  };
-  auto rdB = [&](bf16x8_t* fb, const bf16_t* sa, int half) {
-    const bf16_t* sb = sa + Cf::SA;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int r = wn * 64 + half * 32 + j * 16 + frow, ch = ks * 4 + fq;
-        fb[ks * 2 + j] = *reinterpret_cast<const bf16x8_t*>(sb + r * BK + gswz<BK>(r, ch) * 8);
-      }
-  };
-  auto sync = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    raw_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto mfma_phase = [&](const bf16x8_t* fb, int ah, int bh) {
-    sync();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[ah * 4 + i][bh * 2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              fb[ks * 2 + j], fA[ks * 4 + i], acc[ah * 4 + i][bh * 2 + j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    sync();
-  };
-
-  float* red = reinterpret_cast<float*>(lds + 2 * Cf::STAGE);   // [WM][2][BN] past the ring
-  const bool do_stats = g.stats != nullptr;
-
-  // prologue of the first tile: step 0 whole + step 1's A-top / B-left
-  issue_piece(0, 0); issue_piece(0, 1); issue_piece(0, 2); issue_piece(0, 3);
-  issue_piece(1, 0); issue_piece(1, 1);
-  DTF_WAIT_VM(8);
-  bool first = true;
-  for (;; ++seq) {
-    sync();
-    if (wm == 1) sync();                       // the one-barrier stagger
-    for (int kt = 0; kt < nk; ++kt) {
-      const bf16_t* cur_lds = lds + ((gstep0 + kt) & 1) * Cf::STAGE;
-      rdB(fBl, cur_lds, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      rdA(cur_lds, 0);
-      issue_piece(kt + 1, 2);
-      // step 0 of every tile after the first: the previous tile's NSTORE = 32 stores were
-      // issued after the pieces this phase and the next need (younger than step 0's B-right /
-      // A-bottom: 3 pieces = 6 ops, the 32 stores, this step's 1 or 2 pieces = 2 / 4 ops -> 40)
-      if (!first && kt == 0) DTF_WAIT_VM(40); else DTF_WAIT_VM(8);
-      mfma_phase(fBl, 0, 0);                   // q0: top x left
-      rdB(fBr, cur_lds, 1);
-      issue_piece(kt + 1, 3);
-      if (!first && kt == 0) DTF_WAIT_VM(40); else DTF_WAIT_VM(8);
-      mfma_phase(fBr, 0, 1);                   // q1: top x right
-      rdA(cur_lds, 1);
-      issue_piece(kt + 2, 0);
-      DTF_WAIT_VM(8);
-      mfma_phase(fBr, 1, 1);                   // q2: bottom x right
-      issue_piece(kt + 2, 1);
-      DTF_WAIT_VM(8);
-      mfma_phase(fBl, 1, 0);                   // q3: bottom x left
-    }
-    if (wm == 0) sync();                       // re-align the barrier counts
-
-    // ---- epilogue: accumulators -> (+bias, ReLU, BN statistics, +Cin / masked acc) -> C
-    // lane (frow, fq) of fragment (i, j) holds C[m][n .. n + 3]: m = wm*128 + i*16 + frow,
-    // n = wn*64 + j*16 + fq*4
-    long cbase;
-    uint32_t cbytes;
-    if (strided) {
-      const int n_hi = (cur.m0 + cur.rows_a - 1) / PQc;
-      cbase = (long)cur.n_lo * g.Ho * g.Wo * g.ldc;
-      cbytes = (uint32_t)((long)(n_hi - cur.n_lo + 1) * g.Ho * g.Wo * g.ldc * 2);
-    } else {
-      cbase = (long)cur.m0 * g.ldc;
-      cbytes = (uint32_t)(((long)(cur.rows_a - 1) * g.ldc + g.N) * 2);
-    }
-    const __amdgpu_buffer_rsrc_t rc =
-        __builtin_amdgcn_make_buffer_rsrc(g.C + cbase, 0, (int)cbytes, 0x00020000);
-    const bool nt_store = g.nt != 0;      // non-temporal (aux bit 1)
-    long rowoff[Cf::FM];                       // element offset of row m (from cbase), -1: none
-#pragma unroll
-    for (int i = 0; i < Cf::FM; ++i) {
-      const int m = cur.m0 + wm * 128 + i * 16 + frow;
-      long o = -1;
-      if (m < g.M) {
-        if (strided) {
-          const int q = m % g.Q, t = m / g.Q;
-          const int p = t % g.P, n = t / g.P;
-          o = ((long)(n - cur.n_lo) * g.Ho + p * g.osh + g.oh0) * g.Wo + q * g.osw + g.ow0;
-          o *= g.ldc;
-        } else {
-          o = (long)(m - cur.m0) * g.ldc;
-        }
-      }
-      rowoff[i] = o;
-    }
-#pragma unroll
-    for (int j = 0; j < Cf::FN; ++j) {
-      const int ncol = cur.n0 + wn * 64 + j * 16 + fq * 4;
-      const bool col_ok = ncol < g.N;
-      float b4[4] = {0.f, 0.f, 0.f, 0.f};
-      if (g.bias && col_ok) {
-        const float4 bv = *reinterpret_cast<const float4*>(g.bias + ncol);
-        b4[0] = bv.x; b4[1] = bv.y; b4[2] = bv.z; b4[3] = bv.w;
-      }
-      float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int i = 0; i < Cf::FM; ++i) {
-        const bool ok = col_ok && rowoff[i] >= 0;
-        float v[4];
-        bf16_t h[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          v[r] = acc[i][j][r] + b4[r];
-          if (g.relu) v[r] = fmaxf(v[r], 0.f);
-          h[r] = f2bf(v[r]);
-          if (do_stats && ok) {
-            const float qv = bf2f(h[r]);
-            s1[r] += qv;
-            s2[r] += qv * qv;
-          }
-        }
-        const long eoff = rowoff[i] + ncol;    // element offset from cbase
-        if (ok && (g.Cin || g.acc_mask)) {
-          const bf16_t* src = g.Cin ? g.Cin + cbase + eoff : g.acc_src + cbase + eoff;
-          const uint2 sv = *reinterpret_cast<const uint2*>(src);
-          const uint32_t bits = g.Cin ? 0xFu
-                                      : (g.acc_mask[(cbase + eoff) >> 3] >> ((cbase + eoff) & 7)) & 0xFu;
-          const float s[4] = {__builtin_bit_cast(float, sv.x << 16),
-                              __builtin_bit_cast(float, sv.x & 0xffff0000u),
-                              __builtin_bit_cast(float, sv.y << 16),
-                              __builtin_bit_cast(float, sv.y & 0xffff0000u)};
-#pragma unroll
-          for (int r = 0; r < 4; ++r) h[r] = f2bf(bf2f(h[r]) + ((bits >> r) & 1u ? s[r] : 0.f));
-        }
-        typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-        const u32x2_t w = {(uint32_t)h[0] | ((uint32_t)h[1] << 16),
-                           (uint32_t)h[2] | ((uint32_t)h[3] << 16)};
-        const int so = ok ? (int)(eoff * 2) : (int)kGOOB;
-        if (nt_store) __builtin_amdgcn_raw_buffer_store_b64(w, rc, so, 0, 2);
-        else __builtin_amdgcn_raw_buffer_store_b64(w, rc, so, 0, 0);
-      }
-      if (do_stats) {
-        // column sums over the wave's 128 rows: the 16 lanes of a column group (frow) combine
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-#pragma unroll
-          for (int o = 1; o < 16; o <<= 1) {
-            s1[r] += __shfl_xor(s1[r], o, 64);
-            s2[r] += __shfl_xor(s2[r], o, 64);
-          }
-        }
-        if (frow == 0) {
-          const int col = wn * 64 + j * 16 + fq * 4;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            red[(wm * 2 + 0) * BN + col + r] = s1[r];
-            red[(wm * 2 + 1) * BN + col + r] = s2[r];
-          }
-        }
-      }
-    }
-    if (do_stats) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      raw_barrier();
-      if (tid < BN && cur.n0 + tid < g.N) {
-        float a = 0.f, b = 0.f;
-#pragma unroll
-        for (int k = 0; k < Cf::WM; ++k) { a += red[(k * 2 + 0) * BN + tid]; b += red[(k * 2 + 1) * BN + tid]; }
-        const int tm = cur.m0 / BM;
-        g.stats[((long)tm * 2 + 0) * g.N + cur.n0 + tid] = a;
-        g.stats[((long)tm * 2 + 1) * g.N + cur.n0 + tid] = b;
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      raw_barrier();                           // red is rewritten by the next tile
-    }
-    if (!nxt_valid) break;
-    // ---- next tile: its first pieces are in flight (issued by the last two K-steps)
-#pragma unroll
-    for (int i = 0; i < Cf::FM; ++i)
-#pragma unroll
-      for (int j = 0; j < Cf::FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    gstep0 += nk;
-    cur = tile_of(seq + 1);
-    nxt_valid = tile_of(seq + 2).valid;
-    ra = desc_a(cur);
-    rb = desc_b(cur);
-    cache();
-    first = false;
-    static_assert(NSTORE == 32, "the counted waits below assume 32 stores per lane per tile");
-    // step 0's A-top / B-left landed (waited by the last tile's final phase); the stores
-    // issued since are allowed to fly
-  }
-  DTF_WAIT_VM(0);       // the trailing look-ahead DMAs still target the ring
-}
-
-// ---------------------------------------------------------------------------------------------
-// Persistent ping-pong GEMM, round 5 (gemm_pp2_kernel): gemm_pp's design -- one block per CU
-// walking tiles, the LDS-DMA piece stream running ACROSS tiles so the next tile's first pieces
-// fly while this tile's outputs are stored straight from the registers -- with a main loop that
-// is instruction-for-instruction the per-tile SCHED 2 loop.  gemm_pp lost its main loop to the
-// cross-tile issue path (tile lookup, two per-tile buffer descriptors and the CONV receptive-field
-// geometry recomputed inside every look-ahead issue: SGPR spills on the ping-pong's critical
-// load sections, profiles/measurements/r2_gemm_epilogue_probes.jsonl p1/p4).  Here
+// Persistent ping-pong GEMM (gemm_pp2_kernel): one block per CU walking tiles (strided by the
+// grid), the LDS-DMA piece stream running ACROSS tiles -- the K loop's look-ahead issues of
+// "step nk, nk + 1" are the NEXT tile's steps 0 / 1, and the ring slot parity follows the block's
+// global step count -- so the next tile's first pieces fly while this tile's outputs are stored
+// straight from the registers (no LDS staging, no barrier), with a main loop that is
+// instruction-for-instruction the per-tile SCHED 2 loop.  Its round-3 predecessor (variant 11 in
+// the list at the top of this file) lost its main loop to the cross-tile issue path (tile lookup,
+// two per-tile buffer descriptors and the CONV receptive-field geometry recomputed inside every
+// look-ahead issue: SGPR spills on the ping-pong's critical load sections,
+// profiles/measurements/r2_gemm_epilogue_probes.jsonl p1/p4).  Here
 //   * the buffer descriptors span the WHOLE operands (host: < 2^31 bytes), built once;
 //   * every piece's per-lane source offset (dense) or image pixel / receptive-field corner (CONV)
 //     is computed ONCE per tile for the current AND the next tile; a look-ahead issue selects
@@ -1107,8 +699,9 @@ gemm_pp_kernel(const GemmArgs g) {
 //     distance, and tests the tap's validity bits (no division, table load or bounds test in
 //     the issue: profiles/CONV_GEMM_ISSUE.md);
 //   * K % 64 == 0 (no K-tail test in the issue).
-// The epilogue (bias / ReLU / BN statistics / Cin / masked acc, strided dgrad phases) and the
-// counted waits around the stores are gemm_pp's.
+// Every lane issues the same number of stores per tile (out-of-range ones carry an offset past
+// the C descriptor and are dropped by the hardware range check), so the counted vmcnt waits of
+// the next tile's first phases know exactly how many stores sit behind the pieces they need.
 // EPI bits (each instantiation carries only the epilogue operands it uses -- SGPR pressure):
 // 1 BN statistics, 2 accumulate (Cin / masked acc), 4 strided (dgrad phase) output rows,
 // 8 / 16 GELU forward / backward (below), 32 ReLU (a compile-time bit: as the runtime flag it
@@ -1118,7 +711,7 @@ gemm_pp_kernel(const GemmArgs g) {
 template <int CONV, int EPI, bool TAP0 = false>
 __global__ void __launch_bounds__(512, 1)
 gemm_pp2_kernel(const GemmArgs g) {
-  using Cf = GCfg<256, 256, 64, 2, 8>;
+  using Cf = GCfg<256, 256, 64, 2>;
   constexpr int BM = 256, BN = 256, BK = 64;
   constexpr int NSTORE = Cf::FM * Cf::FN;          // 8-B stores per lane per tile (32)
   extern __shared__ __attribute__((aligned(16))) bf16_t lds[];
@@ -1157,8 +750,8 @@ gemm_pp2_kernel(const GemmArgs g) {
     return (uint32_t)((isA ? 0 : Cf::SA) + (prow(pc, j) - lrow) * BK) * 2u;
   };
   // whole-operand descriptors (host: A / X and B below 2^31 bytes)
-  const i32x4_t ra = rsrc_quad(g.A, (uint32_t)g.ncu);          // ncu carries A's byte size here
-  const i32x4_t rb = rsrc_quad(g.B, (uint32_t)g.group_m);      // group_m carries B's byte size
+  const i32x4_t ra = rsrc_quad(g.A, (uint32_t)g.a_bytes);
+  const i32x4_t rb = rsrc_quad(g.B, (uint32_t)g.b_bytes);
 
   auto tile_mn = [&](int seq, int& m0, int& n0) {
     const long phys = (long)blockIdx.x + (long)seq * gridDim.x;
@@ -1392,7 +985,7 @@ gemm_pp2_kernel(const GemmArgs g) {
     }
     if (wm == 0) sync();
 
-    // ---- epilogue (gemm_pp's): lane (frow, fq) of fragment (i, j) holds C[m][n .. n + 3]
+    // ---- epilogue: lane (frow, fq) of fragment (i, j) holds C[m][n .. n + 3]
     const int n_lo = CONV ? cm0 / PQc : 0;
     const int rows_a = min(BM, g.M - cm0);
     long cbase;
@@ -1732,7 +1325,7 @@ gemm_pp2_kernel(const GemmArgs g) {
 
 template <int CONV, int EPI, bool TAP0 = false>
 void launch_gemm_pp2_t(const GemmArgs& g0, long a_bytes, long b_bytes, hipStream_t st) {
-  using Cf = GCfg<256, 256, 64, 2, 8>;
+  using Cf = GCfg<256, 256, 64, 2>;
   // + the strided epilogue's per-wave row tables (8 waves x 128 ints)
   constexpr size_t LDS = (size_t)2 * Cf::STAGE * 2 + (size_t)Cf::WM * 2 * 256 * 4 +
                          ((EPI & 4) ? (size_t)8 * 128 * 4 : 0);
@@ -1755,8 +1348,8 @@ void launch_gemm_pp2_t(const GemmArgs& g0, long a_bytes, long b_bytes, hipStream
       g0.K % 64 || g0.K < 128)
     throw std::runtime_error("gemm_pp2: operands below 2^31 bytes, K % 64 == 0, K >= 128");
   GemmArgs g = g0;
-  g.ncu = (int)a_bytes;        // the whole-operand descriptor sizes ride in these two fields
-  g.group_m = (int)b_bytes;
+  g.a_bytes = (int)a_bytes;
+  g.b_bytes = (int)b_bytes;
   const long tiles = (long)((g.M + 255) / 256) * ((g.N + 255) / 256);
   long grid = tiles < ncu ? tiles : (ncu / 8) * 8;
   if (grid < 1) grid = 1;
@@ -1794,10 +1387,14 @@ void launch_gemm_pp2(const GemmArgs& g, long a_bytes, long b_bytes, hipStream_t 
       return;
     }
   }
-  if (strided) {
-    if (acc) launch_gemm_pp2_e<CONV, 6>(g, a_bytes, b_bytes, st);
-    else launch_gemm_pp2_e<CONV, 4>(g, a_bytes, b_bytes, st);
-  } else if (stats) {
+  if constexpr (CONV) {
+    if (strided) {
+      if (acc) launch_gemm_pp2_e<CONV, 6>(g, a_bytes, b_bytes, st);
+      else launch_gemm_pp2_e<CONV, 4>(g, a_bytes, b_bytes, st);
+      return;
+    }
+  }
+  if (stats) {
     launch_gemm_pp2_e<CONV, 1>(g, a_bytes, b_bytes, st);
   } else if (acc) {
     launch_gemm_pp2_e<CONV, 2>(g, a_bytes, b_bytes, st);
@@ -1806,35 +1403,6 @@ void launch_gemm_pp2(const GemmArgs& g, long a_bytes, long b_bytes, hipStream_t 
   }
 }
 
-template <int CONV>
-void launch_gemm_pp(const GemmArgs& g, hipStream_t st) {
-  using Cf = GCfg<256, 256, 64, 2, 8>;
-  constexpr size_t LDS = (size_t)2 * Cf::STAGE * 2 + (size_t)Cf::WM * 2 * 256 * 4;
-  static bool attr = false;
-  static int ncu = 0;
-  if (!attr) {
-    HIP_CHECK(hipFuncSetAttribute((const void*)gemm_pp_kernel<CONV>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS));
-    // scratch (spilled VGPRs) would be vector-memory traffic the counted vmcnt waits do not
-    // know about: refuse to run such a build instead of racing on the LDS ring
-    hipFuncAttributes fa{};
-    HIP_CHECK(hipFuncGetAttributes(&fa, (const void*)gemm_pp_kernel<CONV>));
-    if (fa.localSizeBytes > 0)
-      throw std::runtime_error("gemm_pp_kernel was compiled with register spills (scratch " +
-                               std::to_string(fa.localSizeBytes) + " B/lane)");
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-    attr = true;
-  }
-  const long tiles = (long)((g.M + 255) / 256) * ((g.N + 255) / 256);
-  // one block per CU; a multiple of 8 (whole XCDs) so tile t, t + grid, ... stay on one XCD
-  long grid = tiles < ncu ? tiles : (ncu / 8) * 8;
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL((gemm_pp_kernel<CONV>), dim3((unsigned)grid), dim3(Cf::NT), LDS, st, g);
-}
-
-int g_gemm_pp = 0;         // bit 0: persistent register-epilogue kernel for gemm_nt, bit 1: convs
 // round-5 persistent kernel (gemm_pp2): bit 0 gemm_nt (0.92-1.05x hipBLASLt on the BERT shapes,
 // profiles/measurements/r5_gemm_pp2_interleaved_epilogue_vs_v8.jsonl; ResNet-50 +0.6 %), bit 1 the
 // unit-stride implicit-GEMM convs (2-5 % per layer, r5_conv_pp2_per_layer_b1984.jsonl)
@@ -1845,56 +1413,73 @@ int g_gemm_pp2 = 3;
 int g_gemm_pp2_strided = 1;
 int g_gemm_stream = 1;     // output-heavy shapes on the row-streaming kernel (gemm_stream.hip)
 
-int g_gemm_variant = -1;   // -1: auto; 0..3: force (tools/gemm_bench.py A/B)
+int g_gemm_variant = -1;   // -1: auto, or one of 0, 1, 8, 10, 13, 15 (dtf_gemm_set_variant)
 // non-temporal C stores: on since the persistent kernel's full-line stores (BERT-base b512 +1.1 %,
 // profiles/measurements/r5_bert_gemm_nt_stores.jsonl); ResNet-50 A/B neutral in round 2
 int g_gemm_nt = 1;
 int g_gemm_dbg = 0;        // GemmArgs::dbg for timing probes
-
-int g_gemm_stagger_mode = 1, g_gemm_stagger = -1;   // OCC 2 start stagger (-1: auto)
 int g_gemm_group = 0;      // grouped tile order (GemmArgs::group_m) for the non-conv GEMMs
 
-template <int BM, int BN, int BK, int NS, int SCHED = 0, int NW = 8, int PP_PRIO = 1,
-          int CONV = 0, int OCC = 1>
+template <int BM, int BN, int BK, int NS, int SCHED = 0, int CONV = 0>
 void launch_gemm(const GemmArgs& g0, hipStream_t st) {
-  using Cf = GCfg<BM, BN, BK, NS, NW>;
+  using Cf = GCfg<BM, BN, BK, NS>;
   static bool attr = false;
-  static int ncu = 0;
   if (!attr) {
-    HIP_CHECK(hipFuncSetAttribute(
-        (const void*)gemm_nt_kernel<BM, BN, BK, NS, SCHED, NW, PP_PRIO, CONV, OCC>,
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::LDS));
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    HIP_CHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+    HIP_CHECK(hipFuncSetAttribute((const void*)gemm_nt_kernel<BM, BN, BK, NS, SCHED, CONV>,
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cf::LDS));
     attr = true;
   }
-  static_assert(OCC == 1 || 2 * Cf::LDS <= 160 * 1024, "OCC 2: two blocks' LDS per CU");
   GemmArgs g = g0;
   if (!CONV) g.group_m = g_gemm_group;
   const long tiles = (long)((g.M + BM - 1) / BM) * ((g.N + BN - 1) / BN);
-  if (OCC == 2) {
-    g.ncu = ncu;
-    g.stagger_mode = tiles > ncu ? g_gemm_stagger_mode : 0;
-    // about half a tile: ~0.9 us per 32-deep K-step of a 256 x 128 tile with two blocks per
-    // CU; one s_sleep 127 is 8128 cycles (~3.4 us at 2.4 GHz)
-    g.stagger = g_gemm_stagger >= 0 ? g_gemm_stagger : ((g.K + BK - 1) / BK + 7) / 8;
+  hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, BK, NS, SCHED, CONV>), dim3((unsigned)tiles),
+                     dim3(Cf::NT), Cf::LDS, st, g);
+}
+
+// the dense entry points' per-block descriptors span at most one 256-row panel
+void check_dense_ld(const char* who, int K, int lda, int ldb) {
+  if ((long)256 * lda * 2 + 2L * K >= (1L << 31) || (long)256 * ldb * 2 + 2L * K >= (1L << 31))
+    throw std::runtime_error(std::string(who) + ": leading dimension too large");
+}
+
+// The dense entry points' route.  variant -1 (auto): 256 x 128 tiles when N <= 128 (measured
+// 1.02-1.07x the 256 x 256 tile on the N = 128 ResNet 1x1 convs,
+// profiles/measurements/r2_gemm_vs_conv_resnet1x1_b1280.jsonl), else the persistent kernel when
+// it takes the shape and the entry's epilogue (pp2_epi), else the ping-pong; 0 / 1 / 8 / 10 / 15
+// force one (0 and 10: the tests' reference schedules, see the top of this file).
+void launch_dense(const char* who, const GemmArgs& g, int variant, bool pp2_epi, hipStream_t st) {
+  const bool pp2_ok = dtf_gemm_pp2_ok(g.M, g.N, g.K, g.lda, g.ldb) && pp2_epi;
+  if (variant < 0) variant = g.N <= 128 ? 1 : (g_gemm_pp2 & 1) && pp2_ok ? 15 : 8;
+  switch (variant) {
+    case 0: launch_gemm<256, 256, 64, 2>(g, st); break;
+    case 1: launch_gemm<256, 128, 64, 3>(g, st); break;
+    case 10: launch_gemm<256, 128, 64, 3, 3>(g, st); break;
+    case 8: launch_gemm<256, 256, 64, 2, 2>(g, st); break;
+    case 15:
+      if (!pp2_ok)
+        throw std::runtime_error(std::string(who) +
+                                 ": shape not supported by the persistent kernel (variant 15)");
+      launch_gemm_pp2<0>(g, (long)(g.M - 1) * g.lda * 2 + 2L * g.K,
+                         (long)(g.N - 1) * g.ldb * 2 + 2L * g.K, st);
+      break;
   }
-  hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, BK, NS, SCHED, NW, PP_PRIO, CONV, OCC>),
-                     dim3((unsigned)tiles), dim3(Cf::NT), Cf::LDS, st, g);
 }
 
 }  // namespace
 
-void dtf_gemm_set_variant(int v) { g_gemm_variant = v; }
+void dtf_gemm_set_variant(int v) {
+  if (v != -1 && v != 0 && v != 1 && v != 8 && v != 10 && v != 13 && v != 15)
+    throw std::runtime_error("gemm_set_variant: " + std::to_string(v) + " is no variant; -1 "
+                             "(auto), 1 (256 x 128), 8 (ping-pong), 13 (row-streaming), 15 "
+                             "(persistent), or the tests' references 0 and 10");
+  g_gemm_variant = v;
+}
 void dtf_gemm_set_stream(int v) { g_gemm_stream = v; }
-void dtf_gemm_set_pp(int v) { g_gemm_pp = v; }
 void dtf_gemm_set_pp2(int v) { g_gemm_pp2 = v; }
 void dtf_gemm_set_pp2_strided(int v) { g_gemm_pp2_strided = v; }
 int dtf_gemm_get_pp2() { return g_gemm_pp2; }
 void dtf_gemm_set_nt(int v) { g_gemm_nt = v; }
 void dtf_gemm_set_dbg(int v) { g_gemm_dbg = v; }
-void dtf_gemm_set_stagger(int mode, int iters) { g_gemm_stagger_mode = mode; g_gemm_stagger = iters; }
 void dtf_gemm_set_group(int gm) { g_gemm_group = gm < 0 ? 0 : gm; }
 
 // Implicit-GEMM convolution on the ping-pong GEMM: Y[M = N*P*Q][Kout] (+= Cin / masked acc)
@@ -1965,17 +1550,17 @@ void dtf_gemm_conv(const bf16_t* X, const bf16_t* Wt, bf16_t* Y, int N, int H, i
     }
     return;
   }
-  if (Kout <= 128) launch_gemm<256, 128, 64, 3, 3, 8, 1, 1>(g, st);
-  // the persistent kernel for the unit-stride output launches only: its strided (dgrad phase)
-  // epilogue is the swapped 32-B piece one -- 1.2-1.5x slower than the ping-pong's on the
-  // stride-2 data gradients, while the unit-stride convs gain 2-5 %
-  // (profiles/measurements/r5_conv_pp2_per_layer_b1984.jsonl)
+  if (Kout <= 128) launch_gemm<256, 128, 64, 3, 3, 1>(g, st);
+  // the persistent kernel where it takes the launch (whole operands and the strided phases' image
+  // span below 2^31 bytes, taps within 8 of each other): the unit-stride convs gain 2-5 % on it
+  // (profiles/measurements/r5_conv_pp2_per_layer_b1984.jsonl), and the strided data-gradient
+  // phases run on it too since their rows go through the epilogue's LDS row table
+  // (g_gemm_pp2_strided)
   else if ((g_gemm_pp2 & 2) && (g_gemm_pp2_strided || (osh == 1 && osw == 1)) && g.K >= 128 &&
            x_bytes < 0x7FFFFF00L && w_bytes < 0x7FFFFF00L && N < 2048 && H < 1000 && W < 1000 &&
            pp_span && tap_span)
     launch_gemm_pp2<1>(g, x_bytes, w_bytes, st);
-  else if ((g_gemm_pp & 2) && (g.K + 63) / 64 >= 2 && pp_span) launch_gemm_pp<1>(g, st);
-  else launch_gemm<256, 256, 64, 2, 2, 8, 1, 1>(g, st);
+  else launch_gemm<256, 256, 64, 2, 2, 1>(g, st);
 }
 
 // dX = dY . W (gemm_nt form, B = W^T rows) for a data gradient that feeds a GELU: the epilogue
@@ -1987,16 +1572,12 @@ void dtf_gemm_nt_gelu_bwd(const bf16_t* A, const bf16_t* B, bf16_t* C, int M, in
   if (M <= 0 || N <= 0 || K <= 0) return;
   if (K % 8 || N % 8 || lda % 8 || ldb % 8 || lda < K || ldb < K || !gelu_a || !colsum)
     throw std::runtime_error("gemm_nt_gelu_bwd: K, N, leading dims % 8; gelu_a and colsum needed");
-  if ((long)256 * lda * 2 + 2L * K >= (1L << 31) || (long)256 * ldb * 2 + 2L * K >= (1L << 31))
-    throw std::runtime_error("gemm_nt_gelu_bwd: leading dimension too large");
+  check_dense_ld("gemm_nt_gelu_bwd", K, lda, ldb);
   GemmArgs g{};
   g.A = A; g.B = B; g.C = C; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = N;
   g.gelu_a = gelu_a; g.gelu_b = gelu_b; g.colsum = colsum;
   g.nt = g_gemm_nt;
-  if (N <= 128) launch_gemm<256, 128, 64, 3>(g, st);
-  else if ((g_gemm_pp2 & 1) && dtf_gemm_pp2_ok(M, N, K, lda, ldb) && N % 4 == 0)
-    launch_gemm_pp2<0>(g, (long)(M - 1) * lda * 2 + 2L * K, (long)(N - 1) * ldb * 2 + 2L * K, st);
-  else launch_gemm<256, 256, 64, 2, 2>(g, st);
+  launch_dense("gemm_nt_gelu_bwd", g, -1, true, st);
 }
 
 // Z = A . B^T + bias (bf16) and H = gelu(Z) in one pass (BERT's first FFN GEMM: replaces a
@@ -2006,16 +1587,12 @@ void dtf_gemm_nt_bias_gelu(const bf16_t* A, const bf16_t* B, bf16_t* Z, bf16_t* 
   if (M <= 0 || N <= 0 || K <= 0) return;
   if (K % 8 || N % 8 || lda % 8 || ldb % 8 || lda < K || ldb < K || !bias || !H)
     throw std::runtime_error("gemm_nt_bias_gelu: K, N, leading dims % 8; bias and H needed");
-  if ((long)256 * lda * 2 + 2L * K >= (1L << 31) || (long)256 * ldb * 2 + 2L * K >= (1L << 31))
-    throw std::runtime_error("gemm_nt_bias_gelu: leading dimension too large");
+  check_dense_ld("gemm_nt_bias_gelu", K, lda, ldb);
   GemmArgs g{};
   g.A = A; g.B = B; g.C = Z; g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = N;
   g.bias = bias; g.gelu_out = H;
   g.nt = g_gemm_nt;
-  if (N <= 128) launch_gemm<256, 128, 64, 3>(g, st);
-  else if ((g_gemm_pp2 & 1) && dtf_gemm_pp2_ok(M, N, K, lda, ldb) && N % 4 == 0)
-    launch_gemm_pp2<0>(g, (long)(M - 1) * lda * 2 + 2L * K, (long)(N - 1) * ldb * 2 + 2L * K, st);
-  else launch_gemm<256, 256, 64, 2, 2>(g, st);
+  launch_dense("gemm_nt_bias_gelu", g, -1, true, st);
 }
 
 // the persistent kernel gemm_pp2 takes this dense GEMM: K % 64 == 0, K >= 128, whole operands
@@ -2034,9 +1611,7 @@ void dtf_gemm_nt(const bf16_t* A, const bf16_t* B, bf16_t* C, int M, int N, int 
   if (M <= 0 || N <= 0 || K <= 0) return;
   if (K % 8 || N % 8 || lda % 8 || ldb % 8 || ldc % 8 || lda < K || ldb < K || ldc < N)
     throw std::runtime_error("gemm_nt: K, N and the leading dimensions must be multiples of 8");
-  // the per-block descriptors span at most one 256-row panel
-  if ((long)256 * lda * 2 + 2L * K >= (1L << 31) || (long)256 * ldb * 2 + 2L * K >= (1L << 31))
-    throw std::runtime_error("gemm_nt: leading dimension too large");
+  check_dense_ld("gemm_nt", K, lda, ldb);
   if (stats && (bias || relu || Cin))
     throw std::runtime_error("gemm_nt: BN statistics epilogue excludes bias / ReLU / accumulate");
   if (acc_mask && (!acc_src || Cin || ldc != N))
@@ -2053,33 +1628,5 @@ void dtf_gemm_nt(const bf16_t* A, const bf16_t* B, bf16_t* C, int M, int N, int 
   GemmArgs g{A, B, C, bias, Cin, M, N, K, lda, ldb, ldc, relu, stats, acc_src, acc_mask};
   g.nt = g_gemm_nt;
   g.dbg = g_gemm_dbg;
-  // auto: 256 x 128 tiles when N <= 128 (measured 1.02-1.07x the 256 x 256 tile on the N = 128
-  // ResNet 1x1 convs, profiles/measurements/r2_gemm_vs_conv_resnet1x1_b1280.jsonl)
-  const int variant = g_gemm_variant >= 0 ? g_gemm_variant
-                    : (N <= 128 ? 1
-                       : (g_gemm_pp2 & 1) && dtf_gemm_pp2_ok(M, N, K, lda, ldb) &&
-                                 !(stats && (bias || relu)) ? 15
-                       : ((g_gemm_pp & 1) && (K + 63) / 64 >= 2 ? 11 : 8));
-  if (variant == 11 && (K + 63) / 64 < 2)
-    throw std::runtime_error("gemm_nt: the persistent kernel needs K > 64");
-  if (variant == 15 && (!dtf_gemm_pp2_ok(M, N, K, lda, ldb) || (stats && (bias || relu))))
-    throw std::runtime_error("gemm_nt: shape not supported by the persistent kernel (variant 15)");
-  switch (variant) {
-    case 11: launch_gemm_pp<0>(g, st); break;
-    case 15:
-      launch_gemm_pp2<0>(g, (long)(M - 1) * lda * 2 + 2L * K, (long)(N - 1) * ldb * 2 + 2L * K, st);
-      break;
-    case 1: launch_gemm<256, 128, 64, 3>(g, st); break;
-    case 2: launch_gemm<256, 256, 32, 4>(g, st); break;
-    case 3: launch_gemm<256, 128, 32, 4>(g, st); break;
-    case 4: launch_gemm<256, 256, 64, 2, 1>(g, st); break;
-    case 5: launch_gemm<256, 256, 64, 2, 0, 4>(g, st); break;
-    case 6: launch_gemm<256, 256, 64, 2, 1, 4>(g, st); break;
-    case 7: launch_gemm<256, 256, 32, 4, 0, 4>(g, st); break;
-    case 8: launch_gemm<256, 256, 64, 2, 2>(g, st); break;
-    case 9: launch_gemm<256, 256, 64, 2, 2, 8, 0>(g, st); break;
-    case 10: launch_gemm<256, 128, 64, 3, 3>(g, st); break;
-    case 12: launch_gemm<256, 128, 32, 3, 0, 4, 1, 0, 2>(g, st); break;
-    default: launch_gemm<256, 256, 64, 2>(g, st); break;
-  }
+  launch_dense("gemm_nt", g, g_gemm_variant, !(stats && (bias || relu)), st);
 }

@@ -200,13 +200,11 @@ void dtf_conv1x1_bwd_lazy(const bf16_t* dy3, const bf16_t* x3, const uint8_t* ma
 // ---- gemm.hip
 void dtf_gemm_set_variant(int v);
 void dtf_gemm_set_stream(int v);
-void dtf_gemm_set_pp(int v);
 void dtf_gemm_set_pp2(int v);
 void dtf_gemm_set_pp2_strided(int v);
 int dtf_gemm_get_pp2();
 void dtf_gemm_set_nt(int v);
 void dtf_gemm_set_dbg(int v);
-void dtf_gemm_set_stagger(int mode, int iters);
 void dtf_gemm_set_group(int gm);
 int dtf_gemm_conv_part_images(int N, int H, int W, int C, int P, int Q);
 void dtf_gemm_conv(const bf16_t* X, const bf16_t* Wt, bf16_t* Y, int N, int H, int W, int C, int P,

@@ -80,6 +80,22 @@ def test_default_build_has_no_probes():
                                                  "native.py")))
 
 
+def test_gemm_set_variant_refuses_unknown_ids():
+    """A forced GEMM variant is checked when it is set: the ids of deleted kernels and unknown
+    ones raise and name the accepted ones (no launch needed).  0 and 10 stay accepted: they are
+    the reference schedules of tests/test_dense_gpu.py."""
+    pytest.importorskip("distributedtensorflow_amd._lib._dtf_hip")
+    from distributedtensorflow_amd._lib import _dtf_hip as K
+    try:
+        for v in (2, 3, 4, 5, 6, 7, 9, 11, 12, 14, 99):
+            with pytest.raises(RuntimeError, match=r"-1 .*1 .*8 .*13 .*15"):
+                K.gemm_set_variant(v)
+        for v in (-1, 0, 1, 8, 10, 13, 15):
+            K.gemm_set_variant(v)
+    finally:
+        K.gemm_set_variant(-1)
+
+
 def test_dtf_env_recorded(monkeypatch):
     from distributedtensorflow_amd.utils import dtf_env
     for k in list(os.environ):

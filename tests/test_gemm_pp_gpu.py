@@ -1,19 +1,19 @@
-"""The persistent register-epilogue GEMM (csrc/kernels/gemm.hip gemm_pp_kernel, variant 11) and
-the two-blocks-per-CU 256 x 128 kernel (gemm_nt_kernel OCC 2, variant 12) against the round-2
-ping-pong kernel (variant 8) and an fp32 reference.
+"""The persistent ping-pong GEMM (csrc/kernels/gemm.hip gemm_pp2_kernel, variant 15) and the route
+the dispatcher takes on its own (variant -1) against the per-tile ping-pong kernel (variant 8) and
+an fp32 reference.
 
-Variant 12 runs 32-deep K-steps instead of 64-deep ones, but every accumulator still sees the
-same MFMA sequence (k = 0..31, 32..63, ... in order) and the same two-wave-row statistics
-combine, so it is held to the same bit-identity (and is run with its start stagger on).
-
-The new kernel runs the same main loop with the MFMA operands swapped (each lane then holds four
-consecutive output columns) and stores straight from the accumulators, with the LDS-DMA stream
-continuing across the tiles a persistent block walks.  Per output element the products and
-their accumulation order are unchanged, so C must be BIT-IDENTICAL to variant 8 for every
-epilogue mode (bias, ReLU, beta = 1 accumulate, masked residual accumulate); the BatchNorm
-partial sums (a different summation order) must agree to fp32 rounding.  Shapes cover edge
-tiles in M and N, a K tail, K = 128 (two steps: every look-ahead piece belongs to the next
-tile) and more tiles than CUs (several tiles per block).
+The persistent kernel runs variant 8's main loop and stores straight from the accumulators, with
+the LDS-DMA stream continuing across the tiles a persistent block walks.  Per output element the
+products and their accumulation order are unchanged, so C must be BIT-IDENTICAL to variant 8 for
+every epilogue mode (plain, bias + ReLU, beta = 1 accumulate, bias + ReLU + accumulate, masked
+residual accumulate); the BatchNorm partial sums (a different summation order) must agree to fp32
+rounding.  The same holds for whatever kernel the auto route picks: the persistent kernel where
+it takes the shape, variant 8 itself on the K tails.  (None of these shapes goes to the
+row-streaming kernel, variant 13, which takes K in {64, 128, 256} with N % 64 == 0 only: K = 128
+comes with N = 264 here.  tests/test_gemm_stream_gpu.py holds that kernel to variant 8.)  Variant
+8 is held to the fp32 product on every shape.  Shapes cover edge tiles in M and N, a K tail,
+K = 128 (two steps: every look-ahead piece belongs to the next tile) and more tiles than CUs
+(several tiles per block).
 """
 import pytest
 import torch
@@ -46,9 +46,7 @@ def _need_gpu():
         pytest.skip("needs a GPU")
 
 
-@pytest.mark.parametrize("variant", [11, 12])
-@pytest.mark.parametrize("M,N,K", SHAPES)
-def test_pp_matches_pingpong_bitwise(M, N, K, variant):
+def _check_matches_pingpong(M, N, K, variant):
     n = _native()
     g = torch.Generator(device="cuda").manual_seed(M + N + K)
     a = torch.randn(M, K, device="cuda", generator=g).bfloat16()
@@ -58,24 +56,29 @@ def test_pp_matches_pingpong_bitwise(M, N, K, variant):
     out = _run(variant, lambda: n.gemm_nt(a, b))
     assert torch.equal(out, ref8)
     exact = a.float() @ b.float().t()
-    err = ((out.float() - exact).norm() / exact.norm()).item()
+    err = ((ref8.float() - exact).norm() / exact.norm()).item()
     assert err < 5e-3, err
     r8 = _run(8, lambda: n.gemm_nt(a, b, bias=bias, relu=True))
-    r11 = _run(variant, lambda: n.gemm_nt(a, b, bias=bias, relu=True))
-    assert torch.equal(r11, r8)
+    rv = _run(variant, lambda: n.gemm_nt(a, b, bias=bias, relu=True))
+    assert torch.equal(rv, r8)
     cin = torch.randn(M, N, device="cuda", generator=g).bfloat16()
     c8 = _run(8, lambda: n.gemm_nt(a, b, cin=cin.clone()))
-    c11 = _run(variant, lambda: n.gemm_nt(a, b, cin=cin.clone()))
-    assert torch.equal(c11, c8)
+    cv = _run(variant, lambda: n.gemm_nt(a, b, cin=cin.clone()))
+    assert torch.equal(cv, c8)
     # bias + ReLU + accumulate (the persistent kernel's compile-time ReLU on the accumulate form)
     cr8 = _run(8, lambda: n.gemm_nt(a, b, bias=bias, relu=True, cin=cin.clone()))
     cr = _run(variant, lambda: n.gemm_nt(a, b, bias=bias, relu=True, cin=cin.clone()))
     assert torch.equal(cr, cr8)
 
 
-@pytest.mark.parametrize("variant", [11, 12])
-@pytest.mark.parametrize("M,N,K", [(4096, 768, 768), (1000, 520, 200), (256 * 300, 512, 512)])
-def test_pp_masked_accumulate_and_bn_stats(M, N, K, variant):
+@pytest.mark.parametrize("M,N,K", SHAPES)
+def test_pp_matches_pingpong_bitwise(M, N, K):
+    """Variant 8 against the fp32 product, and the auto route bit-identical to variant 8 for the
+    four epilogue forms, on every shape (the K tails included)."""
+    _check_matches_pingpong(M, N, K, -1)
+
+
+def _check_masked_accumulate_and_bn_stats(M, N, K, variant):
     n = _native()
     g = torch.Generator(device="cuda").manual_seed(7)
     a = torch.randn(M, K, device="cuda", generator=g).bfloat16()
@@ -84,18 +87,23 @@ def test_pp_masked_accumulate_and_bn_stats(M, N, K, variant):
     mask = torch.randint(0, 256, (M * N // 8,), device="cuda", dtype=torch.uint8, generator=g)
     acc = n._MaskedGrad(dy, mask)
     m8 = _run(8, lambda: n.gemm_nt(a, b, acc_from=acc))
-    m11 = _run(variant, lambda: n.gemm_nt(a, b, acc_from=acc))
-    assert torch.equal(m11, m8)
+    mv = _run(variant, lambda: n.gemm_nt(a, b, acc_from=acc))
+    assert torch.equal(mv, m8)
     tiles = n._K.gemm_tile_rows(M)
     s8 = torch.zeros(tiles, 2, N, device="cuda")
-    s11 = torch.zeros(tiles, 2, N, device="cuda")
+    sv = torch.zeros(tiles, 2, N, device="cuda")
     y8 = _run(8, lambda: n.gemm_nt(a, b, stats=s8))
-    y11 = _run(variant, lambda: n.gemm_nt(a, b, stats=s11))
-    assert torch.equal(y11, y8)
-    torch.testing.assert_close(s11, s8, rtol=1e-5, atol=1e-3)
+    yv = _run(variant, lambda: n.gemm_nt(a, b, stats=sv))
+    assert torch.equal(yv, y8)
+    torch.testing.assert_close(sv, s8, rtol=1e-5, atol=1e-3)
     yf = y8.float()
-    torch.testing.assert_close(s11[:, 0].sum(0), yf.sum(0), rtol=1e-4, atol=1e-2)
-    torch.testing.assert_close(s11[:, 1].sum(0), (yf * yf).sum(0), rtol=1e-4, atol=1e-1)
+    torch.testing.assert_close(sv[:, 0].sum(0), yf.sum(0), rtol=1e-4, atol=1e-2)
+    torch.testing.assert_close(sv[:, 1].sum(0), (yf * yf).sum(0), rtol=1e-4, atol=1e-1)
+
+
+@pytest.mark.parametrize("M,N,K", [(4096, 768, 768), (1000, 520, 200), (256 * 300, 512, 512)])
+def test_pp_masked_accumulate_and_bn_stats(M, N, K):
+    _check_masked_accumulate_and_bn_stats(M, N, K, -1)
 
 
 PP2_SHAPES = [s for s in SHAPES if s[2] % 64 == 0 and s[2] >= 128] + [(65536, 768, 3072)]
@@ -103,12 +111,12 @@ PP2_SHAPES = [s for s in SHAPES if s[2] % 64 == 0 and s[2] >= 128] + [(65536, 76
 
 @pytest.mark.parametrize("M,N,K", PP2_SHAPES)
 def test_pp2_matches_pingpong_bitwise(M, N, K):
-    """Round 5's persistent kernel (variant 15: whole-operand descriptors, per-tile piece offsets
+    """The persistent kernel (variant 15: whole-operand descriptors, per-tile piece offsets
     computed once for the current and the next tile) -- the same MFMA sequence per output element
     as variant 8, so bit-identical for every epilogue mode, and the BN partial sums to rounding."""
-    test_pp_matches_pingpong_bitwise(M, N, K, 15)
+    _check_matches_pingpong(M, N, K, 15)
     if K in (768, 512):
-        test_pp_masked_accumulate_and_bn_stats(M, N, K, 15)
+        _check_masked_accumulate_and_bn_stats(M, N, K, 15)
 
 
 def test_pp2_refuses_unsupported_shapes():

@@ -54,14 +54,14 @@ def main():
     ap.add_argument("--resnet1x1", type=int, default=0,
                     help="batch: time the ResNet-50 1x1 convs as GEMMs next to the conv kernel")
     ap.add_argument("--dbg", default="0",
-                    help="comma list of gemm_set_dbg values to time (kernel experiments)")
-    ap.add_argument("--variants", default="0",
-                    help="comma list of gemm.hip pipeline variants to time (gemm_set_variant)")
+                    help="comma list of gemm_set_dbg values to time; 1 is a wrong-result timing "
+                         "probe (gemm_nt_kernel, variants 1 and 8, without its epilogue)")
+    ap.add_argument("--variants", default="-1",
+                    help="comma list of gemm_set_variant ids to time: -1 auto, 1 256 x 128, "
+                         "8 ping-pong, 13 row-streaming, 15 persistent (0 / 10: the tests' "
+                         "reference schedules)")
     ap.add_argument("--shapes", default=None,
                     help="extra comma list of MxNxK GEMM shapes (e.g. 388864x1024x256)")
-    ap.add_argument("--stagger", default="1:-1",
-                    help="comma list of mode:iters start staggers for the OCC-2 variant 12 "
-                         "(gemm_set_stagger; -1 iters = auto)")
     a = ap.parse_args()
     rows = []
     if a.resnet1x1:
@@ -124,17 +124,15 @@ def main():
         err_lib = float((ref[sub].float() - exact).norm() / exact.norm())
         t_lib = timeit(lambda: torch.nn.functional.linear(A, B), a.iters)
         fl = 2.0 * M * N * K
-        combos = [(int(x), int(y), st) for x in a.variants.split(",") for y in a.dbg.split(",")
-                  for st in (a.stagger.split(",") if int(x) == 12 else ["1:-1"])]
-        for v, d, st in combos:
+        combos = [(int(x), int(y)) for x in a.variants.split(",") for y in a.dbg.split(",")]
+        for v, d in combos:
             native._K.gemm_set_variant(v)
             native._K.gemm_set_dbg(d)
-            native._K.gemm_set_stagger(*[int(t) for t in st.split(":")])
             ours = native.gemm_nt(A, B)
             err = float((ours[sub].float() - exact).norm() / exact.norm())
             t_ours = timeit(lambda: native.gemm_nt(A, B), a.iters)
             native._K.gemm_set_dbg(0)
-            row = {"shape": name, "variant": v, "dbg": d, "stagger": st, "M": M, "N": N, "K": K,
+            row = {"shape": name, "variant": v, "dbg": d, "M": M, "N": N, "K": K,
                    "ours_us": round(t_ours * 1e6, 1), "hipblaslt_us": round(t_lib * 1e6, 1),
                    "ours_tflops": round(fl / t_ours / 1e12, 1),
                    "hipblaslt_tflops": round(fl / t_lib / 1e12, 1),
@@ -143,7 +141,6 @@ def main():
             rows.append(row)
             print(json.dumps(row), flush=True)
         native._K.gemm_set_variant(-1)
-        native._K.gemm_set_stagger(1, -1)
         del A, B, ours, ref
         torch.cuda.empty_cache()
     if a.out:

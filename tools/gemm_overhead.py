@@ -1,10 +1,12 @@
 """Per-tile fixed cost of the MFMA GEMM (csrc/kernels/gemm.hip): time C = A . B^T at fixed M, N
-over a sweep of K and fit  t = t_fixed + t_step * (K / 64)  per tile round; with
-``gemm_set_dbg(1)`` the epilogue (staging, bias/stats, C stores) is skipped, which splits the
-fixed cost into prologue and epilogue.  Findings (persistent kernel, register
-epilogues): profiles/measurements/r2_gemm_epilogue_probes.jsonl.
+over a sweep of K and fit  t = t_fixed + t_step * (K / 64)  per tile round.  ``--dbg 0,1``
+adds a sweep with ``gemm_set_dbg(1)``, a timing probe that skips the epilogue (staging,
+bias/stats, C stores) of gemm_nt_kernel (variants 1 and 8: the persistent kernel has no such
+probe) and so splits the fixed cost into prologue and epilogue; C is wrong in such a run.
+Findings (persistent kernel, register epilogues):
+profiles/measurements/r2_gemm_epilogue_probes.jsonl.
 
-    python tools/gemm_overhead.py [--out overhead.jsonl]
+    python tools/gemm_overhead.py [--variants 8 --dbg 0,1] [--out overhead.jsonl]
 """
 import argparse
 import json
@@ -41,7 +43,8 @@ def main():
     ap.add_argument("--K", default="64,128,256,512,768,1536,3072")
     ap.add_argument("--variants", default="-1")
     ap.add_argument("--nt", default="0", help="gemm_set_nt values (non-temporal C stores)")
-    ap.add_argument("--dbg", default="0,1", help="gemm_set_dbg values: 1 = skip the epilogue")
+    ap.add_argument("--dbg", default="0",
+                    help="gemm_set_dbg values: 1 = skip the epilogue (wrong results: timing only)")
     a = ap.parse_args()
     rows = []
     for N in [int(x) for x in a.N.split(",")]:
@@ -76,7 +79,7 @@ def main():
                 print(json.dumps(fit), flush=True)
     native._K.gemm_set_dbg(0)
     native._K.gemm_set_variant(-1)
-    native._K.gemm_set_nt(0)
+    native._K.gemm_set_nt(1)
     if a.out:
         with open(a.out, "w") as f:
             for r in rows:
