@@ -541,6 +541,13 @@ PYBIND11_MODULE(_dtf_hip, m) {
     dtf_cast_f32_bf16(P<const float>(x), P<bf16_t>(y), n, S(st));
     check_launch("cast_f32_bf16");
   });
+  m.def("ema_update", [](uintptr_t avg, uintptr_t var, long n, uintptr_t a, int max_blocks,
+                         uintptr_t st) {
+    if (n < 0 || !avg || !var || !a) throw std::invalid_argument("ema_update: bad arguments");
+    dtf_ema_update(P<float>(avg), P<const float>(var), n, P<const float>(a), max_blocks, S(st));
+    check_launch("ema_update");
+  }, py::arg("avg"), py::arg("var"), py::arg("n"), py::arg("a"), py::arg("max_blocks") = 0,
+     py::arg("stream") = (uintptr_t)0);
   m.def("conv_igemm", [](uintptr_t x, uintptr_t w, uintptr_t y, std::vector<int> geom,
                          std::vector<int> dh, std::vector<int> dw, int bk, uintptr_t st,
                          uintptr_t stats, std::vector<uintptr_t> bnb, uintptr_t acc_src,

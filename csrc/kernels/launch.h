@@ -344,6 +344,10 @@ void dtf_grad_norm_finish(const double* partial, long nchunks, const double* ext
 void dtf_grad_norm(const float* g, long n, double* partial, int max_blocks, const double* extra,
                    int nextra, float gscale, float clip, GradNormRecord* rec, hipStream_t st);
 void dtf_cast_f32_bf16(const float* x, bf16_t* y, long n, hipStream_t st);
+// tf.train.ExponentialMovingAverage: avg[i] -= a * (avg[i] - var[i]) over [0, n), a = *a_ptr on the
+// device.  avg / var may start at any element offset.  max_blocks: grid cap, 0 = default.
+void dtf_ema_update(float* avg, const float* var, long n, const float* a_ptr, int max_blocks,
+                    hipStream_t st);
 
 // ---- nlp.hip
 int dtf_bf16_col_sum_ws_floats(int N);

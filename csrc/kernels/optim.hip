@@ -426,6 +426,38 @@ grad_norm_finish_kernel(const double* __restrict__ partial, long nchunks,
   }
 }
 
+// ---- tf.train.ExponentialMovingAverage of the variables: avg -= a * (avg - var), a = 1 - decay
+// read from DEVICE memory (a captured graph replays with each step's own decay).  In this form
+// avg == var is a bit-exact fixed point.  avg and var sit at the same element offset of their
+// flat buffers, so one scalar head of `head` elements brings both to 16-byte alignment; then
+// float4, then a scalar tail.  Buffers misaligned differently get head = n: every element goes
+// through the (grid-stride) scalar head.  Plain loads and stores, one writer per element.
+DTF_DEV float ema_step(float e, float p, float a) { return e - a * (e - p); }
+
+__global__ void __launch_bounds__(kT)
+ema_update_kernel(float* __restrict__ avg, const float* __restrict__ var, long n, long head,
+                  const float* __restrict__ a_ptr) {
+  const float a = *a_ptr;
+  const long t0 = (long)blockIdx.x * kT + threadIdx.x;
+  const long stride = (long)gridDim.x * kT;
+  // head <= 3, or n: all scalar
+  for (long i = t0; i < head; i += stride) avg[i] = ema_step(avg[i], var[i], a);
+  float4* a4 = reinterpret_cast<float4*>(avg + head);
+  const float4* v4 = reinterpret_cast<const float4*>(var + head);
+  const long n4 = (n - head) >> 2;
+  for (long i = t0; i < n4; i += stride) {
+    float4 e = a4[i];
+    const float4 p = v4[i];
+    e.x = ema_step(e.x, p.x, a);
+    e.y = ema_step(e.y, p.y, a);
+    e.z = ema_step(e.z, p.z, a);
+    e.w = ema_step(e.w, p.w, a);
+    a4[i] = e;
+  }
+  // scalar tail
+  for (long i = head + n4 * 4 + t0; i < n; i += stride) avg[i] = ema_step(avg[i], var[i], a);
+}
+
 __global__ void __launch_bounds__(kT)
 cast_f32_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, long n) {
   for (long i = (long)blockIdx.x * kT + threadIdx.x; i < n; i += (long)gridDim.x * kT)
@@ -524,4 +556,17 @@ void dtf_grad_norm(const float* g, long n, double* partial, int max_blocks, cons
 
 void dtf_cast_f32_bf16(const float* x, bf16_t* y, long n, hipStream_t st) {
   hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(grid_for(n)), dim3(kT), 0, st, x, y, n);
+}
+
+void dtf_ema_update(float* avg, const float* var, long n, const float* a_ptr, int max_blocks,
+                    hipStream_t st) {
+  if (n <= 0) return;
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(avg), pv = reinterpret_cast<uintptr_t>(var);
+  // elements up to the next 16-byte boundary; buffers misaligned differently (never the flat
+  // buffers' case) take the scalar path for every element
+  long head = (long)(((16 - (pa & 15)) & 15) >> 2);
+  if ((pa & 15) != (pv & 15) || (pa & 3) || head > n) head = n;
+  int grid = grid_for(n, 4);
+  if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
+  hipLaunchKernelGGL(ema_update_kernel, dim3(grid), dim3(kT), 0, st, avg, var, n, head, a_ptr);
 }

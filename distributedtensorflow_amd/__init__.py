@@ -21,7 +21,7 @@ from .summary import logger  # noqa: F401
 # tf.train optimizer names live under train too
 for _n in ("AdamOptimizer", "AdagradOptimizer", "MomentumOptimizer", "GradientDescentOptimizer",
            "SyncReplicasOptimizer", "LAMBOptimizer", "LARSOptimizer",
-           "AdamWeightDecayOptimizer"):
+           "AdamWeightDecayOptimizer", "ExponentialMovingAverage"):
     setattr(train, _n, getattr(optimizers, _n))
 train.Server = cluster.Server
 train.ClusterSpec = cluster.ClusterSpec

@@ -19,6 +19,8 @@ Keeps the reference's flags and adds strategy selection:
                     --label_smoothing 0.1
     # loss / top-1 / top-k over all replicas: at the end (--eval) and every N steps (--eval_every)
     python train.py --model resnet50 --num_gpus 8 --eval --eval_steps 20 --eval_every 500
+    # moving averages of the variables, evaluated next to the raw weights
+    python train.py --model resnet50 --num_gpus 8 --ema_decay 0.9999 --eval
 
 The chief prints the reference's ``Worker (i): loss = x.xx (global step: n)`` line every
 ``--log_every`` steps and writes ``Global Step`` / ``Loss`` TensorBoard scalars under
@@ -72,6 +74,10 @@ def build_parser():
                         "BERT's AdamWeightDecayOptimizer (with --clip_norm 1.0 the BERT recipe)")
     p.add_argument("--clip_norm", type=float, default=None,
                    help="clip every step's gradient to this global norm, inside the fused update")
+    p.add_argument("--ema_decay", type=float, default=None,
+                   help="keep tf.train.ExponentialMovingAverage(D, num_updates=global_step) of the "
+                        "trainable variables inside the fused step; --eval / --eval_every then "
+                        "also evaluate the averaged weights")
     p.add_argument("--label_smoothing", type=float, default=0.0,
                    help="label smoothing of the sparse softmax cross-entropy loss")
     p.add_argument("--num_ps", type=int, default=None, help="colocated PS owners (strategy ps)")
@@ -151,10 +157,13 @@ def _spawn_local(args, argv):
     return subprocess.call(cmd)
 
 
-def _make_optimizer(name, lr, model_name, batch_global, max_steps=None, clip_norm=None):
+def _make_optimizer(name, lr, model_name, batch_global, max_steps=None, clip_norm=None,
+                    variable_averages=None):
     from . import optimizers as O
     from .optimizers.optimizers import cosine_decay, polynomial_decay
     kw = {} if clip_norm is None else {"clip_norm": clip_norm}
+    if variable_averages is not None:
+        kw["variable_averages"] = variable_averages
     if name == "adam":
         return O.AdamOptimizer(lr, **kw)
     if name == "adagrad":
@@ -215,6 +224,12 @@ def run(args):
     if args.clip_norm is not None and args.job_name:
         from .optimizers.base import CLIP_BETWEEN_GRAPH
         raise SystemExit(CLIP_BETWEEN_GRAPH)
+    if args.ema_decay is not None:
+        from .optimizers.moving_averages import EMA_BETWEEN_GRAPH
+        if args.job_name:
+            raise SystemExit(EMA_BETWEEN_GRAPH)
+        if not 0.0 < args.ema_decay < 1.0:
+            raise SystemExit(f"--ema_decay {args.ema_decay} outside (0, 1)")
     want_gpu = (args.device == "gpu" or
                 (args.device == "auto" and torch.cuda.is_available() and args.num_gpus != 0))
 
@@ -306,13 +321,16 @@ def run(args):
             from .models import bert
             model = getattr(bert, args.model)()
         model.train()
+        global_step = get_or_create_global_step()
+        ema = None
+        if args.ema_decay is not None:
+            ema = dtf.train.ExponentialMovingAverage(args.ema_decay, num_updates=global_step)
         opt = _make_optimizer(opt_name, lr, args.model, batch * nrep, args.max_steps,
-                              args.clip_norm)
+                              args.clip_norm, ema)
         if args.sync_replicas and server is not None:
             nw = len(server.worker_ranks())
             opt = dtf.train.SyncReplicasOptimizer(
                 opt, replicas_to_aggregate=args.replicas_to_aggregate or nw, total_num_replicas=nw)
-        global_step = get_or_create_global_step()
         opt.build(list(model.parameters()))
 
     def train_op():
@@ -339,7 +357,8 @@ def run(args):
     eval_fn = eval_hook = None
     if (args.eval or args.eval_every) and (server is None or is_chief):
         eval_fn = _make_eval_fn(args, model, opt, strategy, device, dtype, batch,
-                                nrep if server is None else 1, rid if server is None else 0)
+                                nrep if server is None else 1, rid if server is None else 0,
+                                ema)
     hooks = [StopAtStepHook(last_step=args.max_steps)]
     if eval_fn is not None and args.eval_every:
         from .train import EvalHook
@@ -397,6 +416,9 @@ def run(args):
         result["eval_loss"] = round(ev["loss"], 4)
         result["eval_top_1"] = round(ev["top_1"], 4)
         result["eval_top_k"] = round(ev["top_k"], 4)
+        for k in ("ema_loss", "ema_top_1", "ema_top_k"):
+            if k in ev:
+                result["eval_" + k] = round(ev[k], 4)
         if args.image_data or args.text_data:
             result["eval_count"] = int(ev["count"])
         elif args.model.startswith("mnist"):
@@ -459,9 +481,12 @@ def _token_dataset(args, split, batch, device, shards, shard_index):
                               shard_index=shard_index)
 
 
-def _make_eval_fn(args, model, opt, strategy, device, dtype, batch, shards, shard_index):
+def _make_eval_fn(args, model, opt, strategy, device, dtype, batch, shards, shard_index,
+                  ema=None):
     """-> eval_fn() -> {"loss", "top_1", "top_k", "count"}: one pass of this replica's shard of
-    the evaluation set through ``train.evaluate`` (collective under a collective strategy)."""
+    the evaluation set through ``train.evaluate`` (collective under a collective strategy).
+    With ``ema`` a second pass evaluates the averaged weights: "ema_loss", "ema_top_1",
+    "ema_top_k"."""
     from .metrics import ClassificationMetrics
     from .train import evaluate
     if args.image_data:
@@ -501,7 +526,13 @@ def _make_eval_fn(args, model, opt, strategy, device, dtype, batch, shards, shar
 
     def eval_fn():
         metrics.reset()
-        return evaluate(model, batches(), metrics, optimizer=opt, strategy=strategy)
+        res = evaluate(model, batches(), metrics, optimizer=opt, strategy=strategy)
+        if ema is not None:
+            metrics.reset()
+            avg = evaluate(model, batches(), metrics, optimizer=opt, strategy=strategy,
+                           averages=ema)
+            res.update({"ema_" + k: avg[k] for k in ("loss", "top_1", "top_k")})
+        return res
     return eval_fn
 
 

@@ -349,6 +349,16 @@ def mlm_mask_tokens(tokens, idx, seed, max_predictions, masking, example_stride=
                                      example_offset)
 
 
+def ema_update(avg, var, a_dev):
+    """One step of ``tf.train.ExponentialMovingAverage`` in place: ``avg -= a * (avg - var)`` over
+    flat fp32 buffers, ``a = 1 - decay`` read from the one-element fp32 tensor ``a_dev`` on the
+    tensors' device (a captured graph replays with each step's own decay).  Not fenced: the
+    optimizer calls it on the range it has just updated."""
+    if _use_native(avg):
+        return _native().ema_update(avg, var, a_dev)
+    return reference.ema_update(avg, var, a_dev)
+
+
 # ----------------------------------------------------------------------------- variable fence
 # A colocated parameter server gathers the updated variable shards AFTER the optimizer step,
 # asynchronously, bucket by bucket, while the next forward already runs (parallel/ps_strategy.py).
@@ -405,5 +415,5 @@ __all__ = [
     "softmax_cross_entropy_clipped_sum", "layer_norm", "gelu", "attention", "dropout",
     "bias_dropout_add_layer_norm", "embedding_layer_norm", "bias_gelu", "bias_gelu_dense",
     "dense_gelu_dense", "attention_qkv", "mlm_loss", "eval_rows", "in_top_k", "augment_images",
-    "mlm_mask_tokens",
+    "mlm_mask_tokens", "ema_update",
 ]

@@ -2053,6 +2053,19 @@ def mlm_mask_tokens(tokens, idx, seed, max_predictions, masking, example_stride=
                      "masked_lm_ids", "masked_lm_weights"), outs))
 
 
+def ema_update(avg, var, a_dev, max_blocks=0):
+    """avg -= a * (avg - var) in place over flat fp32 buffers (or slices of them, at any element
+    offset); ``a_dev``: one fp32 element on the device.  ``max_blocks`` caps the grid (tests)."""
+    for t in (avg, var, a_dev):
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("native ema_update needs contiguous fp32 GPU tensors")
+    if avg.numel() != var.numel() or a_dev.numel() < 1:
+        raise ValueError("ema_update: avg and var differ in size, or a_dev is empty")
+    _K.ema_update(avg.data_ptr(), var.data_ptr(), avg.numel(), a_dev.data_ptr(), int(max_blocks),
+                  _st())
+    return avg
+
+
 # ----------------------------------------------------------------------------- transformer ops
 # (LayerNorm / GELU / attention for BERT live in .native_nlp to keep this file focused)
 

@@ -541,3 +541,12 @@ def space_to_depth_operands(x, w, stride, pad, want_x=True):
     xs = xp.view(n, Hn // s, s, Wn // s, s, cp).permute(0, 1, 3, 2, 4, 5).reshape(
         n, Hn // s, Wn // s, s * s * cp)
     return xs.contiguous(), ws
+
+
+def ema_update(avg, var, a_dev):
+    """tf.train.ExponentialMovingAverage's update in place, in fp32 and in the kernel's operation
+    order: ``avg = avg - a * (avg - var)`` with ``a = 1 - decay`` the one-element fp32 tensor
+    ``a_dev``.  ``avg == var`` is a bit-exact fixed point."""
+    with torch.no_grad():
+        avg.sub_(a_dev.reshape(()) * (avg - var))
+    return avg

@@ -120,7 +120,7 @@ class Optimizer:
     elementwise: bool = True
 
     def __init__(self, learning_rate, name, weight_decay=0.0, decay_filter=None,
-                 use_locking=False, clip_norm=None):
+                 use_locking=False, clip_norm=None, variable_averages=None):
         if clip_norm is not None:
             clip_norm = float(clip_norm)
             if not clip_norm > 0.0:
@@ -146,11 +146,33 @@ class Optimizer:
         # True while a training step is being captured into a HIP graph (train/graphed.py): the
         # per-step hyper-parameters are then written by the replay wrapper, not by the step
         self._capturing = False
+        # tf.train.ExponentialMovingAverage of the variables (optimizers/moving_averages.py)
+        self.variable_averages = None
+        self._variables_to_average = None
+        # apply_gradients was given the average's ``num_updates`` object as ``global_step``: it
+        # is incremented after the update, and TF's average sees the incremented value
+        self._ema_bump = False
+        if variable_averages is not None:
+            self.set_variable_averages(variable_averages)
 
     # ------------------------------------------------------------------ hyper-parameters
     def learning_rate(self, step=None):
         lr = self._lr_value
         return float(lr(step if step is not None else self.iterations)) if callable(lr) else float(lr)
+
+    def set_variable_averages(self, ema, variables_to_average=None):
+        """Attach a :class:`ExponentialMovingAverage`; before ``build``.  ``variables_to_average``, if given, must be exactly the trainable variables:
+        one flat buffer cannot hold a subset."""
+        from .moving_averages import ExponentialMovingAverage
+        if self.space is not None:
+            raise ValueError("variable_averages must be attached before the optimizer is built")
+        if not isinstance(ema, ExponentialMovingAverage):
+            raise TypeError("variable_averages must be an ExponentialMovingAverage, got "
+                            f"{type(ema).__name__}")
+        ema._attach(self)
+        self.variable_averages = ema
+        self._variables_to_average = (None if variables_to_average is None
+                                      else list(variables_to_average))
 
     # ------------------------------------------------------------------ build
     def build(self, variables):
@@ -161,6 +183,16 @@ class Optimizer:
         strat = _strat.get_strategy()
         if self.clip_norm is not None and getattr(strat, "mode", None) == "between_graph":
             raise ValueError(CLIP_BETWEEN_GRAPH)
+        ema = self.variable_averages
+        if ema is not None:
+            from .moving_averages import EMA_BETWEEN_GRAPH
+            if getattr(strat, "mode", None) == "between_graph":
+                raise ValueError(EMA_BETWEEN_GRAPH)
+            if self._variables_to_average is not None and \
+                    sorted(id(v) for v in self._variables_to_average) != \
+                    sorted(id(v) for v in variables if v.requires_grad):
+                raise ValueError("variables_to_average must be exactly the trainable variables: "
+                                 "the averages are one flat buffer over all of them")
         dev = variables[0].device
         shadow = (torch.bfloat16 if dev.type == "cuda" else None) if self.shadow_dtype == "auto" \
             else self.shadow_dtype
@@ -172,6 +204,8 @@ class Optimizer:
         self._build_clip()
         self._reducer = strat.make_gradient_reducer(self.space)
         strat.broadcast_space(self.space)
+        if ema is not None:
+            ema._build(self)      # TF initialises a shadow with the variable's (broadcast) value
         return self.space
 
     def _build_slots(self):
@@ -199,6 +233,9 @@ class Optimizer:
     def apply_gradients(self, grads_and_vars=None, global_step=None):
         assert self.space is not None, "call build()/compute_gradients() first"
         self.iterations += 1
+        ema = self.variable_averages
+        self._ema_bump = ema is not None and global_step is not None and \
+            global_step is ema.num_updates
         if getattr(self._reducer, "applies_update", False):
             # parameter-server strategies: the PS owning the variables applies the update
             step = self._reducer.apply_remote(self)
@@ -223,6 +260,10 @@ class Optimizer:
         # only when set: the configurations of unclipped optimizers stay what they were
         if self.clip_norm is not None:
             cfg["clip_norm"] = self.clip_norm
+        if self.variable_averages is not None:
+            # a description only (the parameter-server tasks refuse it): it does not carry
+            # ``num_updates`` and no optimizer is rebuilt from it
+            cfg["variable_averages"] = self.variable_averages.get_config()
         return cfg
 
     def minimize(self, loss, global_step=None, var_list=None):
@@ -235,8 +276,15 @@ class Optimizer:
     # ------------------------------------------------------------------ update
     def _refresh_hyper(self):
         """Write this step's hyper-parameters into the device buffers the fused kernels read
-        (learning rate; Adam's lr_t; LAMB's bias corrections)."""
+        (learning rate; Adam's lr_t; LAMB's bias corrections).  Overridden per optimizer; the
+        moving average's ``1 - decay`` is written by ``_refresh_ema``, which no override has to
+        remember: ``_apply`` calls it for every eager step and the graph replay wrapper before
+        every replay."""
         self._lr_dev[0].fill_(self.learning_rate())
+
+    def _refresh_ema(self):
+        if self.variable_averages is not None:
+            self.variable_averages._refresh(self._ema_bump)
 
     def _maybe_refresh_hyper(self):
         # inside a graph capture the fill would be recorded with THIS step's constant; the
@@ -317,6 +365,8 @@ class Optimizer:
         if self.clip_norm is not None and not self._clip_held:
             self._grad_norm_pass(gscale, [rng if rng is not None else (0, self.space.numel)],
                                  extra)
+        if not self._capturing:
+            self._refresh_ema()      # on both devices, whatever ``_refresh_hyper`` is overridden to
         self._range = rng
         try:
             if self.space.device.type == "cuda":
@@ -325,6 +375,9 @@ class Optimizer:
                 self._apply_reference(gscale)
         finally:
             self._range = None
+        ema = self.variable_averages
+        if ema is not None:
+            ema._update(rng)
 
     def _regions(self):
         regs = self.space.regions()

@@ -7,6 +7,9 @@ backup workers), drops stale ones, applies once and releases the workers (the to
 Under Mirrored/MultiWorkerMirrored (and the colocated PS) training is already synchronous over
 every replica, so it delegates -- and raises if asked for backup workers
 (``replicas_to_aggregate < replicas``), which only the arrival-order between-graph PS provides.  The queue-runner / init-token API of TF1 is provided as no-ops for drop-in use.
+``variable_averages`` (a ``dtf.train.ExponentialMovingAverage``) is handed to the wrapped optimizer,
+which keeps the averages inside its fused step; ``variables_to_average``, if given, must be exactly
+the trainable variables.
 """
 from __future__ import annotations
 
@@ -24,6 +27,12 @@ class SyncReplicasOptimizer:
                  variables_to_average=None, use_locking=False, name="sync_replicas"):
         from ..parallel.strategy import get_strategy
         self._opt = opt
+        if variable_averages is not None:
+            # tf.train.SyncReplicasOptimizer applies the average after the aggregated update:
+            # here the wrapped optimizer does, inside its fused step
+            opt.set_variable_averages(variable_averages, variables_to_average)
+        elif variables_to_average is not None:
+            raise ValueError("variables_to_average needs variable_averages")
         self.replicas_to_aggregate = int(replicas_to_aggregate)
         self.total_num_replicas = int(total_num_replicas or replicas_to_aggregate)
         if self.replicas_to_aggregate > self.total_num_replicas:

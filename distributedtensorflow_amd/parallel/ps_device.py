@@ -205,6 +205,9 @@ def _make_optimizer(cfg, space):
     cfg = dict(cfg)
     if cfg.get("clip_norm") is not None:
         raise ValueError(CLIP_BETWEEN_GRAPH)
+    if cfg.get("variable_averages") is not None:
+        from ..optimizers.moving_averages import EMA_BETWEEN_GRAPH
+        raise ValueError(EMA_BETWEEN_GRAPH)
     kind = cfg.pop("type")
     cls = {"adam": AdamOptimizer, "adagrad": AdagradOptimizer, "momentum": MomentumOptimizer,
            "sgd": GradientDescentOptimizer, "lamb": LAMBOptimizer,

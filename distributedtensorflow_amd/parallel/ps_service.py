@@ -114,6 +114,9 @@ class _Shard:
         opt = dict(spec["optimizer"])
         if opt.get("clip_norm") is not None:
             raise ValueError(CLIP_BETWEEN_GRAPH)
+        if opt.get("variable_averages") is not None:
+            from ..optimizers.moving_averages import EMA_BETWEEN_GRAPH
+            raise ValueError(EMA_BETWEEN_GRAPH)
         kind = opt.pop("type")
         cls = {"adam": AdamOptimizer, "adagrad": AdagradOptimizer, "momentum": MomentumOptimizer,
                "sgd": GradientDescentOptimizer, "lamb": LAMBOptimizer,

@@ -8,6 +8,7 @@ Files for ``save(..., "model.ckpt", global_step=N)``:
 Keys and layouts are TF's: ``conv2d/kernel`` is stored HWIO (internally KRSC), dense kernels
 ``[in, out]`` (internally ``[out, in]``), Adam slots ``<var>/Adam``, ``<var>/Adam_1`` plus
 ``beta1_power``/``beta2_power``, Momentum ``<var>/Momentum``, and ``global_step`` (int64).
+An optimizer's ``variable_averages`` are stored as ``<var>/ExponentialMovingAverage``.
 """
 from __future__ import annotations
 
@@ -249,6 +250,15 @@ class Saver:
                     sh = getattr(t, "_dtf_shadow", None)
                     if sh is not None:
                         sh.copy_(t)
+        ema = getattr(self.optimizer, "variable_averages", None)
+        if self._var_list is None and ema is not None and ema.buf is not None:
+            names = {n for n in self.optimizer.slot_variables() if n.endswith("/" + ema.name)}
+            if not names & have:
+                # a checkpoint written without averages: as TF initialises a shadow, each
+                # average starts from its (restored) variable
+                with torch.no_grad():
+                    ema.buf.copy_(self.optimizer.space.master)
+                missing = [n for n in missing if n not in names]
         if self.optimizer is not None and "beta1_power" in have and \
                 hasattr(self.optimizer, "beta1"):
             b1p = float(reader.get_tensor("beta1_power"))

@@ -37,13 +37,26 @@ def default_forward(model, batch):
     return model(x), y, None
 
 
-def evaluate(model, batches, metrics, optimizer=None, strategy=None, forward=None):
+def evaluate(model, batches, metrics, optimizer=None, strategy=None, forward=None,
+             averages=None):
     """Run every batch of the finite iterable ``batches`` through ``model`` in evaluation mode,
     add it to ``metrics`` and return ``metrics.result()`` (collective under a collective
     strategy).  ``optimizer``: its pending variable communication is waited for first (a
     colocated parameter server may still be gathering updated shards).  ``forward(model, batch)
     -> (logits, labels, weights)`` replaces :func:`default_forward`.  The model's previous
-    train / eval mode is restored whatever happens."""
+    train / eval mode is restored whatever happens.  ``averages``: an
+    ``ExponentialMovingAverage`` attached to the optimizer; the loop then runs inside its
+    ``swap()``, on the averaged weights (collective under a colocated parameter server)."""
+    if averages is not None:
+        inner = getattr(optimizer, "_opt", optimizer)       # a SyncReplicasOptimizer's
+        if inner is not None and averages.optimizer is not inner:
+            raise ValueError("evaluate: averages= is not attached to this optimizer")
+        space = getattr(averages.optimizer, "space", None)
+        if space is None or {id(p) for p in model.parameters() if p.requires_grad} != \
+                {id(v) for v in space.order}:
+            raise ValueError("evaluate: averages= does not hold this model's variables")
+        with averages.swap():
+            return evaluate(model, batches, metrics, optimizer, strategy, forward)
     forward = forward or default_forward
     if optimizer is not None and getattr(optimizer, "space", None) is not None:
         optimizer.synchronize_variables()
@@ -65,7 +78,8 @@ class EvalHook(SessionRunHook):
     """Evaluate every ``every_n_steps`` global steps.  ``eval_fn() -> dict`` (typically a closure
     over :func:`evaluate` with a fresh single-pass iterator and reset metrics) runs on EVERY
     replica at the same global step, because reading the result is collective; the chief writes
-    ``eval/loss``, ``eval/top_1`` and ``eval/top_k`` at that step to ``summary_writer`` (an
+    ``eval/loss``, ``eval/top_1`` and ``eval/top_k`` (and ``eval/ema_loss``, ``eval/ema_top_1``,
+    ``eval/ema_top_k`` where the result carries the averaged weights' figures) at that step to ``summary_writer`` (an
     ``EventFileWriter`` or a logger ``KVWriter`` such as ``TensorBoardOutputFormat``), else to the
     session's summary writer."""
 
@@ -94,7 +108,8 @@ class EvalHook(SessionRunHook):
         self.results.append((step, res))
         if not getattr(session, "is_chief", True):
             return
-        vals = {f"eval/{k}": res[k] for k in ("loss", "top_1", "top_k") if k in res}
+        vals = {f"eval/{k}": res[k] for k in ("loss", "top_1", "top_k", "ema_loss", "ema_top_1",
+                                              "ema_top_k") if k in res}
         w = self.writer if self.writer is not None else getattr(session, "summary_writer", None)
         if w is None:
             return

@@ -9,7 +9,8 @@ step's kernels on a capture stream (``torch.cuda.graph`` = hipStreamBeginCapture
 hipGraphInstantiate) and each call is one ``hipGraphLaunch``:
 
 * every kernel of the step already launches on the caller's current stream and reads its
-  per-step hyper-parameters (learning rate, Adam's lr_t, LAMB's bias corrections) from DEVICE
+  per-step hyper-parameters (learning rate, Adam's lr_t, LAMB's bias corrections, the variable
+  averages' 1 - decay) from DEVICE
   buffers (``csrc/kernels/optim.hip``); the wrapper refreshes those buffers before each replay
   (``Optimizer._refresh_hyper``) and advances ``iterations`` / ``global_step`` on the host,
   exactly what the eager ``apply_gradients`` does;
@@ -84,6 +85,7 @@ class GraphedTrainStep:
         opt = self.opt
         opt.iterations += 1                  # what apply_gradients does before the update
         opt._refresh_hyper()
+        opt._refresh_ema()
         if self.global_step is not None:
             gs.increment(self.global_step)
         self.graph.replay()
