@@ -249,6 +249,30 @@ PYBIND11_MODULE(_dtf_hip, m) {
     const ConvGeom g = conv_geom("conv_tile_rows", geom);   // checked before the taps
     return dtf_conv_tile_rows(g, make_taps<TapTable>(dh, dw), bnb);
   }, py::arg("geom"), py::arg("dh"), py::arg("dw"), py::arg("bnb") = 0);
+  // the kernel conv_igemm would launch for the same arguments (only the PRESENCE of the pointers
+  // matters: stats, the bnb list, bias, relu and the BN-on-load triple)
+  m.def("conv_route", [](std::vector<int> geom, std::vector<int> dh, std::vector<int> dw, int bk,
+                         bool stats, bool bnb, bool bias, int relu, bool bnl) {
+    static float on = 0.f;
+    static bf16_t ony{};
+    ConvGeom g = conv_geom("conv_route", geom);
+    if (g.P <= 0 || g.Q <= 0) throw std::runtime_error("conv_route: P, Q must be > 0");
+    if (bias) g.bias = &on;
+    g.relu = relu;
+    if (bnl) { g.lsc = &on; g.lsh = &on; g.ly = &ony; }
+    BnBwdEpi e{};
+    if (bnb) e.part = &on;
+    return dtf_conv_route(g, make_taps<TapTable>(dh, dw), bk, stats, e);
+  }, py::arg("geom"), py::arg("dh"), py::arg("dw"), py::arg("bk") = 64, py::arg("stats") = false,
+     py::arg("bnb") = false, py::arg("bias") = false, py::arg("relu") = 0, py::arg("bnl") = false);
+  m.def("conv_wgrad_route", [](std::vector<int> geom, std::vector<int> dh, std::vector<int> dw,
+                               int splits, int tr_mode) {
+    if (geom.size() != 10) throw std::runtime_error("conv_wgrad_route: geom needs 10 ints");
+    if (geom[4] <= 0 || geom[5] <= 0) throw std::runtime_error("conv_wgrad_route: P, Q must be > 0");
+    WgradGeom g{geom[0], geom[1], geom[2], geom[3], geom[4], geom[5], geom[6], geom[7], geom[8],
+                geom[9], 0, 0};
+    return dtf_conv_wgrad_route(g, make_taps<TapTableW>(dh, dw), splits, tr_mode);
+  }, py::arg("geom"), py::arg("dh"), py::arg("dw"), py::arg("splits"), py::arg("tr_mode") = 1);
   m.def("conv_set_halo_bnb", &dtf_conv_set_halo_bnb);
   m.def("conv_set_dma_mode", &dtf_conv_set_dma_mode);
   m.def("filter_transpose", [](std::vector<uintptr_t> src, std::vector<uintptr_t> dst,

@@ -1385,16 +1385,31 @@ static void launch_halo_ring(const bf16_t* X, const bf16_t* Wt, bf16_t* Y, const
                      dim3(kThreads * ST), lds, st, X, Wt, Y, g, taps, stats, bnb);
 }
 
+// The form of the halo kernel a launch takes under the current knobs (part of the route, below)
+enum HaloForm {
+  kHfPlain, kHfStrips2, kHfFreg, kHfBnb, kHfFregBnb, kHfRing, kHfRingStrips2, kHfRingBnb, kHfBnl
+};
+static HaloForm halo_form(int fam, bool bnl, bool bnb, int* nstg_out) {
+  const int nstg = (g_halo_stages >> (fam == 1 ? 0 : 4)) & 15;
+  const bool freg = (g_halo_freg & fam) != 0, st2 = (g_halo_st & fam) != 0;
+  *nstg_out = nstg;
+  if (bnl) return kHfBnl;
+  if (!freg && (nstg == 3 || nstg == 4)) return bnb ? kHfRingBnb : st2 ? kHfRingStrips2 : kHfRing;
+  if (bnb) return freg ? kHfFregBnb : kHfBnb;
+  if (st2) return kHfStrips2;
+  return freg ? kHfFreg : kHfPlain;
+}
+
 template <int C, int W, int WMW, int NT>
 static void launch_halo(const bf16_t* X, const bf16_t* Wt, bf16_t* Y, const ConvGeom& g,
                         const TapTable& taps, float* stats, const BnBwdEpi& bnb, int tiles,
-                        int strips, hipStream_t st) {
+                        HaloForm form, int nstg, hipStream_t st) {
   using Hc = HaloCfg<C, W, WMW, NT>;
-  const int nstg = (g_halo_stages >> (C == 64 ? 0 : 4)) & 15;
-  const bool freg_on = (g_halo_freg & (C == 64 ? 1 : 2)) != 0;
-  if (g.ly) {
-    if (bnb.part || freg_on || nstg == 3 || nstg == 4 || strips != 1)
-      throw std::runtime_error("halo conv: BN on load needs the default forward ring kernel");
+  // the BN-backward reduction scratch [OROWS][2][NT] fp32 sits past the staged tile (in the dead
+  // filter ring, or past the patch with FREG); those forms run one strip per block
+  constexpr size_t scratch = (size_t)Hc::M * Hc::LDC * 2 + (size_t)(kThreads / (NT / 8)) * 2 * NT * 4;
+  switch (form) {
+  case kHfBnl: {
 #ifdef DTF_PROBES
     auto kern = g_bnl_probe ? conv3x3_halo_kernel<C, W, WMW, NT, 1, false, false, 2, true, 1>
                             : conv3x3_halo_kernel<C, W, WMW, NT, 1, false, false, 2, true>;
@@ -1412,41 +1427,36 @@ static void launch_halo(const bf16_t* X, const bf16_t* Wt, bf16_t* Y, const Conv
                        X, Wt, Y, g, taps, stats, bnb);
     return;
   }
-  if (!freg_on && (nstg == 3 || nstg == 4)) {
-    if (bnb.part) {
-      constexpr size_t scratch =
-          (size_t)Hc::M * Hc::LDC * 2 + (size_t)(kThreads / (NT / 8)) * 2 * NT * 4;
-      const size_t base = Hc::lds(1, nstg);
-      const size_t lds = base > scratch ? base : scratch;
-      if (nstg == 3) launch_halo_ring<C, W, WMW, NT, 1, true, 3>(X, Wt, Y, g, taps, stats, bnb, tiles, lds, st);
-      else launch_halo_ring<C, W, WMW, NT, 1, true, 4>(X, Wt, Y, g, taps, stats, bnb, tiles, lds, st);
-    } else if (strips == 2) {
-      if (nstg == 3) launch_halo_ring<C, W, WMW, NT, 2, false, 3>(X, Wt, Y, g, taps, stats, bnb, tiles, Hc::lds(2, 3), st);
-      else launch_halo_ring<C, W, WMW, NT, 2, false, 4>(X, Wt, Y, g, taps, stats, bnb, tiles, Hc::lds(2, 4), st);
-    } else {
-      if (nstg == 3) launch_halo_ring<C, W, WMW, NT, 1, false, 3>(X, Wt, Y, g, taps, stats, bnb, tiles, Hc::lds(1, 3), st);
-      else launch_halo_ring<C, W, WMW, NT, 1, false, 4>(X, Wt, Y, g, taps, stats, bnb, tiles, Hc::lds(1, 4), st);
-    }
-    return;
-  }
-  if (bnb.part) {
-    // one strip per block; the BN-backward reduction scratch [OROWS][2][NT] fp32 sits past the
-    // staged tile (in the dead filter ring, or past the patch with FREG)
-    constexpr size_t scratch = (size_t)Hc::M * Hc::LDC * 2 + (size_t)(kThreads / (NT / 8)) * 2 * NT * 4;
-    const bool freg = (g_halo_freg & (C == 64 ? 1 : 2)) != 0;
-    const size_t base = freg ? Hc::LDS_FREG : Hc::lds(1);
+  case kHfRingBnb: {
+    const size_t base = Hc::lds(1, nstg);
     const size_t lds = base > scratch ? base : scratch;
-    if (freg)
-      hipLaunchKernelGGL((conv3x3_halo_kernel<C, W, WMW, NT, 1, true, true>),
-                         dim3((unsigned)tiles, g.Kout / NT), dim3(kThreads), lds, st, X, Wt, Y, g,
-                         taps, stats, bnb);
-    else
-      hipLaunchKernelGGL((conv3x3_halo_kernel<C, W, WMW, NT, 1, false, true>),
-                         dim3((unsigned)tiles, g.Kout / NT), dim3(kThreads), lds, st, X, Wt, Y, g,
-                         taps, stats, bnb);
+    if (nstg == 3) launch_halo_ring<C, W, WMW, NT, 1, true, 3>(X, Wt, Y, g, taps, stats, bnb, tiles, lds, st);
+    else launch_halo_ring<C, W, WMW, NT, 1, true, 4>(X, Wt, Y, g, taps, stats, bnb, tiles, lds, st);
     return;
   }
-  if (strips == 2) {
+  case kHfRingStrips2:
+    if (nstg == 3) launch_halo_ring<C, W, WMW, NT, 2, false, 3>(X, Wt, Y, g, taps, stats, bnb, tiles, Hc::lds(2, 3), st);
+    else launch_halo_ring<C, W, WMW, NT, 2, false, 4>(X, Wt, Y, g, taps, stats, bnb, tiles, Hc::lds(2, 4), st);
+    return;
+  case kHfRing:
+    if (nstg == 3) launch_halo_ring<C, W, WMW, NT, 1, false, 3>(X, Wt, Y, g, taps, stats, bnb, tiles, Hc::lds(1, 3), st);
+    else launch_halo_ring<C, W, WMW, NT, 1, false, 4>(X, Wt, Y, g, taps, stats, bnb, tiles, Hc::lds(1, 4), st);
+    return;
+  case kHfFregBnb: {
+    const size_t lds = Hc::LDS_FREG > scratch ? Hc::LDS_FREG : scratch;
+    hipLaunchKernelGGL((conv3x3_halo_kernel<C, W, WMW, NT, 1, true, true>),
+                       dim3((unsigned)tiles, g.Kout / NT), dim3(kThreads), lds, st, X, Wt, Y, g,
+                       taps, stats, bnb);
+    return;
+  }
+  case kHfBnb: {
+    const size_t lds = Hc::lds(1) > scratch ? Hc::lds(1) : scratch;
+    hipLaunchKernelGGL((conv3x3_halo_kernel<C, W, WMW, NT, 1, false, true>),
+                       dim3((unsigned)tiles, g.Kout / NT), dim3(kThreads), lds, st, X, Wt, Y, g,
+                       taps, stats, bnb);
+    return;
+  }
+  case kHfStrips2: {
     static bool attr = false;
     if (!attr) {
       HIP_CHECK(hipFuncSetAttribute((const void*)conv3x3_halo_kernel<C, W, WMW, NT, 2>,
@@ -1456,13 +1466,17 @@ static void launch_halo(const bf16_t* X, const bf16_t* Wt, bf16_t* Y, const Conv
     hipLaunchKernelGGL((conv3x3_halo_kernel<C, W, WMW, NT, 2>),
                        dim3((unsigned)((tiles + 1) / 2), g.Kout / NT), dim3(2 * kThreads), Hc::lds(2),
                        st, X, Wt, Y, g, taps, stats, bnb);
-  } else if (g_halo_freg & (C == 64 ? 1 : 2)) {
+    return;
+  }
+  case kHfFreg:
     hipLaunchKernelGGL((conv3x3_halo_kernel<C, W, WMW, NT, 1, true>),
                        dim3((unsigned)tiles, g.Kout / NT), dim3(kThreads), Hc::LDS_FREG, st, X, Wt,
                        Y, g, taps, stats, bnb);
-  } else {
+    return;
+  case kHfPlain:
     hipLaunchKernelGGL((conv3x3_halo_kernel<C, W, WMW, NT, 1>), dim3((unsigned)tiles, g.Kout / NT),
                        dim3(kThreads), Hc::lds(1), st, X, Wt, Y, g, taps, stats, bnb);
+    return;
   }
 }
 
@@ -1515,21 +1529,6 @@ static bool use_conv_gemm(const ConvGeom& g, const TapTable& taps) {
          !g.relu && g.H < 16384 && g.W < 32768;
 }
 
-// M tiles (= BN-statistics slab rows) of exactly the kernel dtf_conv_igemm will pick for this
-// forward launch (no fused BN-backward epilogue)
-int dtf_conv_tile_rows(const ConvGeom& g, const TapTable& taps, int bnb) {
-  if (bnb) {   // a fused-BN-backward data gradient (the dispatch of dtf_conv_igemm with bnb.part)
-    if (g.C % 32 == 0 && !g.bias && !g.relu && use_halo(g, taps) && g_halo_bnb)
-      return g.N * (g.H / kHaloTH);
-    return dtf_conv_stats_rows((long)g.N * g.P * g.Q, g.Kout, g.C, taps.n, 0);
-  }
-  if (use_conv_gemm(g, taps)) return (int)(((long)g.N * g.P * g.Q + 255) / 256);
-  if (g.C % 32 == 0 && use_halo(g, taps)) return g.N * (g.H / kHaloTH);
-  if (use_stem_halo(g, taps)) return g.N * (g.P / kStemTH);
-  const long M = (long)g.N * g.P * g.Q;
-  return dtf_conv_stats_rows(M, g.Kout, g.C, taps.n, 0);
-}
-
 static int g_conv_nt = 0;   // measured neutral on ResNet-50 b2048 (DTF_STORE_NT A/B)
 void dtf_conv_set_nt(int v) { g_conv_nt = v; }
 
@@ -1540,6 +1539,118 @@ bool dtf_conv_bnl_ok(const ConvGeom& g, const TapTable& taps) {
   if (!fam || (g_halo_freg & fam) || (g_halo_st & fam)) return false;
   const int nstg = (g_halo_stages >> (fam == 1 ? 0 : 4)) & 15;
   return nstg != 3 && nstg != 4;
+}
+
+// ---- the route: which kernel a launch takes.  This is the ONE copy of the dispatch conditions:
+// dtf_conv_igemm switches on it, dtf_conv_tile_rows sizes the slabs from it and dtf_conv_route
+// names it, so none of the three can drift from the others.
+enum ConvKind { kRtHaloBnl, kRtStem, kRtGather, kRtGemm, kRtHalo, kRtDma, kRtReg };
+struct ConvRoute {
+  ConvKind kind;
+  bool narrow;      // gather / register kernels: the 256 x 64 tile (Kout <= 64), else 128 x 128
+  int bk;           // register kernels: 32 or 64
+  int chunk;        // gather kernels: 8 (C % 8 == 0, 16-byte chunks) or 1 (element gather)
+  int fam;          // halo kernels: the family, with its form and filter-ring depth
+  HaloForm form;
+  int nstg;
+};
+static ConvRoute conv_route(const ConvGeom& g, const TapTable& taps, int bk, bool stats,
+                            const BnBwdEpi& bnb) {
+  ConvRoute r{kRtReg, g.Kout <= 64, bk, 0, 0, kHfPlain, 0};
+  const bool epi = g.bias || g.relu;       // fused bias / ReLU: register kernel only
+  const long m = (long)g.N * g.P * g.Q;
+  if (g.ly) {                              // BN + ReLU on load: the halo forward kernel only
+    if (!dtf_conv_bnl_ok(g, taps) || !g.lsc || !g.lsh || bnb.part || epi)
+      throw std::runtime_error("conv: BN on load needs a halo-family forward conv");
+    r.kind = kRtHaloBnl;
+    r.fam = halo_family(g, taps);
+    r.form = halo_form(r.fam, true, false, &r.nstg);
+    return r;
+  }
+  if (!bnb.part && use_stem_halo(g, taps)) {
+    r.kind = kRtStem;
+    return r;
+  }
+  if (g.C % 32 != 0) {
+    r.kind = kRtGather;
+    r.chunk = g.C % 8 == 0 ? 8 : 1;        // chunk gather (stem / MNIST conv1, C padded to 8)
+    return r;
+  }
+  if (!bnb.part && use_conv_gemm(g, taps)) {
+    r.kind = kRtGemm;
+    return r;
+  }
+  if (!epi && use_halo(g, taps) && (!bnb.part || (g_halo_bnb && !stats))) {
+    r.kind = kRtHalo;
+    r.fam = halo_family(g, taps);
+    r.form = halo_form(r.fam, false, bnb.part != nullptr, &r.nstg);
+    return r;
+  }
+  if (!epi && use_dma_kernel(m, g.Kout, g.C, taps.n, bk) && g.Kpad % 64 == 0) {
+    r.kind = kRtDma;
+    return r;
+  }
+  // small-K 1x1 convs (one or two 64-deep K-steps: latency-bound blocks): optionally BK 32 with
+  // 16-KB stages -> more blocks per CU (g_small_k bit 1; A/B-measured by tools/conv_bench.py)
+  if ((g_small_k & 2) && taps.n == 1 && g.C <= 128) bk = 32;
+  if ((g_small_k & 4) && taps.n == 1) bk = 32;            // every 1x1 conv
+  if ((g_small_k & 8) && !use_dma_kernel(m, g.Kout, g.C, taps.n, 64)) bk = 32;   // all reg.
+  r.bk = bk == 64 && g.C % 64 == 0 ? 64 : 32;
+  return r;
+}
+
+// M rows of one tile of the route (= rows one BN-statistics / BN-backward slab row sums)
+static long conv_route_tiles(const ConvRoute& r, const ConvGeom& g) {
+  const long M = (long)g.N * g.P * g.Q;
+  switch (r.kind) {
+  case kRtHaloBnl:
+  case kRtHalo: return (long)g.N * (g.H / kHaloTH);
+  case kRtStem: return (long)g.N * (g.P / kStemTH);
+  case kRtGemm: return (M + 255) / 256;
+  case kRtDma: return (M + kDmaBM - 1) / kDmaBM;
+  default: break;
+  }
+  const int BM = r.narrow ? 256 : 128;
+  return (M + BM - 1) / BM;
+}
+
+// M tiles (= BN-statistics slab rows) of exactly the kernel dtf_conv_igemm will pick for this
+// launch; bnb: a data gradient with the fused BN-backward sums
+int dtf_conv_tile_rows(const ConvGeom& g, const TapTable& taps, int bnb) {
+  BnBwdEpi e{};
+  float on = 0.f;
+  if (bnb) e.part = &on;                   // only its presence selects the route
+  return (int)conv_route_tiles(conv_route(g, taps, 64, false, e), g);
+}
+
+// The route's short name: the kernel family, then what picks another instantiation of it.
+std::string dtf_conv_route(const ConvGeom& g, const TapTable& taps, int bk, bool stats,
+                           const BnBwdEpi& bnb) {
+  const ConvRoute r = conv_route(g, taps, bk, stats, bnb);
+  const char* tile = r.narrow ? "_narrow" : "_wide";
+  const std::string tail = bnb.part ? "_bnb" : stats ? "_stats" : "";
+  switch (r.kind) {
+  case kRtStem: return std::string("stem") + (stats ? "_stats" : "");
+  case kRtGather: return "gather" + std::to_string(r.chunk) + tile + tail;
+  case kRtGemm: return std::string("gemm") + (stats ? "_stats" : "");
+  case kRtDma: return "dma" + tail;
+  case kRtReg: return "reg" + std::to_string(r.bk) + tile + tail;
+  case kRtHaloBnl:
+  case kRtHalo: break;
+  }
+  const std::string h = "halo" + std::to_string(r.fam), n = std::to_string(r.nstg);
+  switch (r.form) {
+  case kHfPlain: return h + (stats ? "_stats" : "");
+  case kHfStrips2: return h + "_strips2" + (stats ? "_stats" : "");
+  case kHfFreg: return h + "_freg" + (stats ? "_stats" : "");
+  case kHfBnb: return h + "_bnb";
+  case kHfFregBnb: return h + "_freg_bnb";
+  case kHfRing: return h + "_ring" + n + (stats ? "_stats" : "");
+  case kHfRingStrips2: return h + "_ring" + n + "_strips2" + (stats ? "_stats" : "");
+  case kHfRingBnb: return h + "_ring" + n + "_bnb";
+  case kHfBnl: return h + "_bnl" + (stats ? "_stats" : "");
+  }
+  return h;
 }
 
 void dtf_conv_igemm(const bf16_t* X, const bf16_t* Wt, bf16_t* Y, const ConvGeom& g_in,
@@ -1560,21 +1671,20 @@ void dtf_conv_igemm(const bf16_t* X, const bf16_t* Wt, bf16_t* Y, const ConvGeom
   if (ibytes * span >= 2147483647.0 || wbytes >= 2147483647.0 || m >= 2147483647.0 ||
       (double)g.N * g.Ho * g.Wo >= 2147483647.0)
     throw std::runtime_error("conv: image / filter too large for 32-bit buffer offsets");
-  const bool narrow = g.Kout <= 64;        // 256 x 64 tile for 64-wide layers
-  const bool epi = g.bias || g.relu;       // fused bias / ReLU: register kernel only
-  if (epi && (bnb.part || g.acc))
+  if ((g.bias || g.relu) && (bnb.part || g.acc))
     throw std::runtime_error("conv: fused bias/ReLU epilogue excludes BN / accumulate epilogues");
-  if (g.ly) {                              // BN + ReLU on load: the halo forward kernel only
-    if (!dtf_conv_bnl_ok(g, taps) || !g.lsc || !g.lsh || bnb.part || epi)
-      throw std::runtime_error("conv: BN on load needs a halo-family forward conv");
+  const ConvRoute r = conv_route(g, taps, bk, stats != nullptr, bnb);
+  switch (r.kind) {
+  case kRtHaloBnl:
+  case kRtHalo: {
     const int tiles = g.N * (g.H / kHaloTH);
-    if (halo_family(g, taps) == 1)
-      launch_halo<64, 56, 2, 64>(X, Wt, Y, g, taps, stats, bnb, tiles, 1, st);
+    if (r.fam == 1)
+      launch_halo<64, 56, 2, 64>(X, Wt, Y, g, taps, stats, bnb, tiles, r.form, r.nstg, st);
     else
-      launch_halo<128, 28, 1, 128>(X, Wt, Y, g, taps, stats, bnb, tiles, 1, st);
+      launch_halo<128, 28, 1, 128>(X, Wt, Y, g, taps, stats, bnb, tiles, r.form, r.nstg, st);
     return;
   }
-  if (!bnb.part && use_stem_halo(g, taps)) {
+  case kRtStem: {
     using Sc = StemCfg<112>;
     static bool attr = false;
     if (!attr) {
@@ -1586,34 +1696,23 @@ void dtf_conv_igemm(const bf16_t* X, const bf16_t* Wt, bf16_t* Y, const ConvGeom
                        dim3(kThreads), Sc::LDS, st, X, Wt, Y, g, stats);
     return;
   }
-  if (g.C % 32 != 0) {
+  case kRtGather:
     if (g.Kpad % 32) throw std::runtime_error("conv: Kpad % 32 != 0");
-    if (g.C % 8 == 0) {                    // chunk gather (stem / MNIST conv1, C padded to 8)
-      if (narrow) launch_cfg<4, 1, 32, 2>(X, Wt, Y, g, taps, stats, bnb, st);
+    if (r.chunk == 8) {
+      if (r.narrow) launch_cfg<4, 1, 32, 2>(X, Wt, Y, g, taps, stats, bnb, st);
       else launch_cfg<2, 2, 32, 2>(X, Wt, Y, g, taps, stats, bnb, st);
     } else {
-      if (narrow) launch_cfg<4, 1, 32, 1>(X, Wt, Y, g, taps, stats, bnb, st);
+      if (r.narrow) launch_cfg<4, 1, 32, 1>(X, Wt, Y, g, taps, stats, bnb, st);
       else launch_cfg<2, 2, 32, 1>(X, Wt, Y, g, taps, stats, bnb, st);
     }
     return;
-  }
-  if (!bnb.part && use_conv_gemm(g, taps)) {
+  case kRtGemm:
     dtf_gemm_conv(X, Wt, Y, g.N, g.H, g.W, g.C, g.P, g.Q, g.sh, g.sw, g.Kout, taps.n, taps.dh,
                   taps.dw, g.Ho, g.Wo, g.osh, g.osw, g.oh0, g.ow0, stats,
                   g.acc == 1 ? Y : nullptr, g.acc == 2 ? g.acc_src : nullptr,
                   g.acc == 2 ? g.acc_mask : nullptr, st);
     return;
-  }
-  if (!epi && use_halo(g, taps) && (!bnb.part || (g_halo_bnb && !stats))) {
-    const int fam = halo_family(g, taps);
-    const int tiles = g.N * (g.H / kHaloTH);
-    if (fam == 1)
-      launch_halo<64, 56, 2, 64>(X, Wt, Y, g, taps, stats, bnb, tiles, (g_halo_st & 1) ? 2 : 1, st);
-    else
-      launch_halo<128, 28, 1, 128>(X, Wt, Y, g, taps, stats, bnb, tiles, (g_halo_st & 2) ? 2 : 1, st);
-    return;
-  }
-  if (!epi && use_dma_kernel((long)m, g.Kout, g.C, taps.n, bk) && g.Kpad % 64 == 0) {
+  case kRtDma: {
     const long tiles = (((long)m + kDmaBM - 1) / kDmaBM) * (g.Kout / kDmaBN);
     if (bnb.part)
       hipLaunchKernelGGL(conv_igemm_dma_kernel<true>, dim3((unsigned)tiles), dim3(kDmaThreads), 0,
@@ -1623,17 +1722,15 @@ void dtf_conv_igemm(const bf16_t* X, const bf16_t* Wt, bf16_t* Y, const ConvGeom
                          st, X, Wt, Y, g, taps, stats, bnb);
     return;
   }
-  // small-K 1x1 convs (one or two 64-deep K-steps: latency-bound blocks): optionally BK 32 with
-  // 16-KB stages -> more blocks per CU (g_small_k bit 1; A/B-measured by tools/conv_bench.py)
-  if ((g_small_k & 2) && taps.n == 1 && g.C <= 128) bk = 32;
-  if ((g_small_k & 4) && taps.n == 1) bk = 32;            // every 1x1 conv
-  if ((g_small_k & 8) && !use_dma_kernel((long)m, g.Kout, g.C, taps.n, 64)) bk = 32;   // all reg.
-  if (bk == 64 && g.C % 64 == 0) {
-    if (narrow) launch_cfg<4, 1, 64, 0>(X, Wt, Y, g, taps, stats, bnb, st);
-    else launch_cfg<2, 2, 64, 0>(X, Wt, Y, g, taps, stats, bnb, st);
-  } else {
-    if (narrow) launch_cfg<4, 1, 32, 0>(X, Wt, Y, g, taps, stats, bnb, st);
-    else launch_cfg<2, 2, 32, 0>(X, Wt, Y, g, taps, stats, bnb, st);
+  case kRtReg:
+    if (r.bk == 64) {
+      if (r.narrow) launch_cfg<4, 1, 64, 0>(X, Wt, Y, g, taps, stats, bnb, st);
+      else launch_cfg<2, 2, 64, 0>(X, Wt, Y, g, taps, stats, bnb, st);
+    } else {
+      if (r.narrow) launch_cfg<4, 1, 32, 0>(X, Wt, Y, g, taps, stats, bnb, st);
+      else launch_cfg<2, 2, 32, 0>(X, Wt, Y, g, taps, stats, bnb, st);
+    }
+    return;
   }
 }
 
@@ -1676,9 +1773,7 @@ bool dtf_conv_igemm_grouped(const bf16_t* X, bf16_t* Y, const ConvGeom& g0, int 
     gc.ow0 = ow0[c];
     gc.Kpad = kpad[c];
     // the kernel dtf_conv_igemm would choose must be the register kernel
-    if (use_conv_gemm(gc, t) || use_halo(gc, t) ||
-        (use_dma_kernel(m, gc.Kout, gc.C, nt, 64) && gc.Kpad % 64 == 0))
-      return false;
+    if (conv_route(gc, t, 64, false, bnb).kind != kRtReg) return false;
     const double wbytes = 2.0 * gc.Kout * gc.Kpad;
     if (wbytes >= 2147483647.0) return false;
     grp.Wt[c] = wts[c];

@@ -1328,6 +1328,67 @@ int dtf_conv_wgrad_splits(long M, int Kout, int TC, long ws_cap, int taps) {
   return (int)((M + mps - 1) / mps);
 }
 
+// ---- the route: which kernel a launch takes.  The ONE copy of the dispatch conditions:
+// dtf_conv_wgrad switches on it and dtf_conv_wgrad_route names it.
+enum WgradKind { kWrHalo, kWrStem, kWrPp, kWrDma, kWrReg };
+struct WgradRoute {
+  WgradKind kind;
+  bool generic;   // register kernel: C % 8 != 0 (element loads)
+  bool tr;        // register kernel: transposing LDS reads (tr_mode bit 0; 0 is the debug path)
+  bool narrow;    // DMA kernel: the 1 x 4 wave (64 x 256) tile
+  bool dense1;    // one-tap unit-stride unpadded layer: no pixel decode (DMA and ping-pong forms)
+  int pipe;       // DMA kernel: g_wgrad_pipe
+  int form, sch;  // ping-pong kernel: its FORM and SCH template arguments
+};
+static WgradRoute wgrad_route(const WgradGeom& g, const TapTableW& taps, int splits, int tr_mode) {
+  if (g.N <= 0 || g.P <= 0 || g.Q <= 0 || g.C <= 0 || g.Kout <= 0)
+    throw std::runtime_error("wgrad: empty geometry");
+  WgradRoute r{kWrReg, (g.C % 8) != 0, (tr_mode & 1) != 0, false, false, g_wgrad_pipe, 0, 0};
+  if (wgrad_halo_ok(g, taps) && splits == wgrad_halo_blocks(g.N, g.H)) {
+    r.kind = kWrHalo;
+    return r;
+  }
+  if (wgrad_stem_ok(g, taps) && splits == wgrad_stem_blocks(g.N)) {
+    r.kind = kWrStem;
+    return r;
+  }
+  const long M = (long)g.N * g.P * g.Q;
+  const int TC = taps.n * g.C;
+  // fdivmod (float reciprocal + one correction step) is exact while m / Q < 2^21; the DMA
+  // kernels pack a pixel's (h, w) as (h << 16) | w
+  const bool dma = g_wgrad_dma_mode != 0 && !r.generic && r.tr && M / g.Q < (1L << 21) &&
+                   g.H < 16000 && g.W < 65536;
+  if (!dma) return r;
+  r.dense1 = (g_wgrad_dense & 1) && taps.n == 1 && taps.dh[0] == 0 && taps.dw[0] == 0 &&
+             g.sh == 1 && g.sw == 1 && g.H == g.P && g.W == g.Q;
+  if (wgrad_pp(g.Kout, TC) && g.ldw % 4 == 0) {
+    r.kind = kWrPp;
+    r.form = r.dense1 ? (g_wgrad_dense == 3 ? 3 : 1)
+                      : g_wgrad_direct == 1 ? 2 : g_wgrad_direct == 2 ? 4 : 0;
+    r.sch = g_wgrad_deep >= 0 && g_wgrad_deep <= 2 ? g_wgrad_deep : 0;
+    if (r.form == 4) r.sch = 0;            // the readlane decode has the default schedule only
+    return r;
+  }
+  r.kind = kWrDma;
+  r.narrow = wgrad_narrow(g.Kout, taps.n);
+  return r;
+}
+
+std::string dtf_conv_wgrad_route(WgradGeom g, const TapTableW& taps, int splits, int tr_mode) {
+  const WgradRoute r = wgrad_route(g, taps, splits, tr_mode);
+  switch (r.kind) {
+  case kWrHalo: return "halo";
+  case kWrStem: return "stem";
+  case kWrPp:
+    return "pp" + std::to_string(r.form) + (r.sch == 1 ? "_deep" : r.sch == 2 ? "_early" : "");
+  case kWrDma:
+    return std::string(r.narrow ? "dma_narrow" : "dma_2x2") + (r.dense1 ? "_dense" : "") +
+           "_pipe" + std::to_string(r.pipe >= 1 && r.pipe <= 3 ? r.pipe : 0);
+  case kWrReg: break;
+  }
+  return std::string(r.generic ? "generic" : "reg") + (r.tr ? "" : "_notr");
+}
+
 // splits == 1 (and not accumulating): dW written directly.  Otherwise `ws` holds splits x Kout x
 // ldw floats; the slabs are summed (in split order) into dW by a second launch, which adds the
 // existing dW last when `accumulate` (direct writes into the flat gradient buffer).
@@ -1338,7 +1399,8 @@ void dtf_conv_wgrad(const bf16_t* X, const bf16_t* dY, float* dW, float* ws, Wgr
   if (g.Kout % 8) throw std::runtime_error("wgrad: Kout % 8 != 0");
   const bool via_ws = splits > 1 || accumulate;
   if (splits < 1 || (via_ws && !ws)) throw std::runtime_error("wgrad: bad split workspace");
-  if (wgrad_halo_ok(g, taps) && splits == wgrad_halo_blocks(g.N, g.H)) {
+  const WgradRoute r = wgrad_route(g, taps, splits, tr_mode);
+  if (r.kind == kWrHalo) {
     if (!ws) throw std::runtime_error("wgrad halo: needs the slab workspace");
     static bool attr = false;
     if (!attr) {
@@ -1352,7 +1414,7 @@ void dtf_conv_wgrad(const bf16_t* X, const bf16_t* dY, float* dW, float* ws, Wgr
     return;
   }
 
-  if (wgrad_stem_ok(g, taps) && splits == wgrad_stem_blocks(g.N)) {
+  if (r.kind == kWrStem) {
     if (!ws) throw std::runtime_error("wgrad stem: needs the slab workspace");
     static bool attr = false;
     if (!attr) {
@@ -1382,18 +1444,11 @@ void dtf_conv_wgrad(const bf16_t* X, const bf16_t* dY, float* dW, float* ws, Wgr
   if (nsplit != splits) throw std::runtime_error("wgrad: split plan mismatch");
   float* target = via_ws ? ws : dW;
   const size_t lds = (size_t)2 * (OPER_A + OPER_B) * sizeof(bf16_t) + 2 * DTF_MAX_TAPS * sizeof(int);
-  const bool generic = (g.C % 8) != 0;
-  // fdivmod (float reciprocal + one correction step) is exact while m / Q < 2^21; the DMA
-  // kernels pack a pixel's (h, w) as (h << 16) | w
-  const bool dma = g_wgrad_dma_mode != 0 && !generic && (tr_mode & 1) && M / g.Q < (1L << 21) &&
-                   g.H < 16000 && g.W < 65536;
-  const bool narrow = dma && wgrad_narrow(g.Kout, taps.n);
+  const bool generic = r.generic, narrow = r.narrow, dense1 = r.dense1;
   const int bm = narrow ? 64 : BM, bn = narrow ? 256 : BN;
   const long tiles = (long)((g.Kout + bm - 1) / bm) * ((TC + bn - 1) / bn);
   const dim3 grid((unsigned)(tiles * nsplit));
-  const bool dense1 = (g_wgrad_dense & 1) && taps.n == 1 && taps.dh[0] == 0 && taps.dw[0] == 0 &&
-                      g.sh == 1 && g.sw == 1 && g.H == g.P && g.W == g.Q;
-  if (dma && wgrad_pp(g.Kout, TC) && g.ldw % 4 == 0) {
+  if (r.kind == kWrPp) {
     static bool attr = false;
     if (!attr) {
       for (const void* k : {(const void*)conv_wgrad_pp_kernel<0>,
@@ -1416,8 +1471,6 @@ void dtf_conv_wgrad(const bf16_t* X, const bf16_t* dY, float* dW, float* ws, Wgr
     }
     const long ptiles = (long)((g.Kout + 255) / 256) * ((TC + 255) / 256);
     const bool deep = g_wgrad_deep == 1;
-    const int form = dense1 ? (g_wgrad_dense == 3 ? 3 : 1)
-                            : g_wgrad_direct == 1 ? 2 : g_wgrad_direct == 2 ? 4 : 0;
     using PpKern = void (*)(const bf16_t*, const bf16_t*, float*, const WgradGeom, const TapTableW,
                             float, float);
     static const PpKern kerns[3][4] = {
@@ -1427,12 +1480,11 @@ void dtf_conv_wgrad(const bf16_t* X, const bf16_t* dY, float* dW, float* ws, Wgr
          conv_wgrad_pp_kernel<3, 1>},
         {conv_wgrad_pp_kernel<0, 2>, conv_wgrad_pp_kernel<1, 2>, conv_wgrad_pp_kernel<2, 2>,
          conv_wgrad_pp_kernel<3, 2>}};
-    const int sch = g_wgrad_deep >= 0 && g_wgrad_deep <= 2 ? g_wgrad_deep : 0;
-    auto kern = form == 4 ? conv_wgrad_pp_kernel<4> : kerns[sch][form];
+    auto kern = r.form == 4 ? conv_wgrad_pp_kernel<4> : kerns[r.sch][r.form];
     hipLaunchKernelGGL(kern, dim3((unsigned)(ptiles * nsplit)), dim3(kPpT),
                        deep ? kPpDeepLDS : kPpLDS, st, X, dY, target, g, taps,
                        1.0f / (float)g.Q, 1.0f / (float)g.P);
-  } else if (dma) {
+  } else if (r.kind == kWrDma) {
     const float iq = 1.0f / (float)g.Q, ip = 1.0f / (float)g.P;
 #define DTF_WGRAD_LAUNCH(WM_, WN_, BK_, NS_)                                                     \
   do {                                                                                           \
@@ -1444,13 +1496,13 @@ void dtf_conv_wgrad(const bf16_t* X, const bf16_t* dY, float* dW, float* ws, Wgr
       hipLaunchKernelGGL((conv_wgrad_dma_kernel<WM_, WN_, BK_, NS_>), grid, dim3(kThreads),     \
                          (WdCfg<WM_, WN_, BK_, NS_>::LDS), st, X, dY, target, g, taps, iq, ip); \
   } while (0)
-    if (g_wgrad_pipe == 1) {   // 32-pixel steps, 4-stage ring (3 steps of DMA in flight)
+    if (r.pipe == 1) {   // 32-pixel steps, 4-stage ring (3 steps of DMA in flight)
       if (narrow) DTF_WGRAD_LAUNCH(1, 4, 32, 4);
       else DTF_WGRAD_LAUNCH(2, 2, 32, 4);
-    } else if (g_wgrad_pipe == 3) {   // 32-pixel steps, double buffer, half epilogue: 4 blk/CU
+    } else if (r.pipe == 3) {   // 32-pixel steps, double buffer, half epilogue: 4 blk/CU
       if (narrow) DTF_WGRAD_LAUNCH(1, 4, 32, 2);
       else DTF_WGRAD_LAUNCH(2, 2, 32, 2);
-    } else if (g_wgrad_pipe == 2) {   // 64-pixel steps, 3-stage ring (1 block / CU)
+    } else if (r.pipe == 2) {   // 64-pixel steps, 3-stage ring (1 block / CU)
       if (narrow) DTF_WGRAD_LAUNCH(1, 4, 64, 3);
       else DTF_WGRAD_LAUNCH(2, 2, 64, 3);
     } else {                   // 64-pixel steps, double buffer
@@ -1458,7 +1510,7 @@ void dtf_conv_wgrad(const bf16_t* X, const bf16_t* dY, float* dW, float* ws, Wgr
       else DTF_WGRAD_LAUNCH(2, 2, 64, 2);
     }
 #undef DTF_WGRAD_LAUNCH
-  } else if (!(tr_mode & 1)) {  // debug path: element-wise LDS reads instead of ds_read_b64_tr_b16
+  } else if (!r.tr) {  // debug path: element-wise LDS reads instead of ds_read_b64_tr_b16
     if (generic) hipLaunchKernelGGL((conv_wgrad_kernel<true, false>), grid, dim3(kThreads), lds, st, X, dY, target, g, taps, tr_mode >> 1);
     else hipLaunchKernelGGL((conv_wgrad_kernel<false, false>), grid, dim3(kThreads), lds, st, X, dY, target, g, taps, tr_mode >> 1);
   } else if (generic) {

@@ -146,6 +146,10 @@ void dtf_conv_set_halo_bnb(int v);
 int dtf_conv_stats_rows(long M, int Kout, int C, int taps, int W);
 void dtf_conv_set_gemm(int v);
 int dtf_conv_tile_rows(const ConvGeom& g, const TapTable& taps, int bnb);
+// the short name of the kernel dtf_conv_igemm launches for these arguments ("halo1", "dma",
+// "reg32_wide", "gather8_narrow", "gemm", "stem", ...): the dispatcher branches on the same function
+std::string dtf_conv_route(const ConvGeom& g, const TapTable& taps, int bk, bool stats,
+                           const BnBwdEpi& bnb);
 void dtf_conv_set_nt(int v);
 bool dtf_conv_bnl_ok(const ConvGeom& g, const TapTable& taps);
 void dtf_conv_igemm(const bf16_t* X, const bf16_t* Wt, bf16_t* Y, const ConvGeom& g_in,
@@ -173,6 +177,9 @@ int dtf_conv_wgrad_halo_splits(int N, int H, int W, int C, int P, int Q, int Kou
 int dtf_conv_wgrad_splits(long M, int Kout, int TC, long ws_cap, int taps);
 void dtf_conv_wgrad(const bf16_t* X, const bf16_t* dY, float* dW, float* ws, WgradGeom g,
                     const TapTableW& taps, int splits, int tr_mode, int accumulate, hipStream_t st);
+// the short name of the kernel dtf_conv_wgrad launches for these arguments ("halo", "stem", "pp1",
+// "dma_narrow_pipe3", "reg", "generic", ...): the dispatcher branches on the same function
+std::string dtf_conv_wgrad_route(WgradGeom g, const TapTableW& taps, int splits, int tr_mode);
 void dtf_slab_reduce(const float* ws, float* out, long n, int nsplit, int accumulate,
                      hipStream_t st);
 int dtf_wgrad_stem_dz_splits(int N);

@@ -480,12 +480,13 @@ def conv2d_wgrad(x, dy, w_shape, stride, padding, out=None):
     geom = [n, h, wd, c, P, Q, sh, sw, K, tc]
     dhs, dws = [t[0] for t in taps], [t[1] for t in taps]
     # stage-1 3x3 layers: the halo kernel (one fp32 slab per block) when it applies
-    splits = _K.conv_wgrad_halo_splits(geom, dhs, dws) or \
-        _K.conv_wgrad_splits(n * P * Q, K, tc, _WGRAD_WS_CAP, R * S)
+    slabbed = _K.conv_wgrad_halo_splits(geom, dhs, dws)
+    splits = slabbed or _K.conv_wgrad_splits(n * P * Q, K, tc, _WGRAD_WS_CAP, R * S)
     acc = out is not None
     dW = out if acc else torch.empty(K, tc, device=x.device, dtype=torch.float32)
+    # the halo / stem kernels write slabs even as one block (N = 1, H = 4: one strip)
     ws = (torch.empty(splits * K * tc, device=x.device, dtype=torch.float32)
-          if splits > 1 or acc else None)
+          if splits > 1 or acc or slabbed else None)
     _K.conv_wgrad(x.data_ptr(), dy.contiguous().data_ptr(), dW.data_ptr(), _p(ws), geom,
                   dhs, dws, splits, _st(), 1, int(acc))
     return dW.reshape(K, R, S, C)

@@ -1089,6 +1089,10 @@ def test_no_record_outlives_its_step():
     # (per-step caches alternating, and the side-stream weight-gradient launches interleaving
     # their allocations with the main stream's differently from step to step: 1.2-3 MB on
     # fresh boxes)
+    # (the peaks also depend on which cached blocks torch's allocator hands out, i.e. on the tests
+    # that ran before this one in the process: alone in a fresh process step 25 is 4.1 MB above
+    # step 2 while the pool warms up over the first five steps.  Files that leave many odd-sized
+    # cached blocks, such as test_conv_kernels_gpu.py, release them when they are done.)
     early, late = max(peaks[1:6]), max(peaks[-5:])
     assert late - early < 4 * 2**20, peaks
     assert max(peaks[1:]) - min(peaks[1:]) < 8 * 2**20, peaks
