@@ -572,6 +572,14 @@ PYBIND11_MODULE(_dtf_hip, m) {
     check_launch("ema_update");
   }, py::arg("avg"), py::arg("var"), py::arg("n"), py::arg("a"), py::arg("max_blocks") = 0,
      py::arg("stream") = (uintptr_t)0);
+  m.def("grad_accumulate", [](uintptr_t dst, uintptr_t src, long n, int mode, int max_blocks,
+                              uintptr_t st) {
+    if (n < 0 || !dst || !src || (mode != 0 && mode != 1))
+      throw std::invalid_argument("grad_accumulate: bad arguments");
+    dtf_grad_accumulate(P<float>(dst), P<const float>(src), n, mode, max_blocks, S(st));
+    check_launch("grad_accumulate");
+  }, py::arg("dst"), py::arg("src"), py::arg("n"), py::arg("mode"), py::arg("max_blocks") = 0,
+     py::arg("stream") = (uintptr_t)0);
   m.def("conv_igemm", [](uintptr_t x, uintptr_t w, uintptr_t y, std::vector<int> geom,
                          std::vector<int> dh, std::vector<int> dw, int bk, uintptr_t st,
                          uintptr_t stats, std::vector<uintptr_t> bnb, uintptr_t acc_src,

@@ -355,6 +355,11 @@ void dtf_cast_f32_bf16(const float* x, bf16_t* y, long n, hipStream_t st);
 // device.  avg / var may start at any element offset.  max_blocks: grid cap, 0 = default.
 void dtf_ema_update(float* avg, const float* var, long n, const float* a_ptr, int max_blocks,
                     hipStream_t st);
+// Gradient accumulation over micro-batches: mode 0 dst[i] = src[i], mode 1 dst[i] = dst[i] + src[i]
+// over [0, n), one fp32 add per element.  dst / src may start at any element offset and must not
+// overlap.  max_blocks: grid cap, 0 = default.
+void dtf_grad_accumulate(float* dst, const float* src, long n, int mode, int max_blocks,
+                         hipStream_t st);
 
 // ---- nlp.hip
 int dtf_bf16_col_sum_ws_floats(int N);

@@ -458,6 +458,38 @@ ema_update_kernel(float* __restrict__ avg, const float* __restrict__ var, long n
   for (long i = head + n4 * 4 + t0; i < n; i += stride) avg[i] = ema_step(avg[i], var[i], a);
 }
 
+// ---- gradient accumulation over micro-batches: dst = src (ADD false) or dst = dst + src (ADD
+// true) over flat fp32 buffers: the store and the add of a held micro-step, and the fold of the
+// accumulator into a bucket's gradient range on the update step.  One IEEE add per element (no
+// multiply next to it, so nothing to contract).  Same layout as the EMA pass: dst and src sit at
+// the same element offset of their flat buffers, a scalar head of `head` elements brings both to
+// 16-byte alignment, then float4, then a scalar tail; buffers misaligned differently get
+// head = n.  Plain loads and stores, one writer per element.
+template <bool ADD>
+__global__ void __launch_bounds__(kT)
+grad_accumulate_kernel(float* __restrict__ dst, const float* __restrict__ src, long n, long head) {
+  const long t0 = (long)blockIdx.x * kT + threadIdx.x;
+  const long stride = (long)gridDim.x * kT;
+  // head <= 3, or n: all scalar
+  for (long i = t0; i < head; i += stride) dst[i] = ADD ? dst[i] + src[i] : src[i];
+  float4* d4 = reinterpret_cast<float4*>(dst + head);
+  const float4* s4 = reinterpret_cast<const float4*>(src + head);
+  const long n4 = (n - head) >> 2;
+  for (long i = t0; i < n4; i += stride) {
+    float4 s = s4[i];
+    if (ADD) {
+      const float4 d = d4[i];
+      s.x = d.x + s.x;
+      s.y = d.y + s.y;
+      s.z = d.z + s.z;
+      s.w = d.w + s.w;
+    }
+    d4[i] = s;
+  }
+  // scalar tail
+  for (long i = head + n4 * 4 + t0; i < n; i += stride) dst[i] = ADD ? dst[i] + src[i] : src[i];
+}
+
 __global__ void __launch_bounds__(kT)
 cast_f32_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, long n) {
   for (long i = (long)blockIdx.x * kT + threadIdx.x; i < n; i += (long)gridDim.x * kT)
@@ -569,4 +601,22 @@ void dtf_ema_update(float* avg, const float* var, long n, const float* a_ptr, in
   int grid = grid_for(n, 4);
   if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
   hipLaunchKernelGGL(ema_update_kernel, dim3(grid), dim3(kT), 0, st, avg, var, n, head, a_ptr);
+}
+
+void dtf_grad_accumulate(float* dst, const float* src, long n, int mode, int max_blocks,
+                         hipStream_t st) {
+  if (n <= 0) return;
+  const uintptr_t pd = reinterpret_cast<uintptr_t>(dst), ps = reinterpret_cast<uintptr_t>(src);
+  // as dtf_ema_update: a bucket or owner range starts at any element of the flat buffers, at
+  // the same one in both; buffers misaligned differently take the scalar path throughout
+  long head = (long)(((16 - (pd & 15)) & 15) >> 2);
+  if ((pd & 15) != (ps & 15) || (pd & 3) || head > n) head = n;
+  int grid = grid_for(n, 4);
+  if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
+  if (mode)
+    hipLaunchKernelGGL(grad_accumulate_kernel<true>, dim3(grid), dim3(kT), 0, st, dst, src, n,
+                       head);
+  else
+    hipLaunchKernelGGL(grad_accumulate_kernel<false>, dim3(grid), dim3(kT), 0, st, dst, src, n,
+                       head);
 }

@@ -74,6 +74,9 @@ def build_parser():
                         "BERT's AdamWeightDecayOptimizer (with --clip_norm 1.0 the BERT recipe)")
     p.add_argument("--clip_norm", type=float, default=None,
                    help="clip every step's gradient to this global norm, inside the fused update")
+    p.add_argument("--accumulation_steps", type=int, default=1,
+                   help="accumulate the gradients of N micro-batches per update (a global batch "
+                        "of batch * replicas * N); steps, logging and hooks count updates")
     p.add_argument("--ema_decay", type=float, default=None,
                    help="keep tf.train.ExponentialMovingAverage(D, num_updates=global_step) of the "
                         "trainable variables inside the fused step; --eval / --eval_every then "
@@ -158,10 +161,12 @@ def _spawn_local(args, argv):
 
 
 def _make_optimizer(name, lr, model_name, batch_global, max_steps=None, clip_norm=None,
-                    variable_averages=None):
+                    variable_averages=None, accumulation_steps=1):
     from . import optimizers as O
     from .optimizers.optimizers import cosine_decay, polynomial_decay
     kw = {} if clip_norm is None else {"clip_norm": clip_norm}
+    if accumulation_steps > 1:
+        kw["accumulation_steps"] = accumulation_steps
     if variable_averages is not None:
         kw["variable_averages"] = variable_averages
     if name == "adam":
@@ -224,6 +229,12 @@ def run(args):
     if args.clip_norm is not None and args.job_name:
         from .optimizers.base import CLIP_BETWEEN_GRAPH
         raise SystemExit(CLIP_BETWEEN_GRAPH)
+    accum = args.accumulation_steps
+    if accum < 1:
+        raise SystemExit(f"--accumulation_steps {accum} must be at least 1")
+    if accum > 1 and args.job_name:
+        from .optimizers.base import ACCUM_BETWEEN_GRAPH
+        raise SystemExit(ACCUM_BETWEEN_GRAPH)
     if args.ema_decay is not None:
         from .optimizers.moving_averages import EMA_BETWEEN_GRAPH
         if args.job_name:
@@ -325,15 +336,15 @@ def run(args):
         ema = None
         if args.ema_decay is not None:
             ema = dtf.train.ExponentialMovingAverage(args.ema_decay, num_updates=global_step)
-        opt = _make_optimizer(opt_name, lr, args.model, batch * nrep, args.max_steps,
-                              args.clip_norm, ema)
+        opt = _make_optimizer(opt_name, lr, args.model, batch * nrep * accum, args.max_steps,
+                              args.clip_norm, ema, accum)
         if args.sync_replicas and server is not None:
             nw = len(server.worker_ranks())
             opt = dtf.train.SyncReplicasOptimizer(
                 opt, replicas_to_aggregate=args.replicas_to_aggregate or nw, total_num_replicas=nw)
         opt.build(list(model.parameters()))
 
-    def train_op():
+    def micro_step():
         if args.model.startswith("bert"):
             b = next(data)
             w = b.get("masked_lm_weights")
@@ -350,7 +361,14 @@ def run(args):
             else:
                 loss = ops.sparse_softmax_cross_entropy(logits, y, args.label_smoothing)
         opt.minimize(loss, global_step=global_step)
-        return {"loss": loss}
+        return loss
+
+    def train_op():
+        # one update per run: hooks, logging and --train_steps count updates
+        if accum == 1:
+            return {"loss": micro_step()}
+        losses = [micro_step().detach().float() for _ in range(accum)]
+        return {"loss": torch.stack(losses).mean()}
 
     # ---- evaluation: every replica of a strategy evaluates its shard; in a between-graph
     # cluster the chief worker alone does, on the variables it pulled
@@ -404,9 +422,11 @@ def run(args):
     if args.clip_norm is not None and last is not None:
         # the last step's pre-clip norm: the one host read of it
         result["grad_norm"] = round(float(opt.last_grad_norm.item()), 6)
+    if accum > 1:
+        result["accumulation_steps"] = accum
     steps_done = global_step.value() - (first_step or 0)
     if steps_done > 0 and server is None:
-        result["examples_per_sec"] = round(steps_done * batch * nrep / elapsed, 1)
+        result["examples_per_sec"] = round(steps_done * batch * nrep * accum / elapsed, 1)
     ev = None
     if eval_fn is not None and args.eval:
         ev = eval_fn()                     # collective: every replica of the strategy is here

@@ -359,6 +359,17 @@ def ema_update(avg, var, a_dev):
     return reference.ema_update(avg, var, a_dev)
 
 
+def grad_accumulate(dst, src, add):
+    """Gradient accumulation over micro-batches, in place over flat fp32 buffers or slices of
+    them: ``dst = src`` (``add`` false: the first held micro-batch) or ``dst += src`` (a later
+    held micro-batch; the fold of the accumulator into a gradient range on the update step).
+    One fp32 add per element, so non-finite values pass through.  Not fenced: it reads no
+    variable."""
+    if _use_native(dst):
+        return _native().grad_accumulate(dst, src, add)
+    return reference.grad_accumulate(dst, src, add)
+
+
 # ----------------------------------------------------------------------------- variable fence
 # A colocated parameter server gathers the updated variable shards AFTER the optimizer step,
 # asynchronously, bucket by bucket, while the next forward already runs (parallel/ps_strategy.py).
@@ -415,5 +426,5 @@ __all__ = [
     "softmax_cross_entropy_clipped_sum", "layer_norm", "gelu", "attention", "dropout",
     "bias_dropout_add_layer_norm", "embedding_layer_norm", "bias_gelu", "bias_gelu_dense",
     "dense_gelu_dense", "attention_qkv", "mlm_loss", "eval_rows", "in_top_k", "augment_images",
-    "mlm_mask_tokens", "ema_update",
+    "mlm_mask_tokens", "ema_update", "grad_accumulate",
 ]

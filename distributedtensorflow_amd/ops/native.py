@@ -2067,6 +2067,19 @@ def ema_update(avg, var, a_dev, max_blocks=0):
     return avg
 
 
+def grad_accumulate(dst, src, add, max_blocks=0):
+    """dst = src (``add`` false) or dst += src in place over flat fp32 buffers (or slices of them,
+    at any element offset); one fp32 add per element.  ``max_blocks`` caps the grid (tests)."""
+    for t in (dst, src):
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("native grad_accumulate needs contiguous fp32 GPU tensors")
+    if dst.numel() != src.numel():
+        raise ValueError("grad_accumulate: dst and src differ in size")
+    _K.grad_accumulate(dst.data_ptr(), src.data_ptr(), dst.numel(), 1 if add else 0,
+                       int(max_blocks), _st())
+    return dst
+
+
 # ----------------------------------------------------------------------------- transformer ops
 # (LayerNorm / GELU / attention for BERT live in .native_nlp to keep this file focused)
 

@@ -550,3 +550,14 @@ def ema_update(avg, var, a_dev):
     with torch.no_grad():
         avg.sub_(a_dev.reshape(()) * (avg - var))
     return avg
+
+
+def grad_accumulate(dst, src, add):
+    """Gradient accumulation's pass in place: ``dst = src``, or ``dst = dst + src`` (one fp32 add
+    per element) when ``add``."""
+    with torch.no_grad():
+        if add:
+            dst.add_(src)
+        else:
+            dst.copy_(src)
+    return dst

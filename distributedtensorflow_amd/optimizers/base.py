@@ -56,6 +56,9 @@ class FlatSpace:
         self.grad = torch.zeros(off, device=dev, dtype=torch.float32)
         self.shadow = (torch.zeros(off, device=dev, dtype=shadow_dtype)
                        if shadow_dtype is not None else None)
+        # gradient accumulation: the held micro-batches' gradient sum, laid out as ``grad``;
+        # allocated by ``Optimizer.build`` only for accumulation_steps > 1
+        self.accum = None
         with torch.no_grad():
             for v, o in zip(self.order, self.offsets):
                 n = v.numel()
@@ -99,6 +102,11 @@ def default_decay_filter(v):
     return not (re.search(r"(batch_norm|_bn/|/gamma|/beta|/bias)", name) or v.dim() <= 1)
 
 
+ACCUM_BETWEEN_GRAPH = ("accumulation_steps > 1 is not available in the between-graph "
+                       "parameter-server mode: the parameter-server tasks apply each pushed "
+                       "gradient on arrival, so a worker has nowhere to hold micro-batches")
+
+
 CLIP_BETWEEN_GRAPH = ("clip_norm is not available in the between-graph parameter-server mode: "
                       "gradient buckets leave the worker from the backward hooks before the "
                       "global norm is known")
@@ -111,7 +119,15 @@ class Optimizer:
     of ``grad_scale * g``, then the update).  One deterministic norm pass over the gradient
     writes the multiplier to the device and the fused update reads it from there: no pass that
     rewrites the gradient, no host sync.  ``last_grad_norm`` (a one-element device tensor) holds
-    the step's pre-clip norm."""
+    the step's pre-clip norm.
+
+    ``accumulation_steps=N``: N consecutive ``minimize`` calls (or ``compute_gradients`` /
+    ``apply_gradients`` pairs) make ONE update.  Calls 1 .. N-1 are held micro-steps: backward
+    runs, the gradient goes into ``space.accum`` (``accum = g1``, then ``accum += g``), nothing
+    is communicated and nothing else moves.  Call N folds the accumulator into the gradient
+    (bucket by bucket, before each bucket's collective) and updates with the gradient
+    multiplier ``grad_scale() / N``: the mean over the N micro-batches of
+    ``((g1 + g2) + ...) + gN``, summed in fp32 in micro-step order."""
 
     slot_names: tuple = ()
     # the update of each element depends only on that element's gradient / slots (a sharded
@@ -120,7 +136,14 @@ class Optimizer:
     elementwise: bool = True
 
     def __init__(self, learning_rate, name, weight_decay=0.0, decay_filter=None,
-                 use_locking=False, clip_norm=None, variable_averages=None):
+                 use_locking=False, clip_norm=None, variable_averages=None,
+                 accumulation_steps=1):
+        if type(accumulation_steps) is not int or accumulation_steps < 1:
+            raise ValueError("accumulation_steps must be an int >= 1, got "
+                             f"{accumulation_steps!r}")
+        self.accumulation_steps = accumulation_steps
+        self._accumulated = 0        # micro-batches held in space.accum
+        self._accum_hold = False     # the last compute_gradients was a held micro-step
         if clip_norm is not None:
             clip_norm = float(clip_norm)
             if not clip_norm > 0.0:
@@ -183,6 +206,8 @@ class Optimizer:
         strat = _strat.get_strategy()
         if self.clip_norm is not None and getattr(strat, "mode", None) == "between_graph":
             raise ValueError(CLIP_BETWEEN_GRAPH)
+        if self.accumulation_steps > 1 and getattr(strat, "mode", None) == "between_graph":
+            raise ValueError(ACCUM_BETWEEN_GRAPH)
         ema = self.variable_averages
         if ema is not None:
             from .moving_averages import EMA_BETWEEN_GRAPH
@@ -198,6 +223,8 @@ class Optimizer:
             else self.shadow_dtype
         self.space = FlatSpace(variables, self.decay_filter, shadow)
         self.space.elementwise = self.elementwise      # read by sharding gradient reducers
+        if self.accumulation_steps > 1:
+            self.space.accum = torch.zeros_like(self.space.grad)
         self._build_slots()
         self._lr_dev = torch.zeros(4, device=dev, dtype=torch.float32)
         self._nonfinite = torch.zeros(1, device=dev, dtype=torch.int32)
@@ -216,6 +243,12 @@ class Optimizer:
         if self.space is None:
             self.build(var_list)
         from .. import profiler
+        if self.accumulation_steps > 1:
+            # calls 1 .. N-1 of an update are held (the reducer communicates nothing); call N
+            # folds the accumulator in before each bucket's collective
+            self._accum_hold = self._accumulated < self.accumulation_steps - 1
+            self._reducer.hold = self._accum_hold
+            self._reducer.fold = not self._accum_hold
         self.space.zero_grad()
         self._reducer.begin_step()
         fn = getattr(loss, "grad_fn", None)
@@ -228,10 +261,18 @@ class Optimizer:
         ops.end_step()
         with profiler.maybe_phase("comm"):
             self._reducer.finish()
+        if self.accumulation_steps > 1:
+            if self._accum_hold:
+                ops.grad_accumulate(self.space.accum, self.space.grad, self._accumulated > 0)
+                self._accumulated += 1
+            else:
+                self._accumulated = 0        # folded into the gradient by the reducer
         return [(v.grad, v) for v in self.space.order]
 
     def apply_gradients(self, grads_and_vars=None, global_step=None):
         assert self.space is not None, "call build()/compute_gradients() first"
+        if self._accum_hold:
+            return None              # a held micro-step: the gradient is in space.accum
         self.iterations += 1
         ema = self.variable_averages
         self._ema_bump = ema is not None and global_step is not None and \
@@ -247,10 +288,27 @@ class Optimizer:
             return step
         from .. import profiler
         with profiler.maybe_phase("optimizer"):
-            self._apply(self._reducer.grad_scale())
+            self._apply(self._gscale())
         if global_step is not None:
             gs.increment(global_step)
         return None
+
+    def _gscale(self):
+        """The update's gradient multiplier: the reducer's cross-replica scale, over the number
+        of accumulated micro-batches (formed in doubles; the kernels take it as fp32)."""
+        g = self._reducer.grad_scale()
+        return g / self.accumulation_steps if self.accumulation_steps > 1 else g
+
+    @property
+    def accumulated(self):
+        """Micro-batches currently held in the accumulator: 0 .. accumulation_steps - 1."""
+        return self._accumulated
+
+    def reset_accumulation(self):
+        """Drop a partial accumulation: the next micro-step is the first of a whole update
+        (after a restore or a cluster recovery; checkpoints do not carry the accumulator)."""
+        self._accumulated = 0
+        self._accum_hold = False
 
     def get_config(self) -> dict:
         """Serializable description (shipped to parameter-server tasks)."""
@@ -264,6 +322,8 @@ class Optimizer:
             # a description only (the parameter-server tasks refuse it): it does not carry
             # ``num_updates`` and no optimizer is rebuilt from it
             cfg["variable_averages"] = self.variable_averages.get_config()
+        if self.accumulation_steps > 1:
+            cfg["accumulation_steps"] = self.accumulation_steps
         return cfg
 
     def minimize(self, loss, global_step=None, var_list=None):

@@ -26,8 +26,8 @@ import torch
 import torch.distributed as dist
 
 from .strategy import (BucketedAllReduce, MirroredStrategy, ReduceOp, Strategy,
-                       _broadcast_training_state, _NullReducer, _torch_op,
-                       collective_cluster_changed, comm_call,
+                       _broadcast_training_state, _NullReducer, _reset_accumulation,
+                       _torch_op, collective_cluster_changed, comm_call,
                        force_reducer_default, init_process_group_from_env, rejoin_collective)
 
 
@@ -508,7 +508,7 @@ class _ColocatedPSReducer(BucketedAllReduce):
         optimizer._clip_held = clip
         try:
             for s, e in mine:
-                optimizer._apply(self.grad_scale(), (s, e))
+                optimizer._apply(optimizer._gscale(), (s, e))
         finally:
             optimizer._clip_held = False
         m = self.space.master
@@ -538,7 +538,7 @@ class _ColocatedPSReducer(BucketedAllReduce):
         ranges it owns (a rank that owns nothing contributes 0), the sums are all-gathered
         (8 bytes per rank) and every rank adds them in rank order -- the same S, and with it
         the same clip multiplier, on every rank."""
-        gs = self.grad_scale()
+        gs = optimizer._gscale()      # 1 / world, over the accumulated micro-batches
         optimizer._grad_norm_pass(gs, mine)
         if self._norm_sums is None:
             self._norm_sums = torch.zeros(self.world, device=self.space.device,
@@ -726,6 +726,7 @@ class ParameterServerStrategy(Strategy):
             (dist.get_world_size() > 1 or self.force_reducer)
 
     def sync_after_restore(self, optimizer, global_step=None, restored=False):
+        _reset_accumulation(optimizer)
         _broadcast_training_state(self.collective, optimizer, global_step, restored=restored)
 
     def cluster_changed(self):

@@ -93,6 +93,12 @@ def force_reducer_default():
 
 
 class _NullReducer:
+    # gradient accumulation (Optimizer.compute_gradients sets both before ``begin_step``):
+    # ``hold`` -- a held micro-step, nothing is communicated and no statistic moves; ``fold`` --
+    # the update step, ``space.accum`` is added into the gradient before it is reduced
+    hold = False
+    fold = False
+
     def __init__(self, space=None):
         self.space = space
 
@@ -100,7 +106,9 @@ class _NullReducer:
         pass
 
     def finish(self):
-        pass
+        if self.fold:
+            from .. import ops
+            ops.grad_accumulate(self.space.grad, self.space.accum, True)
 
     def drain(self):
         """Complete any communication still in flight that writes the variables (the colocated
@@ -164,6 +172,8 @@ class BucketedAllReduce:
                  average=True, compress_bf16=False, overlap=True, comm=None):
         from .comm import C10dComm
         self.space = space
+        self.hold = False            # gradient accumulation: see _NullReducer
+        self.fold = False
         self.group = group
         self.comm = comm if comm is not None else C10dComm(group)
         self.world = dist.get_world_size(group)
@@ -199,6 +209,7 @@ class BucketedAllReduce:
         self.pending = [0] * len(ranges)
         self.works = []
         self.launched = [False] * len(ranges)
+        self.folded = [False] * len(ranges)
         self.stats = CommStats(len(ranges), [(e - s) * 4 for s, e, _ in ranges])
         # collective issue order of the current / last completed step: every rank must issue
         # the same buckets in the same order (verify_bucket_agreement)
@@ -229,11 +240,23 @@ class BucketedAllReduce:
 
     def _make_hook(self, i):
         def hook(_p):
+            if self.hold:
+                return
             b = self.var_bucket[i]
             self.pending[b] -= 1
             if self.pending[b] == 0 and not self._perturb:
+                self._fold(b)
                 self._launch(b)
         return hook
+
+    def _fold(self, b):
+        """The update step of an accumulation: add the held micro-batches' sum into bucket
+        ``b``'s gradient range, once, on the current stream, before the bucket is reduced."""
+        if self.fold and not self.folded[b]:
+            self.folded[b] = True
+            from .. import ops
+            s, e, _ = self.buckets[b]
+            ops.grad_accumulate(self.space.grad[s:e], self.space.accum[s:e], True)
 
     @comm_call
     def _launch(self, b):
@@ -261,8 +284,11 @@ class BucketedAllReduce:
         return dist.all_gather(parts, part, group=self.group, async_op=True), view, parts, L
 
     def begin_step(self):
+        if self.hold:
+            return       # the records of the last communicating step stay
         self.pending = [len(m) for (_, _, m) in self.buckets]
         self.launched = [False] * len(self.buckets)
+        self.folded = [False] * len(self.buckets)
         self.works = []
         self.launch_log = []
 
@@ -297,6 +323,8 @@ class BucketedAllReduce:
 
     @comm_call
     def finish(self):
+        if self.hold:
+            return
         from .watchdog import check as _wd_check
         _wd_check()
         st = self.stats
@@ -310,6 +338,7 @@ class BucketedAllReduce:
         for b in (range(len(self.buckets) - 1, -1, -1) if self._perturb
                   else range(len(self.buckets))):
             if not self.launched[b]:
+                self._fold(b)
                 self._launch(b)
         self.last_order = tuple(self.launch_log)
         gathers = []
@@ -406,7 +435,9 @@ class Strategy:
 
     def sync_after_restore(self, optimizer, global_step=None, restored=False):
         """After the chief restored a checkpoint: make every replica hold the chief's variables,
-        optimizer slots, update count and global step (collective strategies only)."""
+        optimizer slots, update count and global step (collective strategies only).  A partial
+        gradient accumulation is dropped: training restarts at a whole update."""
+        _reset_accumulation(optimizer)
 
 
 class _DefaultStrategy(Strategy):
@@ -435,6 +466,12 @@ def _parse_device(d):
         idx = int(d.split(":")[-1]) if ":" in d else 0
         return torch.device("cuda", idx)
     return torch.device(d)
+
+
+def _reset_accumulation(optimizer):
+    # checkpoints do not carry a partial accumulation
+    if optimizer is not None and hasattr(optimizer, "reset_accumulation"):
+        optimizer.reset_accumulation()
 
 
 def _broadcast_training_state(active, optimizer, global_step=None, src=0, restored=False):
@@ -655,6 +692,7 @@ class MirroredStrategy(Strategy):
         return self._dist
 
     def sync_after_restore(self, optimizer, global_step=None, restored=False):
+        _reset_accumulation(optimizer)
         _broadcast_training_state(self._dist, optimizer, global_step, restored=restored)
 
     def cluster_changed(self):

@@ -22,6 +22,11 @@ Replays are bit-identical to eager steps (same kernels, same order; tests/test_g
 Limits: one process (no collective gradient reducer inside the graph); ops whose per-step
 randomness is drawn on the host (dropout seeds) are frozen by capture, so models with dropout
 are refused.
+
+Gradient accumulation (``accumulation_steps=N``): the step function runs all N micro-steps of one
+update, its static inputs hold the N micro-batches, and the whole update is one graph -- still
+one ``iterations`` and one ``global_step`` per replay.  A step function that leaves a partial
+update is refused: a replay would never finish it.
 """
 from __future__ import annotations
 
@@ -52,6 +57,7 @@ class GraphedTrainStep:
                 out = step_fn(*self.static_inputs)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
+        _check_whole_update(optimizer, "the warm-up")
         if not isinstance(getattr(optimizer, "_reducer", None), _NullReducer):
             raise RuntimeError("GraphedTrainStep captures single-process steps only "
                                f"(gradient reducer {type(optimizer._reducer).__name__})")
@@ -70,6 +76,7 @@ class GraphedTrainStep:
                 self.static_out = step_fn(*self.static_inputs)
         finally:
             optimizer._capturing = False
+        _check_whole_update(optimizer, "the capture")
         if _seed_draws() != draws0:
             raise RuntimeError("GraphedTrainStep: the step draws dropout seeds on the host; a "
                                "captured graph would replay one mask forever")
@@ -91,6 +98,16 @@ class GraphedTrainStep:
         self.graph.replay()
         self.replays += 1
         return self.static_out
+
+
+def _check_whole_update(optimizer, when):
+    held = getattr(optimizer, "accumulated", 0)
+    if held:
+        n = optimizer.accumulation_steps
+        optimizer.reset_accumulation()
+        raise RuntimeError(f"GraphedTrainStep: the step function left {held} of {n} micro-batches "
+                           f"accumulated after {when}; it must run all {n} micro-steps of one "
+                           "update per call (a replay would never finish the partial update)")
 
 
 def _seed_draws():
