@@ -220,6 +220,244 @@ void launch_augment(const uint8_t* images, const int64_t* idx, const int* boxes,
                        static_cast<const OutT*>(lut), static_cast<OutT*>(out), N, B, Hs, Ws, Ho,
                        Wo, fill, tiles, chunks);
 }
+
+// ---- sample mixing (Mixup / CutMix) inside the same launch: dtf_augment_mix_images
+//
+// Row b is mixed with row p = partner[b] of the SAME batch, in the 8-bit pixel domain (the table
+// is affine and the weights sum to 1, so mixing before it equals mixing after it at the source's
+// precision).  With vA the rule above for row b and vB the rule for row p (its own idx, box and
+// flip) at the same output pixel, q = clamp(lam_q[b], 0, 65536) and the cut box
+// (oy0, ox0, h, w) of row b clipped to the output:
+//   v   = vB                                             inside the box
+//       = (q vA + (65536 - q) vB + 32768) >> 16          outside     (<= 65536 * 255 + 32768: int)
+//   out = lut[c][v]
+// A partner outside [0, B) or equal to b leaves the row unmixed (q = 65536, no box).
+//
+// The mapping is augment_kernel's, with a second set of axis tables and a second scalar image
+// base for the partner.  Taps are issued only where their value is used: an item that no box
+// reaches and whose q is 65536 fills no partner tables; a thread's group of 8 pixels reads the
+// partner only if q < 65536 or the box reaches the group, and itself only if q > 0 and the box
+// does not cover the group.  A group that the box edge crosses selects per pixel.
+struct AugTables {
+  int x0[kAugCols], x1[kAugCols], xf[kAugCols];
+  int y0[kAugRows], y1[kAugRows], yf[kAugRows];
+};
+
+struct AugRow {                      // one side's row entry, read once per thread
+  uint32_t ro0, ro1;
+  int fy;
+  bool r0_ok, r1_ok;
+};
+
+DTF_DEV AugRow aug_row(const AugTables& t, int r) {
+  AugRow a;
+  const int yf = t.yf[r];
+  a.ro0 = (uint32_t)t.y0[r];
+  a.ro1 = (uint32_t)t.y1[r];
+  a.fy = yf & 255;
+  a.r0_ok = (yf & kAugTap0) != 0;
+  a.r1_ok = (yf & kAugTap1) != 0;
+  return a;
+}
+
+// One side's tables of an item: the columns of the chunk and the rows of the tile.
+DTF_DEV void aug_fill_tables(AugTables& t, int tid, int rows, int cols, int oy0, int px0,
+                             const int* __restrict__ box, bool fl, bool img_ok, int Hs, int Ws,
+                             int C, int Ho, int Wo) {
+  if (tid < cols) {
+    const int ox = px0 + tid;
+    aug_entry(fl ? Wo - 1 - ox : ox, Wo, box[3], box[1], Ws, C, &t.x0[tid], &t.x1[tid],
+              &t.xf[tid]);
+  }
+  if (tid < rows) {
+    int wf;
+    aug_entry(oy0 + tid, Ho, box[2], box[0], Hs, Ws * C, &t.y0[tid], &t.y1[tid], &wf);
+    t.yf[tid] = img_ok ? wf : (wf & 255);
+  }
+}
+
+// v of the C channels of pixel `pi` of the chunk (vector path: each tap is one load)
+template <int C>
+DTF_DEV void aug_pixel(const uint8_t* __restrict__ img, const AugTables& t, const AugRow& a,
+                       int pi, uint32_t last4, uint32_t fillw, int* v) {
+  const int xf = t.xf[pi], fx = xf & 255;
+  const uint32_t o0 = (uint32_t)t.x0[pi], o1 = (uint32_t)t.x1[pi];
+  const bool c0_ok = (xf & kAugTap0) != 0, c1_ok = (xf & kAugTap1) != 0;
+  const uint32_t w00 = a.r0_ok && c0_ok ? aug_tap<C>(img, a.ro0 + o0, last4) : fillw;
+  const uint32_t w01 = a.r0_ok && c1_ok ? aug_tap<C>(img, a.ro0 + o1, last4) : fillw;
+  const uint32_t w10 = a.r1_ok && c0_ok ? aug_tap<C>(img, a.ro1 + o0, last4) : fillw;
+  const uint32_t w11 = a.r1_ok && c1_ok ? aug_tap<C>(img, a.ro1 + o1, last4) : fillw;
+#pragma unroll
+  for (int c = 0; c < C; ++c)
+    v[c] = aug_blend((w00 >> (8 * c)) & 255, (w01 >> (8 * c)) & 255, (w10 >> (8 * c)) & 255,
+                     (w11 >> (8 * c)) & 255, fx, a.fy);
+}
+
+// v of channel c of pixel `pi` (tail path: one byte per tap; offsets of taps outside are 0)
+DTF_DEV int aug_elem(const uint8_t* __restrict__ img, const AugTables& t, const AugRow& a, int pi,
+                     int c, int fill) {
+  const int xf = t.xf[pi], fx = xf & 255;
+  const uint32_t o0 = (uint32_t)t.x0[pi], o1 = (uint32_t)t.x1[pi];
+  const bool c0_ok = (xf & kAugTap0) != 0, c1_ok = (xf & kAugTap1) != 0;
+  const int v00 = img[a.ro0 + o0 + c], v01 = img[a.ro0 + o1 + c];
+  const int v10 = img[a.ro1 + o0 + c], v11 = img[a.ro1 + o1 + c];
+  const int p00 = a.r0_ok && c0_ok ? v00 : fill, p01 = a.r0_ok && c1_ok ? v01 : fill;
+  const int p10 = a.r1_ok && c0_ok ? v10 : fill, p11 = a.r1_ok && c1_ok ? v11 : fill;
+  return aug_blend(p00, p01, p10, p11, fx, a.fy);
+}
+
+DTF_DEV int aug_mix(int va, int vb, int q, bool inside) {
+  return inside ? vb : (q * va + (65536 - q) * vb + 32768) >> 16;
+}
+
+template <typename OutT, int C, int G>
+__global__ void __launch_bounds__(kAugThreads)
+augment_mix_kernel(const uint8_t* __restrict__ images, const int64_t* __restrict__ idx,
+                   const int* __restrict__ boxes, const uint8_t* __restrict__ flip,
+                   const OutT* __restrict__ lut, const int* __restrict__ partner,
+                   const int* __restrict__ lam_q, const int* __restrict__ cut,
+                   OutT* __restrict__ out, long N, int B, int Hs, int Ws, int Ho, int Wo, int fill,
+                   int tiles, int chunks) {
+  __shared__ OutT s_lut[C * 256];
+  __shared__ AugTables s_a, s_b;                 // row b's and its partner's
+  const int tid = threadIdx.x;
+  for (int i = tid; i < C * 256; i += kAugThreads) s_lut[i] = lut[i];
+
+  const uint32_t per_b = (uint32_t)tiles * (uint32_t)chunks;
+  const uint32_t items = (uint32_t)B * per_b;                        // < 2^31: launcher
+  const int64_t row_elems = (int64_t)Wo * C;
+  const int64_t img_bytes = (int64_t)Hs * Ws * C;
+  const uint32_t last4 = (uint32_t)(Hs * Ws * C - 4);               // vector path: >= 0, launcher
+  const uint32_t fillw = (uint32_t)fill * 0x010101u;
+  for (uint32_t u = blockIdx.x; u < items; u += gridDim.x) {
+    const int b = (int)(u / per_b);
+    const int rem = (int)(u - (uint32_t)b * per_b);
+    const int tile = rem / chunks, chunk = rem - tile * chunks;
+    const int oy0 = tile * kAugRows, px0 = chunk * kAugCols;
+    const int rows = Ho - oy0 < kAugRows ? Ho - oy0 : kAugRows;
+    const int cols = Wo - px0 < kAugCols ? Wo - px0 : kAugCols;
+
+    // the plan of row b, block-uniform: a partner outside the batch, or itself, is no partner
+    const int pr = partner[b];
+    const bool mixed = pr >= 0 && pr < B && pr != b;
+    const int p = mixed ? pr : b;
+    int q = lam_q[b];
+    q = !mixed || q > 65536 ? 65536 : (q < 0 ? 0 : q);
+    // the cut box clipped to the output, [cy0, cy1) x [cx0, cx1); empty: cy1 <= cy0
+    int cy0 = 0, cy1 = 0, cx0 = 0, cx1 = 0;
+    if (mixed && cut[4 * b + 2] > 0 && cut[4 * b + 3] > 0) {
+      const int64_t y = cut[4 * b], x = cut[4 * b + 1];
+      const int64_t ye = y + cut[4 * b + 2], xe = x + cut[4 * b + 3];
+      cy0 = (int)(y < 0 ? 0 : (y > Ho ? Ho : y));
+      cx0 = (int)(x < 0 ? 0 : (x > Wo ? Wo : x));
+      cy1 = (int)(ye < 0 ? 0 : (ye > Ho ? Ho : ye));
+      cx1 = (int)(xe < 0 ? 0 : (xe > Wo ? Wo : xe));
+      if (cx1 <= cx0) cy1 = cy0;
+    }
+    const bool box_here = cy0 < oy0 + rows && cy1 > oy0 && cx0 < px0 + cols && cx1 > px0 &&
+                          cy1 > cy0;
+    const bool need_b = q < 65536 || box_here;   // block-uniform
+
+    // the partner's index hangs on partner[b]: a second load latency, paid only where it is used
+    const int64_t na = idx[b], nb = need_b ? idx[p] : na;
+    const bool a_ok = na >= 0 && na < N, b_ok = nb >= 0 && nb < N;   // a bad index reads as fill
+    const uint8_t* img_a = images + (a_ok ? na : 0) * img_bytes;     // block-uniform
+    const uint8_t* img_b = images + (b_ok ? nb : 0) * img_bytes;
+
+    __syncthreads();                 // the previous item's table reads (and the LUT staging)
+    aug_fill_tables(s_a, tid, rows, cols, oy0, px0, boxes + 4 * b, flip[b] != 0, a_ok, Hs, Ws, C,
+                    Ho, Wo);
+    if (need_b)
+      aug_fill_tables(s_b, tid, rows, cols, oy0, px0, boxes + 4 * p, flip[p] != 0, b_ok, Hs, Ws,
+                      C, Ho, Wo);
+    __syncthreads();
+
+    const int g0 = px0 * C / G, gpc = cols * C / G;       // this chunk's groups of a row
+    const float inv_gpc = 1.0f / (float)gpc;
+    for (int k = tid; k < rows * gpc; k += kAugThreads) {
+      int r = (int)(((float)k + 0.5f) * inv_gpc);          // k / gpc, r < 16: fixed up below
+      r = r * gpc > k ? r - 1 : r;
+      r = (r + 1) * gpc <= k ? r + 1 : r;
+      const int g = k - r * gpc;
+      const int oy = oy0 + r;
+      const bool in_y = oy >= cy0 && oy < cy1;
+      const AugRow ra = aug_row(s_a, r);
+      AugRow rb = ra;
+      if (need_b) rb = aug_row(s_b, r);
+
+      OutT res[G];
+      if constexpr (G == 1) {
+        const int pi = g / C, c = g - pi * C, ox = px0 + pi;
+        const bool inside = in_y && ox >= cx0 && ox < cx1;
+        const bool use_a = !inside && q > 0, use_b = inside || q < 65536;
+        const int va = use_a ? aug_elem(img_a, s_a, ra, pi, c, fill) : 0;
+        const int vb = use_b ? aug_elem(img_b, s_b, rb, pi, c, fill) : 0;
+        res[0] = s_lut[c * 256 + aug_mix(va, vb, q, inside)];
+      } else {
+        // the box's columns inside this group of 8 pixels: [lo, hi)
+        const int gx = px0 + g * 8;
+        const int lo = cx0 > gx ? cx0 : gx, hi = cx1 < gx + 8 ? cx1 : gx + 8;
+        const int n_in = in_y && hi > lo ? hi - lo : 0;
+        const bool use_a = n_in < 8 && q > 0, use_b = n_in > 0 || q < 65536;
+#pragma unroll
+        for (int px = 0; px < 8; ++px) {
+          const int pi = g * 8 + px;
+          const bool inside = n_in > 0 && gx + px >= lo && gx + px < hi;
+          int va[C], vb[C];
+#pragma unroll
+          for (int c = 0; c < C; ++c) va[c] = vb[c] = 0;
+          if (use_a) aug_pixel<C>(img_a, s_a, ra, pi, last4, fillw, va);
+          if (use_b) aug_pixel<C>(img_b, s_b, rb, pi, last4, fillw, vb);
+#pragma unroll
+          for (int c = 0; c < C; ++c)
+            res[px * C + c] = s_lut[c * 256 + aug_mix(va[c], vb[c], q, inside)];
+        }
+      }
+
+      OutT* dst = out + ((int64_t)b * Ho + oy) * row_elems + (int64_t)(g0 + g) * G;
+      if constexpr (G == 1) {
+        dst[0] = res[0];
+      } else if constexpr (sizeof(OutT) == 2) {
+#pragma unroll
+        for (int w4 = 0; w4 < G / 8; ++w4) {
+          const OutT* h = res + 8 * w4;
+          uint4 w;                     // the table already holds bf16 bits: pack them as they are
+          w.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
+          w.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
+          w.z = (uint32_t)h[4] | ((uint32_t)h[5] << 16);
+          w.w = (uint32_t)h[6] | ((uint32_t)h[7] << 16);
+          reinterpret_cast<uint4*>(dst)[w4] = w;
+        }
+      } else {
+#pragma unroll
+        for (int w4 = 0; w4 < G / 4; ++w4)
+          reinterpret_cast<float4*>(dst)[w4] =
+              make_float4(res[4 * w4], res[4 * w4 + 1], res[4 * w4 + 2], res[4 * w4 + 3]);
+      }
+    }
+  }
+}
+
+template <typename OutT, int C>
+void launch_augment_mix(const uint8_t* images, const int64_t* idx, const int* boxes,
+                        const uint8_t* flip, const void* lut, const int* partner,
+                        const int* lam_q, const int* cut, void* out, long N, int B, int Hs, int Ws,
+                        int Ho, int Wo, int fill, int max_blocks, hipStream_t st) {
+  const bool vec = (Wo * C) % 8 == 0 && (long)Hs * Ws * C >= 4;      // as launch_augment
+  const int tiles = (Ho + kAugRows - 1) / kAugRows, chunks = (Wo + kAugCols - 1) / kAugCols;
+  const long items = (long)B * tiles * chunks;
+  if (items >= 2147483647L) throw std::runtime_error("augment_mix_images: batch too large");
+  const long cap = max_blocks > 0 ? max_blocks : kAugDefaultBlocks;
+  const dim3 grid((unsigned)(items < cap ? items : cap)), block(kAugThreads);
+  if (vec)
+    hipLaunchKernelGGL((augment_mix_kernel<OutT, C, 8 * C>), grid, block, 0, st, images, idx,
+                       boxes, flip, static_cast<const OutT*>(lut), partner, lam_q, cut,
+                       static_cast<OutT*>(out), N, B, Hs, Ws, Ho, Wo, fill, tiles, chunks);
+  else
+    hipLaunchKernelGGL((augment_mix_kernel<OutT, C, 1>), grid, block, 0, st, images, idx, boxes,
+                       flip, static_cast<const OutT*>(lut), partner, lam_q, cut,
+                       static_cast<OutT*>(out), N, B, Hs, Ws, Ho, Wo, fill, tiles, chunks);
+}
 }  // namespace
 
 void dtf_augment_images(const uint8_t* images, const int64_t* idx, const int* boxes,
@@ -239,6 +477,31 @@ void dtf_augment_images(const uint8_t* images, const int64_t* idx, const int* bo
 #define DTF_AUG(T, CC)                                                                          \
   launch_augment<T, CC>(images, idx, boxes, flip, lut, out, N, B, Hs, Ws, Ho, Wo, fill,         \
                         max_blocks, st)
+  if (out_bf16) {
+    if (C == 3) DTF_AUG(bf16_t, 3); else DTF_AUG(bf16_t, 1);
+  } else {
+    if (C == 3) DTF_AUG(float, 3); else DTF_AUG(float, 1);
+  }
+#undef DTF_AUG
+}
+
+void dtf_augment_mix_images(const uint8_t* images, const int64_t* idx, const int* boxes,
+                            const uint8_t* flip, const void* lut, const int* partner,
+                            const int* lam_q, const int* cut, void* out, long N, int B, int Hs,
+                            int Ws, int C, int Ho, int Wo, int fill, int out_bf16, int max_blocks,
+                            hipStream_t st) {
+  // the same limits as dtf_augment_images
+  if (C != 1 && C != 3) throw std::runtime_error("augment_mix_images: C must be 1 or 3");
+  if (N < 1 || Hs < 1 || Ws < 1) throw std::runtime_error("augment_mix_images: empty image set");
+  if (B < 0 || Ho < 1 || Wo < 1) throw std::runtime_error("augment_mix_images: bad output shape");
+  if ((long)Hs * Ws * C > 2147483647L || Ho > (1 << 20) || Wo > (1 << 20))
+    throw std::runtime_error("augment_mix_images: one image must stay below 2 GiB");
+  if (fill < 0 || fill > 255) throw std::runtime_error("augment_mix_images: fill must be one byte");
+  if (max_blocks < 0) throw std::runtime_error("augment_mix_images: negative max_blocks");
+  if (B == 0) return;
+#define DTF_AUG(T, CC)                                                                          \
+  launch_augment_mix<T, CC>(images, idx, boxes, flip, lut, partner, lam_q, cut, out, N, B, Hs,  \
+                            Ws, Ho, Wo, fill, max_blocks, st)
   if (out_bf16) {
     if (C == 3) DTF_AUG(bf16_t, 3); else DTF_AUG(bf16_t, 1);
   } else {

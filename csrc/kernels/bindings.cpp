@@ -154,6 +154,16 @@ PYBIND11_MODULE(_dtf_hip, m) {
                        max_blocks, S(st));
     check_launch("augment_images");
   });
+  m.def("augment_mix_images", [](uintptr_t images, uintptr_t idx, uintptr_t boxes, uintptr_t flip,
+                                 uintptr_t lut, uintptr_t partner, uintptr_t lam_q, uintptr_t cut,
+                                 uintptr_t out, long N, int B, int Hs, int Ws, int C, int Ho,
+                                 int Wo, int fill, int out_bf16, int max_blocks, uintptr_t st) {
+    dtf_augment_mix_images(P<uint8_t>(images), P<int64_t>(idx), P<int>(boxes), P<uint8_t>(flip),
+                           P<void>(lut), P<int>(partner), P<int>(lam_q), P<int>(cut),
+                           P<void>(out), N, B, Hs, Ws, C, Ho, Wo, fill, out_bf16, max_blocks,
+                           S(st));
+    check_launch("augment_mix_images");
+  });
   // rule = [vocab_size, pad_id, cls_id, sep_id, mask_id, random_low, prob_q16];
   // outs = [input_ids, segment_ids, input_mask, masked_lm_positions, masked_lm_ids,
   //         masked_lm_weights]
@@ -470,6 +480,14 @@ PYBIND11_MODULE(_dtf_hip, m) {
     dtf_softmax_xent_smooth(P<const float>(logits), P<const void>(labels), label_bytes, B, V,
                             P<float>(loss_rows), P<float>(grad), gscale, smoothing, S(st));
     check_launch("softmax_xent_smooth");
+  });
+  m.def("softmax_xent_pair", [](uintptr_t logits, uintptr_t labels_a, uintptr_t labels_b,
+                                int label_bytes, uintptr_t lam, int B, int V, uintptr_t loss_rows,
+                                uintptr_t grad, float gscale, float smoothing, uintptr_t st) {
+    dtf_softmax_xent_pair(P<const float>(logits), P<const void>(labels_a),
+                          P<const void>(labels_b), label_bytes, P<const float>(lam), B, V,
+                          P<float>(loss_rows), P<float>(grad), gscale, smoothing, S(st));
+    check_launch("softmax_xent_pair");
   });
   // the update kernels: ``gmul`` (trailing keyword, 0 = none) is the device address of the clip
   // multiplier a grad_norm pass wrote; when set it replaces ``gscale``

@@ -292,6 +292,13 @@ void dtf_augment_images(const uint8_t* images, const int64_t* idx, const int* bo
                         const uint8_t* flip, const void* lut, void* out, long N, int B, int Hs,
                         int Ws, int C, int Ho, int Wo, int fill, int out_bf16, int max_blocks,
                         hipStream_t st);
+// the same, row b mixed with row partner[b] of the batch (Mixup weight lam_q / 65536, CutMix box
+// cut[b] = (oy0, ox0, h, w) in output pixels)
+void dtf_augment_mix_images(const uint8_t* images, const int64_t* idx, const int* boxes,
+                            const uint8_t* flip, const void* lut, const int* partner,
+                            const int* lam_q, const int* cut, void* out, long N, int B, int Hs,
+                            int Ws, int C, int Ho, int Wo, int fill, int out_bf16, int max_blocks,
+                            hipStream_t st);
 
 // ---- mlm_mask.hip
 // the masking settings (data.TokenMasking), a kernel argument by value
@@ -312,6 +319,10 @@ void dtf_softmax_xent(const float* logits, const void* labels, int label_bytes, 
 void dtf_softmax_xent_smooth(const float* logits, const void* labels, int label_bytes, int B, int V,
                              float* loss_rows, float* grad, float grad_scale, float smoothing,
                              hipStream_t st);
+// two labels per row, weighted lam[b] and 1 - lam[b] (Mixup / CutMix); smoothing = 0 allowed
+void dtf_softmax_xent_pair(const float* logits, const void* labels_a, const void* labels_b,
+                           int label_bytes, const float* lam, int B, int V, float* loss_rows,
+                           float* grad, float grad_scale, float smoothing, hipStream_t st);
 
 // ---- metrics.hip
 void dtf_eval_rows(uintptr_t logits, int elem_bytes, const void* labels, int label_bytes, int N,

@@ -110,6 +110,12 @@ def build_parser():
     p.add_argument("--augment", choices=("rrc", "pad_crop", "none"), default="rrc",
                    help="training transform with --image_data: random-resized-crop, pad 4 + "
                         "crop, or resize only (each with random flips)")
+    p.add_argument("--mixup_alpha", type=float, default=0.0,
+                   help="with --image_data: Mixup of each training batch inside the augmentation "
+                        "kernel, blend weight ~ Beta(A, A); the loss becomes the two-label one")
+    p.add_argument("--cutmix_alpha", type=float, default=0.0,
+                   help="with --image_data: CutMix, box area share ~ Beta(A, A); with "
+                        "--mixup_alpha too, each batch draws one of the two")
     p.add_argument("--num_classes", type=int, default=None,
                    help="classes of the --image_data set (default: 1000 for ResNet, 10 for MNIST "
                         "models)")
@@ -135,6 +141,13 @@ def check_data_args(args):
             raise SystemExit(f"--mlm_prob {args.mlm_prob} outside [0, 1]")
         if args.max_predictions < 1:
             raise SystemExit(f"--max_predictions {args.max_predictions} must be at least 1")
+    if args.mixup_alpha or args.cutmix_alpha:
+        if args.mixup_alpha < 0 or args.cutmix_alpha < 0:
+            raise SystemExit("--mixup_alpha and --cutmix_alpha must be >= 0")
+        if args.model.startswith("bert") or args.model == "mnist_mlp":
+            raise SystemExit(f"--mixup_alpha / --cutmix_alpha: {args.model} has no two-label loss")
+        if not args.image_data:
+            raise SystemExit("--mixup_alpha / --cutmix_alpha need --image_data")
 
 
 DEFAULTS = {   # (batch, optimizer, learning rate) per model
@@ -212,6 +225,7 @@ def run(args):
 
     import distributedtensorflow_amd as dtf
     from . import ops
+    from .data import MixedLabels
     from .parallel import (MirroredStrategy, MultiWorkerMirroredStrategy, OneDeviceStrategy,
                            ParameterServerStrategy)
     from .summary import logger
@@ -355,7 +369,9 @@ def run(args):
         else:
             x, y = next(data)
             logits = model(x)
-            if args.model == "mnist_mlp":
+            if isinstance(y, MixedLabels):
+                loss = ops.mixed_softmax_cross_entropy(logits, *y, args.label_smoothing)
+            elif args.model == "mnist_mlp":
                 onehot = torch.nn.functional.one_hot(y, 10).to(logits.dtype)
                 loss = ops.softmax_cross_entropy_clipped_sum(logits, onehot)
             else:
@@ -424,6 +440,9 @@ def run(args):
         result["grad_norm"] = round(float(opt.last_grad_norm.item()), 6)
     if accum > 1:
         result["accumulation_steps"] = accum
+    for k in ("mixup_alpha", "cutmix_alpha"):
+        if getattr(args, k):
+            result[k] = getattr(args, k)
     steps_done = global_step.value() - (first_step or 0)
     if steps_done > 0 and server is None:
         result["examples_per_sec"] = round(steps_done * batch * nrep * accum / elapsed, 1)
@@ -454,7 +473,7 @@ def _image_dataset(args, split, num_classes, batch, device, dtype, shards, shard
     """--image_data: the HBM-resident ``split`` of DIR as a DeviceImageDataset.  ResNets get
     --image_size outputs under the ImageNet channel statistics, the MNIST models 28 x 28 x 1
     scaled to [0, 1]; the batch shrinks to the shard where that is smaller."""
-    from .data import DeviceImageDataset, ImageAugment, images
+    from .data import DeviceImageDataset, ImageAugment, ImageMix, images
     from .data.images import IMAGENET_MEAN, IMAGENET_STD
     imgs, labels = images.load_arrays(args.image_data, split, num_classes)
     C = imgs.shape[3]
@@ -471,11 +490,15 @@ def _image_dataset(args, split, num_classes, batch, device, dtype, shards, shard
     batch = max(1, min(batch, len(range(shard_index, len(labels), shards))))
     # between-graph workers all hold the whole set: each shuffles and augments on its own stream
     stream = args.task_index if args.job_name else shard_index
+    mix = None
+    if split == "train" and (args.mixup_alpha or args.cutmix_alpha):
+        mix = ImageMix(args.mixup_alpha, args.cutmix_alpha)
     return DeviceImageDataset(imgs, labels, batch, device, aug, dtype=dtype,
                               shuffle=split == "train", seed=args.seed + stream,
                               aug_seed=args.seed + 1000003 * (stream + 1),
                               num_shards=shards, shard_index=shard_index,
-                              flatten=args.model == "mnist_mlp")
+                              flatten=args.model == "mnist_mlp", mix=mix,
+                              mix_seed=args.seed + 2000003 * (stream + 1))
 
 
 def _token_dataset(args, split, batch, device, shards, shard_index):

@@ -4,10 +4,11 @@ on-device masked-LM example creation), synthetic ImageNet / MLM generators for b
 from . import images, mnist, tokens
 from .dataset import Dataset, Iterator, NativeBatchDataset
 from .device import DeviceArrayDataset
-from .images import DeviceImageDataset, ImageAugment
+from .images import DeviceImageDataset, ImageAugment, ImageMix, MixedLabels, mix_plan
 from .synthetic import SyntheticImageNet, SyntheticMLM
 from .tokens import DeviceTokenDataset, TokenMasking, load_token_arrays
 
 __all__ = ["images", "mnist", "tokens", "Dataset", "DeviceArrayDataset", "DeviceImageDataset",
-           "DeviceTokenDataset", "ImageAugment", "Iterator", "NativeBatchDataset",
-           "SyntheticImageNet", "SyntheticMLM", "TokenMasking", "load_token_arrays"]
+           "DeviceTokenDataset", "ImageAugment", "ImageMix", "Iterator", "MixedLabels",
+           "NativeBatchDataset", "SyntheticImageNet", "SyntheticMLM", "TokenMasking",
+           "load_token_arrays", "mix_plan"]

@@ -16,9 +16,15 @@ On disk a set is two arrays per split in one directory (:func:`load_arrays`):
 
 Crop boxes are (y0, x0, h, w) in source pixels, int32, one pure function per mode:
 :func:`rrc_boxes`, :func:`pad_crop_boxes`, :func:`center_boxes`.
+
+Sample mixing (:class:`ImageMix`: Mixup, CutMix) happens in the same kernel
+(``ops.augment_mix_images``): :func:`mix_plan` turns the draws of a third CPU generator into each
+row's partner, blend weight and cut box, and the batch's labels become
+:class:`MixedLabels` for ``ops.mixed_softmax_cross_entropy``.
 """
 from __future__ import annotations
 
+import collections
 import math
 import os
 
@@ -123,6 +129,113 @@ def center_boxes(Hs, Ws, fraction=0.875):
     return torch.tensor([[(Hs - h) // 2, (Ws - w) // 2, h, w]], dtype=torch.int32)
 
 
+# ----------------------------------------------------------------------------- sample mixing
+
+MixedLabels = collections.namedtuple("MixedLabels", ["labels_a", "labels_b", "lam"])
+MixedLabels.__doc__ = """The labels of a mixed batch: the target of row b is ``lam[b]`` of class
+``labels_a[b]`` and ``1 - lam[b]`` of class ``labels_b[b]`` (``lam`` fp32 [B]); the arguments of
+``ops.mixed_softmax_cross_entropy`` in order."""
+
+
+class ImageMix:
+    """Mixup (Zhang et al. 2018) and CutMix (Yun et al. 2019) of a :class:`DeviceImageDataset`,
+    with timm's ``Mixup`` semantics.  ``mixup_alpha`` / ``cutmix_alpha``: the Beta(alpha, alpha)
+    parameters, 0 = that method off.  ``prob``: the chance that a batch (an example) is mixed at
+    all.  ``switch_prob``: with both methods on, the chance of CutMix.  ``mode``: "batch" (one
+    draw per batch) or "elem" (one per example).  Row b's partner is row B - 1 - b."""
+
+    MODES = ("batch", "elem")
+
+    def __init__(self, mixup_alpha=0.0, cutmix_alpha=0.0, prob=1.0, switch_prob=0.5,
+                 mode="batch"):
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        self.prob, self.switch_prob = float(prob), float(switch_prob)
+        if not (self.mixup_alpha >= 0 and self.cutmix_alpha >= 0) or \
+                math.isinf(self.mixup_alpha) or math.isinf(self.cutmix_alpha):
+            raise ValueError("ImageMix: the alphas must be finite and >= 0")
+        if self.mixup_alpha == 0 and self.cutmix_alpha == 0:
+            raise ValueError("ImageMix: one of mixup_alpha and cutmix_alpha must be > 0")
+        if not (0 <= self.prob <= 1 and 0 <= self.switch_prob <= 1):
+            raise ValueError("ImageMix: prob and switch_prob must be in [0, 1]")
+        if mode not in self.MODES:
+            raise ValueError(f"ImageMix: mode {mode!r} not in {self.MODES}")
+        self.mode = mode
+
+    def draw(self, B, generator):
+        """The draws of one batch from ``generator`` (CPU) -> (u, g) for :func:`mix_plan`:
+        ``u`` float64 [R, 4] uniforms, then ``g`` = (Mixup's, CutMix's) float64 [R, 2] standard
+        gammas of shape alpha, None for an alpha of 0; R = 1 per batch, B per example."""
+        R = B if self.mode == "elem" else 1
+        u = torch.rand(R, 4, generator=generator, dtype=torch.float64, device="cpu")
+        g = tuple(torch._standard_gamma(torch.full((R, 2), a, dtype=torch.float64, device="cpu"),
+                                        generator) if a > 0 else None
+                  for a in (self.mixup_alpha, self.cutmix_alpha))
+        return u, g
+
+
+def mix_plan(u, g, B, out_hw, mix):
+    """The mixing plan of one batch from supplied draws (:meth:`ImageMix.draw`), computed on the
+    host in float64 -> (partner int32 [B], lam_q int32 [B], cut int32 [B, 4], lam fp32 [B]).
+
+    Per draw row (one for the batch, or one per example): applied iff ``u0 < prob``; CutMix iff
+    only ``cutmix_alpha > 0``, or both are and ``u1 < switch_prob``; ``l = g0 / (g0 + g1)`` of
+    the chosen method's gammas (0.5 if the sum is 0), a Beta(alpha, alpha) draw.
+    Mixup: ``lam_q = floor(l 65536 + 0.5)``, ``lam = lam_q / 65536``, no box.
+    CutMix (timm's ``rand_bbox``): ``r = sqrt(1 - l)``, box size ``(floor(Ho r), floor(Wo r))``,
+    centre ``(min(floor(u2 Ho), Ho - 1), min(floor(u3 Wo), Wo - 1))``, edges
+    ``clamp(centre -/+ size // 2, 0, O)``; ``lam_q = 65536`` and ``lam = 1 - area / (Ho Wo)`` of
+    the clipped box.  Not applied: ``lam_q = 65536``, no box, ``lam = 1``.
+    ``partner[b] = B - 1 - b``."""
+    Ho, Wo = (int(v) for v in out_hw)
+    R = B if mix.mode == "elem" else 1
+    if tuple(u.shape) != (R, 4):
+        raise ValueError(f"mix_plan: u must be [{R}, 4]")
+    g_mix, g_cut = g
+    for a, t in ((mix.mixup_alpha, g_mix), (mix.cutmix_alpha, g_cut)):
+        if (a > 0) != (t is not None) or (t is not None and tuple(t.shape) != (R, 2)):
+            raise ValueError(f"mix_plan: g holds one [{R}, 2] draw per alpha > 0, else None")
+    u = u.to(torch.float64)           # the plan is formed on the host, whatever the default
+
+    def beta(t):
+        t = t.to(torch.float64)
+        s = t[:, 0] + t[:, 1]
+        return torch.where(s > 0, t[:, 0] / torch.where(s > 0, s, torch.ones_like(s)),
+                           torch.full_like(s, 0.5))
+
+    applied = u[:, 0] < mix.prob
+    if g_mix is None:
+        is_cut = torch.ones(R, dtype=torch.bool, device="cpu")
+    elif g_cut is None:
+        is_cut = torch.zeros(R, dtype=torch.bool, device="cpu")
+    else:
+        is_cut = u[:, 1] < mix.switch_prob
+    zero = torch.zeros(R, dtype=torch.float64, device="cpu")
+    l_mix = beta(g_mix) if g_mix is not None else zero + 1.0
+    l_cut = beta(g_cut) if g_cut is not None else zero + 1.0
+
+    q_mix = torch.floor(l_mix * 65536.0 + 0.5)
+    r = torch.sqrt(1.0 - l_cut)
+    ch, cw = torch.floor(Ho * r), torch.floor(Wo * r)
+    cy = torch.clamp(torch.floor(u[:, 2] * Ho), max=Ho - 1)
+    cx = torch.clamp(torch.floor(u[:, 3] * Wo), max=Wo - 1)
+    hy, hx = torch.floor(ch / 2), torch.floor(cw / 2)
+    y_lo, y_hi = torch.clamp(cy - hy, 0, Ho), torch.clamp(cy + hy, 0, Ho)
+    x_lo, x_hi = torch.clamp(cx - hx, 0, Wo), torch.clamp(cx + hx, 0, Wo)
+    box = torch.stack([y_lo, x_lo, y_hi - y_lo, x_hi - x_lo], dim=1)
+    lam_cut = 1.0 - (y_hi - y_lo) * (x_hi - x_lo) / float(Ho * Wo)
+
+    cutting = applied & is_cut
+    lam_q = torch.where(applied & ~is_cut, q_mix, zero + 65536.0)
+    lam = torch.where(cutting, lam_cut, lam_q / 65536.0)
+    cut = torch.where(cutting.unsqueeze(1), box, torch.zeros_like(box))
+    if float(lam.min()) < 0.0 or float(lam.max()) > 1.0:
+        raise ValueError("mix_plan: lam outside [0, 1]")
+    partner = torch.arange(B - 1, -1, -1, dtype=torch.int32, device="cpu")
+    return (partner, lam_q.to(torch.int32).expand(B).contiguous(),
+            cut.to(torch.int32).expand(B, 4).contiguous(),
+            lam.to(torch.float32).expand(B).contiguous())
+
+
 # ----------------------------------------------------------------------------- the dataset
 
 class ImageAugment:
@@ -179,13 +292,18 @@ class DeviceImageDataset(DeviceArrayDataset):
     second, CPU generator (``aug_seed``), so the order is the same with and without augmentation
     and the same seeds give the same batches on the CPU and on the GPU.
 
+    ``mix``: an :class:`ImageMix`.  Training batches are then mixed inside the same kernel
+    (``ops.augment_mix_images``) and ``__next__`` yields ``(x, MixedLabels)``; the plan's draws
+    come from a third CPU generator (``mix_seed``), so example order and crops are those of the
+    unmixed dataset.  ``single_pass()`` never mixes.
+
     Upload: the (possibly memory-mapped) array is copied ``chunk_bytes`` at a time into a
     preallocated device tensor, the shard selection applied per chunk, so the host never holds
     a second copy of the set.  ``flatten``: batches are [B, Ho * Wo * C] (the MLP's input)."""
 
     def __init__(self, images, labels, batch_size, device, augment, dtype=None, shuffle=False,
                  seed=0, aug_seed=0, num_shards=1, shard_index=0, drop_remainder=True,
-                 chunk_bytes=256 << 20, flatten=False):
+                 chunk_bytes=256 << 20, flatten=False, mix=None, mix_seed=0):
         device = torch.device(device)
         if images.dtype != np.uint8 or images.ndim != 4 or images.shape[3] not in (1, 3):
             raise ValueError("DeviceImageDataset: images must be uint8 [N, H, W, C], C in (1, 3)")
@@ -220,6 +338,12 @@ class DeviceImageDataset(DeviceArrayDataset):
         self._aug_gen.manual_seed(aug_seed)
         self._eval_box = center_boxes(Hs, Ws, augment.eval_fraction).to(device)
         self._whole_box = torch.tensor([[0, 0, Hs, Ws]], dtype=torch.int32, device=device)
+        if mix is not None and not isinstance(mix, ImageMix):
+            raise ValueError("DeviceImageDataset: mix must be an ImageMix")
+        self.mix = mix
+        if mix is not None:
+            self._mix_gen = torch.Generator(device="cpu")
+            self._mix_gen.manual_seed(mix_seed)
 
     @staticmethod
     def _upload(images, device, num_shards, shard_index, chunk_bytes):
@@ -234,11 +358,13 @@ class DeviceImageDataset(DeviceArrayDataset):
             return t.pin_memory().to(self.device, non_blocking=True)
         return t
 
-    def _train_boxes(self, B):
+    def _train_boxes(self, B, plan=None):
         """-> (boxes int32 [B, 4], flip u8 [B]) of one training batch, on the dataset's device.
         The boxes are B-sized, so they are formed on the host, where the uniforms are drawn (a few
         dozen small device launches per step would cost more than the augmentation kernel
-        itself), and reach the device as one int32 [B, 5] copy: (y0, x0, h, w, flip)."""
+        itself), and reach the device as one int32 [B, 5] copy: (y0, x0, h, w, flip).
+        ``plan``: host int32 [B, k] columns that ride the same copy (the mixing plan); the
+        result then has a third element, those columns on the device."""
         a = self.augment
         Hs, Ws = self.images.shape[1:3]
         if a.mode == "random_resized_crop":
@@ -251,11 +377,34 @@ class DeviceImageDataset(DeviceArrayDataset):
             r = self._uniforms(B, 1)
             boxes = torch.tensor([[0, 0, Hs, Ws]], dtype=torch.int32, device="cpu").expand(B, 4)
         else:                                   # nothing random: no draw, no copy
-            return (self._whole_box.expand(B, 4).contiguous(),
-                    torch.zeros(B, dtype=torch.uint8, device=self.device))
+            fixed = (self._whole_box.expand(B, 4).contiguous(),
+                     torch.zeros(B, dtype=torch.uint8, device=self.device))
+            return fixed if plan is None else fixed + (self._to_device(plan),)
         flip = (r[:, -1] < 0.5) if a.flip else torch.zeros(B, dtype=torch.bool, device="cpu")
-        both = self._to_device(torch.cat([boxes, flip.to(torch.int32).unsqueeze(1)], dim=1))
-        return both[:, :4].contiguous(), both[:, 4].to(torch.uint8)
+        cols = [boxes, flip.to(torch.int32).unsqueeze(1)] + ([] if plan is None else [plan])
+        both = self._to_device(torch.cat(cols, dim=1))
+        out = both[:, :4].contiguous(), both[:, 4].to(torch.uint8)
+        return out if plan is None else out + (both[:, 5:],)
+
+    def _train_mixed(self, idx):
+        """One mixed training batch: the plan rides the boxes' copy as 7 more int32 columns
+        (partner, lam_q, the cut box, the bits of lam)."""
+        from .. import ops
+        B = idx.numel()
+        partner, lam_q, cut, lam = mix_plan(*self.mix.draw(B, self._mix_gen), B,
+                                            self.augment.out_hw, self.mix)
+        plan = torch.cat([partner.unsqueeze(1), lam_q.unsqueeze(1), cut,
+                          lam.view(torch.int32).unsqueeze(1)], dim=1)
+        boxes, flip, plan = self._train_boxes(B, plan)
+        partner = plan[:, 0].contiguous()
+        x = ops.augment_mix_images(self.images, idx.contiguous(), boxes, flip, self._lut,
+                                   self.augment.out_hw, partner, plan[:, 1].contiguous(),
+                                   plan[:, 2:6].contiguous(), self.augment.fill)
+        if self.flatten:
+            x = x.reshape(B, -1)
+        labels = self.labels.index_select(0, idx)
+        return x, MixedLabels(labels, labels.index_select(0, partner.long()),
+                              plan[:, 6].contiguous().view(torch.float32))
 
     def single_pass(self, batch_size=None):
         """This shard's examples in order, once, the remainder batch included, under the
@@ -269,6 +418,8 @@ class DeviceImageDataset(DeviceArrayDataset):
     def _gather(self, idx, train=True):
         from .. import ops
         B = idx.numel()
+        if train and self.mix is not None:
+            return self._train_mixed(idx)
         if train:
             boxes, flip = self._train_boxes(B)
         else:

@@ -200,6 +200,16 @@ def sparse_softmax_cross_entropy(logits, labels, label_smoothing=0.0):
     return reference.sparse_softmax_cross_entropy(logits, labels, label_smoothing)
 
 
+def mixed_softmax_cross_entropy(logits, labels_a, labels_b, lam, label_smoothing=0.0):
+    """The two-label loss of Mixup / CutMix in one read of the logits: mean cross-entropy against
+    ``lam onehot(a) + (1 - lam) onehot(b)`` (``lam`` fp32 [B] on the logits' device), smoothed
+    like :func:`sparse_softmax_cross_entropy`."""
+    if _use_native(logits):
+        return _native().mixed_softmax_cross_entropy(logits, labels_a, labels_b, lam,
+                                                     label_smoothing)
+    return reference.mixed_softmax_cross_entropy(logits, labels_a, labels_b, lam, label_smoothing)
+
+
 def softmax_cross_entropy_clipped_sum(logits, onehot):
     """The MLP template's loss (templates/00_mnist_replica.py:160-164), a batch SUM."""
     if _use_native(logits):
@@ -333,6 +343,21 @@ def augment_images(images, idx, boxes, flip, lut, out_hw, fill=0):
     return reference.augment_images(images, idx, boxes, flip, lut, out_hw, fill)
 
 
+def augment_mix_images(images, idx, boxes, flip, lut, out_hw, partner, lam_q, cut, fill=0,
+                       max_blocks=0):
+    """:func:`augment_images` with sample mixing in the same pass: row b is blended with row
+    ``partner[b]`` of the batch (that row's own index, box and flip) with weight
+    ``lam_q[b] / 65536`` (Mixup), and takes the partner's pixels inside ``cut[b]`` =
+    (oy0, ox0, h, w) in output pixels (CutMix).  Integer arithmetic in the 8-bit pixel domain,
+    so both backends give the same bits; the rule is spelled out in
+    :func:`reference.augment_mix_images`.  ``max_blocks``: grid cap of the kernel (0 = default)."""
+    if _use_native(images):
+        return _native().augment_mix_images(images, idx, boxes, flip, lut, out_hw, partner, lam_q,
+                                            cut, fill, max_blocks)
+    return reference.augment_mix_images(images, idx, boxes, flip, lut, out_hw, partner, lam_q, cut,
+                                        fill)
+
+
 def mlm_mask_tokens(tokens, idx, seed, max_predictions, masking, example_stride=1,
                     example_offset=0):
     """One batch of an HBM-resident token set -> BERT's masked-LM inputs: gather ``idx`` from
@@ -413,7 +438,8 @@ _OPS = ("conv2d", "conv2d_bias_relu", "batch_norm", "batch_norm_add_batch_norm",
         "bias_dropout_add_layer_norm", "embedding_layer_norm", "bias_gelu", "bias_gelu_dense",
         "dense_gelu_dense", "relu", "max_pool2d", "global_avg_pool", "sparse_softmax_cross_entropy",
         "softmax_cross_entropy_clipped_sum", "gelu", "attention", "dropout", "attention_qkv",
-        "mlm_loss", "eval_rows", "in_top_k", "augment_images", "mlm_mask_tokens")
+        "mlm_loss", "eval_rows", "in_top_k", "augment_images", "mlm_mask_tokens",
+        "augment_mix_images", "mixed_softmax_cross_entropy")
 _FENCED = _OPS
 for _name in _OPS:
     globals()[_name] = _dispatch(_name, globals()[_name], True)
@@ -426,5 +452,6 @@ __all__ = [
     "softmax_cross_entropy_clipped_sum", "layer_norm", "gelu", "attention", "dropout",
     "bias_dropout_add_layer_norm", "embedding_layer_norm", "bias_gelu", "bias_gelu_dense",
     "dense_gelu_dense", "attention_qkv", "mlm_loss", "eval_rows", "in_top_k", "augment_images",
-    "mlm_mask_tokens", "ema_update", "grad_accumulate",
+    "mlm_mask_tokens", "ema_update", "grad_accumulate", "augment_mix_images",
+    "mixed_softmax_cross_entropy",
 ]

@@ -1958,6 +1958,40 @@ def sparse_softmax_cross_entropy(logits, labels, label_smoothing=0.0):
     return _SoftmaxXent.apply(logits, labels, float(label_smoothing))
 
 
+class _SoftmaxXentPair(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels_a, labels_b, lam, label_smoothing=0.0):
+        lg = logits.detach().float().contiguous()
+        B, V = lg.shape
+        la, lb = labels_a.contiguous(), labels_b.contiguous()
+        if la.dtype not in (torch.int64, torch.int32) or lb.dtype != la.dtype:
+            la, lb = la.long(), lb.long()
+        rows = torch.empty(B, device=lg.device, dtype=torch.float32)
+        grad = torch.empty_like(lg)
+        _K.softmax_xent_pair(lg.data_ptr(), la.data_ptr(), lb.data_ptr(), la.element_size(),
+                             lam.contiguous().data_ptr(), B, V, rows.data_ptr(), grad.data_ptr(),
+                             1.0 / B, float(label_smoothing), _st())
+        ctx.save_for_backward(grad)
+        ctx.ldt = logits.dtype
+        return rows.mean()
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad * g).to(ctx.ldt), None, None, None, None
+
+
+def mixed_softmax_cross_entropy(logits, labels_a, labels_b, lam, label_smoothing=0.0):
+    """The two-label loss (csrc/kernels/loss.hip, the PAIR instantiation; semantics:
+    ops/reference.py mixed_softmax_cross_entropy).  ``lam`` is not range-checked here: that would
+    be a device sync; the dataset that makes it and the CPU path check it."""
+    from .reference import _mixed_xent_check
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError("label_smoothing must be in [0, 1]")
+    _mixed_xent_check(logits, labels_a, labels_b, lam)
+    return _SoftmaxXentPair.apply(logits, labels_a, labels_b, lam, float(label_smoothing))
+
+
 # ----------------------------------------------------------------------------- evaluation
 
 def eval_rows(logits, labels, vocab=None):
@@ -2029,6 +2063,28 @@ def augment_images(images, idx, boxes, flip, lut, out_hw, fill=0, max_blocks=0):
                       boxes.contiguous().data_ptr(), flip.contiguous().data_ptr(),
                       lut.contiguous().data_ptr(), out.data_ptr(), N, B, Hs, Ws, C, Ho, Wo,
                       int(fill), int(lut.dtype == _BF16), int(max_blocks), _st())
+    return out
+
+
+def augment_mix_images(images, idx, boxes, flip, lut, out_hw, partner, lam_q, cut, fill=0,
+                       max_blocks=0):
+    """``augment_images`` with Mixup / CutMix of row b and row ``partner[b]`` in the SAME launch
+    (csrc/kernels/augment.hip; the rule: ops/reference.py augment_mix_images, bit for bit).  A
+    partner outside the batch leaves its row unmixed and an index outside the set yields ``fill``
+    pixels, rather than a read out of range (no device sync to check either here)."""
+    from .reference import _augment_check
+    if not images.is_cuda:
+        raise ValueError("native augment_mix_images needs GPU tensors")
+    B, Ho, Wo = _augment_check(images, idx, boxes, flip, lut, out_hw, fill,
+                               (partner, lam_q, cut))
+    N, Hs, Ws, C = images.shape
+    out = torch.empty(B, Ho, Wo, C, device=images.device, dtype=lut.dtype)
+    _K.augment_mix_images(images.data_ptr(), idx.contiguous().data_ptr(),
+                          boxes.contiguous().data_ptr(), flip.contiguous().data_ptr(),
+                          lut.contiguous().data_ptr(), partner.contiguous().data_ptr(),
+                          lam_q.contiguous().data_ptr(), cut.contiguous().data_ptr(),
+                          out.data_ptr(), N, B, Hs, Ws, C, Ho, Wo, int(fill),
+                          int(lut.dtype == _BF16), int(max_blocks), _st())
     return out
 
 

@@ -124,6 +124,39 @@ def sparse_softmax_cross_entropy(logits, labels, label_smoothing=0.0):
     return F.cross_entropy(logits.float(), labels.long(), label_smoothing=float(label_smoothing))
 
 
+def mixed_softmax_cross_entropy(logits, labels_a, labels_b, lam, label_smoothing=0.0):
+    """The two-label loss of Mixup / CutMix: the mean over the batch of the cross-entropy against
+    ``lam onehot(a) + (1 - lam) onehot(b)``, smoothed as ``sparse_softmax_cross_entropy``.
+    ``lam``: fp32 [B] in [0, 1], the weight of ``labels_a``; ``1 - lam`` is formed in fp32."""
+    if not 0.0 <= label_smoothing <= 1.0:
+        raise ValueError("label_smoothing must be in [0, 1]")
+    _mixed_xent_check(logits, labels_a, labels_b, lam)
+    if lam.numel() and (float(lam.min()) < 0.0 or float(lam.max()) > 1.0):
+        raise ValueError("mixed_softmax_cross_entropy: lam outside [0, 1]")
+    e, x = float(label_smoothing), logits.float()
+    xa = x.gather(1, labels_a.long().unsqueeze(1)).squeeze(1)
+    xb = x.gather(1, labels_b.long().unsqueeze(1)).squeeze(1)
+    rows = torch.logsumexp(x, 1) - (1.0 - e) * (lam * xa + (1.0 - lam) * xb)
+    if e:
+        rows = rows - (e / x.shape[1]) * x.sum(1)
+    return rows.mean()
+
+
+def _mixed_xent_check(logits, labels_a, labels_b, lam):
+    """Shared argument validation of ``mixed_softmax_cross_entropy`` (both backends)."""
+    if logits.dim() != 2:
+        raise ValueError("logits must be [B, V]")
+    B = logits.shape[0]
+    if tuple(labels_a.shape) != (B,) or tuple(labels_b.shape) != (B,):
+        raise ValueError("mixed_softmax_cross_entropy: labels_a and labels_b must be [B]")
+    if lam.dtype != torch.float32 or tuple(lam.shape) != (B,):
+        raise ValueError("mixed_softmax_cross_entropy: lam must be fp32 [B]")
+    for t in (labels_a, labels_b, lam):
+        if t.device != logits.device:
+            raise ValueError("mixed_softmax_cross_entropy: every argument lives on the logits' "
+                             "device")
+
+
 def softmax_cross_entropy_clipped_sum(logits, onehot):
     """The MLP template's loss: -sum(y * log(clip(softmax(logits), 1e-10, 1)))
     (``templates/00_mnist_replica.py:162-164``)."""
@@ -323,8 +356,9 @@ def eval_rows(logits, labels, vocab=None, loss_dtype=torch.float32):
     return loss.to(loss_dtype), rank
 
 
-def _augment_check(images, idx, boxes, flip, lut, out_hw, fill):
-    """Shared argument validation of ``augment_images`` (both backends) -> (B, Ho, Wo)."""
+def _augment_check(images, idx, boxes, flip, lut, out_hw, fill, mix=None):
+    """Shared argument validation of ``augment_images`` and, with ``mix`` = (partner, lam_q,
+    cut), of ``augment_mix_images`` (both backends) -> (B, Ho, Wo)."""
     if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] not in (1, 3):
         raise ValueError("augment_images: images must be uint8 [N, Hs, Ws, C] with C in {1, 3}")
     if not images.is_contiguous() or images.shape[0] < 1:
@@ -347,6 +381,17 @@ def _augment_check(images, idx, boxes, flip, lut, out_hw, fill):
     for t in (idx, boxes, flip, lut):
         if t.device != images.device:
             raise ValueError("augment_images: every argument lives on the images' device")
+    if mix is not None:
+        partner, lam_q, cut = mix
+        if partner.dtype != torch.int32 or tuple(partner.shape) != (B,):
+            raise ValueError("augment_mix_images: partner must be int32 [B]")
+        if lam_q.dtype != torch.int32 or tuple(lam_q.shape) != (B,):
+            raise ValueError("augment_mix_images: lam_q must be int32 [B]")
+        if cut.dtype != torch.int32 or tuple(cut.shape) != (B, 4):
+            raise ValueError("augment_mix_images: cut must be int32 [B, 4] = (oy0, ox0, h, w)")
+        for t in mix:
+            if t.device != images.device:
+                raise ValueError("augment_mix_images: every argument lives on the images' device")
     return B, Ho, Wo
 
 
@@ -378,7 +423,15 @@ def augment_images(images, idx, boxes, flip, lut, out_hw, fill=0):
 
     i.e. TF's ``resize_bilinear(half_pixel_centers=True)`` without antialiasing, weights
     quantised to 1/256; a box of the output's size is an exact copy through the table."""
-    B, Ho, Wo = _augment_check(images, idx, boxes, flip, lut, out_hw, fill)
+    _augment_check(images, idx, boxes, flip, lut, out_hw, fill)
+    v = _augment_v(images, idx, boxes, flip, out_hw, fill)
+    return lut[torch.arange(images.shape[3], device=images.device).view(1, 1, 1, -1), v.long()]
+
+
+def _augment_v(images, idx, boxes, flip, out_hw, fill):
+    """The resampled 8-bit value ``v`` of the rule of ``augment_images`` -> int32
+    [B, Ho, Wo, C] (checked arguments)."""
+    B, (Ho, Wo) = idx.numel(), (int(v) for v in out_hw)
     N, Hs, Ws, C = images.shape
     dev = images.device
     if B and (int(idx.min()) < 0 or int(idx.max()) >= N):
@@ -402,8 +455,42 @@ def augment_images(images, idx, boxes, flip, lut, out_hw, fill=0):
     fx = fx.to(torch.int32).view(B, 1, Wo, 1)
     top = (256 - fx) * tap(iy0, ix0) + fx * tap(iy0, ix1)
     bot = (256 - fx) * tap(iy1, ix0) + fx * tap(iy1, ix1)
-    v = ((256 - fy) * top + fy * bot + 32768) >> 16
-    return lut[torch.arange(C, device=dev).view(1, 1, 1, C), v.long()]
+    return ((256 - fy) * top + fy * bot + 32768) >> 16
+
+
+def augment_mix_images(images, idx, boxes, flip, lut, out_hw, partner, lam_q, cut, fill=0):
+    """``augment_images`` with row b mixed with row ``p = partner[b]`` of the same batch (Mixup /
+    CutMix), in the 8-bit pixel domain: the oracle of the ``augment_mix_images`` kernel and the
+    CPU path; both produce the same bits.
+
+    ``partner`` int32 [B]; ``lam_q`` int32 [B], the weight of row b in 1/65536; ``cut`` int32
+    [B, 4] = (oy0, ox0, h, w) in output pixels, clipped to the output, h <= 0 or w <= 0: no box.
+    With vA the ``v`` of ``augment_images`` for row b and vB the one for row p (p's own index,
+    box and flip) at the same output pixel, and q = clamp(lam_q[b], 0, 65536):
+
+        v = vB if oy0 <= oy < oy0 + h and ox0 <= ox < ox0 + w
+            else (q vA + (65536 - q) vB + 32768) >> 16
+        out = lut[c][v]
+
+    The table is affine and the weights sum to 1, so this is the mix of the normalised images at
+    the precision of the source.  q = 65536 without a box is ``augment_images`` to the bit, q = 0
+    the partner's row; a row that is its own partner is unmixed.  A partner outside [0, B)
+    raises here (the kernel, which cannot, leaves the row unmixed)."""
+    B, Ho, Wo = _augment_check(images, idx, boxes, flip, lut, out_hw, fill,
+                               (partner, lam_q, cut))
+    dev = images.device
+    if B and (int(partner.min()) < 0 or int(partner.max()) >= B):
+        raise ValueError("augment_mix_images: partner outside the batch")
+    va = _augment_v(images, idx, boxes, flip, out_hw, fill)
+    vb = va[partner.long()]                   # row p at the same output pixel
+    q = lam_q.clamp(0, 65536).view(B, 1, 1, 1)
+    c = cut.long()
+    oy = torch.arange(Ho, device=dev).view(1, Ho, 1)
+    ox = torch.arange(Wo, device=dev).view(1, 1, Wo)
+    y0, x0, h, w = (c[:, i].view(B, 1, 1) for i in range(4))
+    inside = (oy >= y0) & (oy < y0 + h) & (ox >= x0) & (ox < x0 + w) & (h > 0) & (w > 0)
+    v = torch.where(inside.unsqueeze(3), vb, (q * va + (65536 - q) * vb + 32768) >> 16)
+    return lut[torch.arange(images.shape[3], device=dev).view(1, 1, 1, -1), v.long()]
 
 
 MLM_MAX_SEQ = 512
