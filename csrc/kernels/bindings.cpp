@@ -166,19 +166,28 @@ PYBIND11_MODULE(_dtf_hip, m) {
   });
   // rule = [vocab_size, pad_id, cls_id, sep_id, mask_id, random_low, prob_q16];
   // outs = [input_ids, segment_ids, input_mask, masked_lm_positions, masked_lm_ids,
-  //         masked_lm_weights]
+  //         masked_lm_weights]; continuation: uint8 [vocab_size], or 0 for the token rule
   m.def("mlm_mask_tokens", [](uintptr_t tokens, int token_bytes, uintptr_t idx,
                               const std::vector<uintptr_t>& outs, long N, int B, int S_, int P_,
                               uint32_t seed, long ex_stride, long ex_offset,
-                              const std::vector<uint32_t>& rule, int max_blocks, uintptr_t st) {
+                              const std::vector<uint32_t>& rule, int max_blocks, uintptr_t st,
+                              uintptr_t continuation) {
     if (outs.size() != 6 || rule.size() != 7)
       throw std::runtime_error("mlm_mask_tokens: needs 6 outputs and 7 rule entries");
     const MlmMaskRule r{rule[0], rule[1], rule[2], rule[3], rule[4], rule[5], rule[6]};
-    dtf_mlm_mask_tokens(P<void>(tokens), token_bytes, P<int64_t>(idx), P<int64_t>(outs[0]),
-                        P<int64_t>(outs[1]), P<int64_t>(outs[2]), P<int64_t>(outs[3]),
-                        P<int64_t>(outs[4]), P<float>(outs[5]), N, B, S_, P_, seed, ex_stride,
-                        ex_offset, r, max_blocks, S(st));
-    check_launch("mlm_mask_tokens");
+    if (continuation == 0) {
+      dtf_mlm_mask_tokens(P<void>(tokens), token_bytes, P<int64_t>(idx), P<int64_t>(outs[0]),
+                          P<int64_t>(outs[1]), P<int64_t>(outs[2]), P<int64_t>(outs[3]),
+                          P<int64_t>(outs[4]), P<float>(outs[5]), N, B, S_, P_, seed, ex_stride,
+                          ex_offset, r, max_blocks, S(st));
+      check_launch("mlm_mask_tokens");
+    } else {
+      dtf_mlm_mask_words(P<void>(tokens), token_bytes, P<int64_t>(idx), P<uint8_t>(continuation),
+                         P<int64_t>(outs[0]), P<int64_t>(outs[1]), P<int64_t>(outs[2]),
+                         P<int64_t>(outs[3]), P<int64_t>(outs[4]), P<float>(outs[5]), N, B, S_, P_,
+                         seed, ex_stride, ex_offset, r, max_blocks, S(st));
+      check_launch("mlm_mask_words");
+    }
   });
   m.def("gemm_f32_splits", &dtf_gemm_f32_splits);
   m.def("gemm_f32", [](uintptr_t a, uintptr_t b, uintptr_t c, uintptr_t bias, int M, int N, int K,

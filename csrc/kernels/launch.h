@@ -312,6 +312,13 @@ void dtf_mlm_mask_tokens(const void* tokens, int token_bytes, const int64_t* idx
                          int64_t* positions, int64_t* ids, float* weights, long N, int B, int S,
                          int P, uint32_t seed, long ex_stride, long ex_offset,
                          const MlmMaskRule& rule, int max_blocks, hipStream_t st);
+// the same with whole-word masking: continuation[v] = 1 marks id v of the vocabulary as a
+// continuation piece, and a word's pieces are selected together
+void dtf_mlm_mask_words(const void* tokens, int token_bytes, const int64_t* idx,
+                        const uint8_t* continuation, int64_t* input_ids, int64_t* segment_ids,
+                        int64_t* input_mask, int64_t* positions, int64_t* ids, float* weights,
+                        long N, int B, int S, int P, uint32_t seed, long ex_stride, long ex_offset,
+                        const MlmMaskRule& rule, int max_blocks, hipStream_t st);
 
 // ---- loss.hip
 void dtf_softmax_xent(const float* logits, const void* labels, int label_bytes, int B, int V,

@@ -127,6 +127,10 @@ def build_parser():
                    help="share of a row's tokens chosen for prediction with --text_data")
     p.add_argument("--max_predictions", type=int, default=20,
                    help="masked positions per example with --text_data")
+    p.add_argument("--whole_word_mask", action="store_true",
+                   help="with --text_data: whole-word masking (the pieces of a word are predicted "
+                        "together), for training and evaluation; reads DIR/continuation.npy, "
+                        "uint8 [vocab_size] with 1 at the ## pieces")
     return p
 
 
@@ -141,6 +145,12 @@ def check_data_args(args):
             raise SystemExit(f"--mlm_prob {args.mlm_prob} outside [0, 1]")
         if args.max_predictions < 1:
             raise SystemExit(f"--max_predictions {args.max_predictions} must be at least 1")
+    if args.whole_word_mask:
+        if not args.text_data:
+            raise SystemExit("--whole_word_mask needs --text_data")
+        table = os.path.join(args.text_data, "continuation.npy")
+        if not os.path.exists(table):
+            raise SystemExit(f"--whole_word_mask needs {table}")
     if args.mixup_alpha or args.cutmix_alpha:
         if args.mixup_alpha < 0 or args.cutmix_alpha < 0:
             raise SystemExit("--mixup_alpha and --cutmix_alpha must be >= 0")
@@ -443,6 +453,8 @@ def run(args):
     for k in ("mixup_alpha", "cutmix_alpha"):
         if getattr(args, k):
             result[k] = getattr(args, k)
+    if args.whole_word_mask:
+        result["whole_word_mask"] = True
     steps_done = global_step.value() - (first_step or 0)
     if steps_done > 0 and server is None:
         result["examples_per_sec"] = round(steps_done * batch * nrep * accum / elapsed, 1)
@@ -503,10 +515,16 @@ def _image_dataset(args, split, num_classes, batch, device, dtype, shards, shard
 
 def _token_dataset(args, split, batch, device, shards, shard_index):
     """--text_data: the HBM-resident ``split`` of DIR as a DeviceTokenDataset under --mlm_prob /
-    --max_predictions (and DIR/meta.json, where present); the batch shrinks to the shard where
-    that is smaller."""
-    from .data import DeviceTokenDataset, TokenMasking, load_token_arrays
+    --max_predictions (and DIR/meta.json, where present), with DIR/continuation.npy under
+    --whole_word_mask; the batch shrinks to the shard where that is smaller."""
+    from .data import DeviceTokenDataset, TokenMasking, load_continuation, load_token_arrays
     tokens, masking = load_token_arrays(args.text_data, split, TokenMasking(prob=args.mlm_prob))
+    continuation = None
+    if args.whole_word_mask:
+        try:
+            continuation = load_continuation(args.text_data, masking)
+        except (FileNotFoundError, ValueError) as e:
+            raise SystemExit(f"--whole_word_mask: {e}")
     S = tokens.shape[1]
     if S > 512 or args.max_predictions > S:
         raise SystemExit(f"{args.text_data}: rows of {S} tokens; the sequence length is at most "
@@ -521,7 +539,7 @@ def _token_dataset(args, split, batch, device, shards, shard_index):
                               shuffle=split == "train", seed=args.seed + stream,
                               mask_seed=args.seed + 1000003 * (stream + 1),
                               eval_seed=args.seed & 0xFFFFFFFF, num_shards=shards,
-                              shard_index=shard_index)
+                              shard_index=shard_index, continuation=continuation)
 
 
 def _make_eval_fn(args, model, opt, strategy, device, dtype, batch, shards, shard_index,

@@ -6,9 +6,10 @@ from .dataset import Dataset, Iterator, NativeBatchDataset
 from .device import DeviceArrayDataset
 from .images import DeviceImageDataset, ImageAugment, ImageMix, MixedLabels, mix_plan
 from .synthetic import SyntheticImageNet, SyntheticMLM
-from .tokens import DeviceTokenDataset, TokenMasking, load_token_arrays
+from .tokens import (DeviceTokenDataset, TokenMasking, load_continuation, load_token_arrays,
+                     wordpiece_continuation)
 
 __all__ = ["images", "mnist", "tokens", "Dataset", "DeviceArrayDataset", "DeviceImageDataset",
            "DeviceTokenDataset", "ImageAugment", "ImageMix", "Iterator", "MixedLabels",
            "NativeBatchDataset", "SyntheticImageNet", "SyntheticMLM", "TokenMasking",
-           "load_token_arrays", "mix_plan"]
+           "load_continuation", "load_token_arrays", "mix_plan", "wordpiece_continuation"]

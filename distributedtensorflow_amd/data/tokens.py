@@ -11,6 +11,9 @@ On disk a set is one array per split in one directory (:func:`load_token_arrays`
 
     {split}_tokens.npy   uint16 or int32 [N, S], S <= 512   (memory-mapped, never copied whole)
     meta.json            optional: vocab_size, pad_id, cls_id, sep_id, mask_id
+    continuation.npy     optional: uint8 or bool [vocab_size], 1 at the continuation pieces of the
+                         vocabulary (``##...``); whole-word masking reads it
+                         (:func:`wordpiece_continuation` makes it from a vocab.txt)
 
 A row is one packed example, ``[CLS] a ... [SEP] b ... [SEP] pad ...``; segment ids and the input
 mask are derived from it, so nothing else is stored.
@@ -94,6 +97,45 @@ def load_token_arrays(data_dir, split, masking=None):
     return tokens, masking
 
 
+def wordpiece_continuation(vocab):
+    """The whole-word table of a WordPiece vocabulary -> np.uint8 [len(vocab)], 1 where the piece
+    starts with ``##``.  ``vocab``: the path of a vocab.txt (one piece per line, line k is id k)
+    or a sequence of pieces."""
+    if isinstance(vocab, (str, os.PathLike)):
+        with open(vocab, encoding="utf-8") as f:
+            vocab = [line.rstrip("\r\n") for line in f]
+    return np.fromiter((p.startswith("##") for p in vocab), dtype=np.uint8, count=len(vocab))
+
+
+def check_continuation(table, masking, where="continuation"):
+    """-> ``table`` as contiguous np.uint8 [vocab_size]; ValueError unless it is uint8 or bool of
+    that shape, holds 0 / 1 only and leaves pad_id, cls_id, sep_id and mask_id unflagged."""
+    table = np.asarray(table)
+    if table.dtype not in (np.uint8, np.bool_):
+        raise ValueError(f"{where}: dtype {table.dtype}, expected uint8 or bool")
+    if table.shape != (masking.vocab_size,):
+        raise ValueError(f"{where}: shape {table.shape}, expected [{masking.vocab_size}] "
+                         "(vocab_size)")
+    table = np.ascontiguousarray(table.view(np.uint8))
+    if table.max() > 1:
+        raise ValueError(f"{where}: a value above 1")
+    for name in ("pad_id", "cls_id", "sep_id", "mask_id"):
+        if table[getattr(masking, name)]:
+            raise ValueError(f"{where}: {name} {getattr(masking, name)} is flagged as a "
+                             "continuation piece")
+    return table
+
+
+def load_continuation(data_dir, masking):
+    """-> ``DIR/continuation.npy`` as np.uint8 [vocab_size], checked against ``masking`` (the one
+    :func:`load_token_arrays` returned).  FileNotFoundError names a missing file."""
+    path = os.path.join(data_dir, "continuation.npy")
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"{path}: no such file (whole-word masking needs the table of "
+                                "continuation pieces)")
+    return check_continuation(np.load(path), masking, path)
+
+
 class DeviceTokenDataset(DeviceArrayDataset):
     """A :class:`DeviceArrayDataset` of token rows whose batches are masked-LM examples made on
     the device by one kernel; a batch is the dict :class:`SyntheticMLM` yields plus
@@ -108,11 +150,15 @@ class DeviceTokenDataset(DeviceArrayDataset):
 
     ``tokens``: uint16 or int32 [N, S] (numpy, possibly memory-mapped); 16-bit sets are held as
     their int16 reinterpretation and read unsigned.  Upload: chunked and shard-strided
-    (:func:`upload_sharded`)."""
+    (:func:`upload_sharded`).
+
+    ``continuation`` (uint8 or bool [vocab_size], 1 at the ``##`` pieces) turns on whole-word
+    masking, for training batches and ``single_pass()`` alike: the table is checked here,
+    uploaded once and handed to every call of the kernel."""
 
     def __init__(self, tokens, batch_size, device, masking=None, max_predictions=20,
                  shuffle=False, seed=0, mask_seed=0, eval_seed=0, num_shards=1, shard_index=0,
-                 drop_remainder=True, chunk_bytes=256 << 20):
+                 drop_remainder=True, chunk_bytes=256 << 20, continuation=None):
         device = torch.device(device)
         masking = masking or TokenMasking()
         if tokens.dtype not in (np.uint16, np.int32) or tokens.ndim != 2:
@@ -121,6 +167,9 @@ class DeviceTokenDataset(DeviceArrayDataset):
             raise ValueError(f"DeviceTokenDataset: shard {shard_index} of {num_shards}")
         if not 0 <= int(eval_seed) < (1 << 32):
             raise ValueError("DeviceTokenDataset: eval_seed must be in [0, 2^32)")
+        if continuation is not None:
+            continuation = check_continuation(continuation, masking, "DeviceTokenDataset: "
+                                              "continuation")
         self.tokens = upload_sharded(tokens, device, num_shards, shard_index, int(chunk_bytes),
                                      view=np.int16 if tokens.dtype == np.uint16 else None)
         self.n = len(self.tokens)
@@ -141,9 +190,13 @@ class DeviceTokenDataset(DeviceArrayDataset):
         self._mask_gen = torch.Generator(device="cpu")
         self._mask_gen.manual_seed(mask_seed)
         self.eval_seed = int(eval_seed)
-        from ..ops.reference import _mlm_check            # validates S, P and the ids now
-        _mlm_check(self.tokens, torch.zeros(0, dtype=torch.int64, device=device), 0,
-                   self.max_predictions, masking)
+        from ..ops.reference import _mlm_check, _mlm_continuation_check
+        rule = _mlm_check(self.tokens, torch.zeros(0, dtype=torch.int64, device=device), 0,
+                          self.max_predictions, masking)[3]  # validates S, P and the ids now
+        self.continuation = None
+        if continuation is not None:
+            self.continuation = torch.from_numpy(continuation).to(device)
+            _mlm_continuation_check(self.continuation, self.tokens, rule)
 
     @property
     def seq_len(self):
@@ -164,4 +217,5 @@ class DeviceTokenDataset(DeviceArrayDataset):
                                      dtype=torch.int64, device="cpu"))
         return ops.mlm_mask_tokens(self.tokens, idx.contiguous(), seed, self.max_predictions,
                                    self.masking, example_stride=self.num_shards,
-                                   example_offset=self.shard_index)
+                                   example_offset=self.shard_index,
+                                   continuation=self.continuation)

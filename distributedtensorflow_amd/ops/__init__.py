@@ -359,19 +359,22 @@ def augment_mix_images(images, idx, boxes, flip, lut, out_hw, partner, lam_q, cu
 
 
 def mlm_mask_tokens(tokens, idx, seed, max_predictions, masking, example_stride=1,
-                    example_offset=0):
+                    example_offset=0, continuation=None):
     """One batch of an HBM-resident token set -> BERT's masked-LM inputs: gather ``idx`` from
     ``tokens`` [N, S] (16-bit or int32 storage, read unsigned), derive ``input_mask`` and
     ``segment_ids``, choose up to ``max_predictions`` positions and apply the 80 / 10 / 10
     replacement under ``masking`` (a :class:`data.TokenMasking`).  Everything random is a
     counter-based hash of (``seed``, example number, position), the example number being
     ``example_offset + idx * example_stride``; integer arithmetic, so both backends give the same
-    bits.  The rule is spelled out in :func:`reference.mlm_mask_tokens`."""
+    bits.  ``continuation`` (uint8 / bool [vocab_size], 1 at the ``##`` pieces of a WordPiece
+    vocabulary) switches to whole-word masking: the pieces of a word are chosen together.  The
+    rule is spelled out in :func:`reference.mlm_mask_tokens`."""
     if _use_native(tokens):
         return _native().mlm_mask_tokens(tokens, idx, seed, max_predictions, masking,
-                                         example_stride, example_offset)
+                                         example_stride, example_offset,
+                                         continuation=continuation)
     return reference.mlm_mask_tokens(tokens, idx, seed, max_predictions, masking, example_stride,
-                                     example_offset)
+                                     example_offset, continuation=continuation)
 
 
 def ema_update(avg, var, a_dev):

@@ -2089,15 +2089,20 @@ def augment_mix_images(images, idx, boxes, flip, lut, out_hw, partner, lam_q, cu
 
 
 def mlm_mask_tokens(tokens, idx, seed, max_predictions, masking, example_stride=1,
-                    example_offset=0, max_blocks=0):
+                    example_offset=0, max_blocks=0, continuation=None):
     """Masked-LM example creation of one batch in ONE launch (csrc/kernels/mlm_mask.hip; the
     rule: ops/reference.py mlm_mask_tokens, bit for bit).  An index outside the set yields an
     all-pad row rather than a read past the array (no device sync to check it here).
-    ``max_blocks``: grid cap of this call (0 = the launcher's default)."""
-    from .reference import _mlm_check
+    ``max_blocks``: grid cap of this call (0 = the launcher's default).  ``continuation``
+    (uint8 / bool [vocab_size] on the device) selects the whole-word instantiation."""
+    from .reference import _mlm_check, _mlm_continuation_check
     if not tokens.is_cuda:
         raise ValueError("native mlm_mask_tokens needs GPU tensors")
     B, S, P, rule = _mlm_check(tokens, idx, seed, max_predictions, masking)
+    table = 0
+    if continuation is not None:
+        _mlm_continuation_check(continuation, tokens, rule)
+        table = continuation.data_ptr()
     dev = tokens.device
     seq = [torch.empty(B, S, device=dev, dtype=torch.int64) for _ in range(3)]
     pred = [torch.empty(B, P, device=dev, dtype=torch.int64) for _ in range(2)]
@@ -2105,7 +2110,8 @@ def mlm_mask_tokens(tokens, idx, seed, max_predictions, masking, example_stride=
     outs = seq + pred + [weights]
     _K.mlm_mask_tokens(tokens.data_ptr(), tokens.element_size(), idx.contiguous().data_ptr(),
                        [t.data_ptr() for t in outs], tokens.shape[0], B, S, P, int(seed),
-                       int(example_stride), int(example_offset), rule, int(max_blocks), _st())
+                       int(example_stride), int(example_offset), rule, int(max_blocks), _st(),
+                       table)
     return dict(zip(("input_ids", "segment_ids", "input_mask", "masked_lm_positions",
                      "masked_lm_ids", "masked_lm_weights"), outs))
 

@@ -528,8 +528,67 @@ def _mlm_check(tokens, idx, seed, max_predictions, masking):
     return idx.numel(), S, P, rule
 
 
+def _mlm_continuation_check(continuation, tokens, rule):
+    """Shared validation of the whole-word table (both backends): uint8 or bool ``[vocab_size]``,
+    contiguous, on the tokens' device, values 0 / 1, the four special ids not flagged.  The two
+    value checks read the table, which on a GPU waits for the device; they run once per table
+    (and again after an in-place write to it) and are remembered on the tensor, so a training
+    step does not wait."""
+    V, pad, cls, sep, mask_id = rule[:5]
+    if not isinstance(continuation, torch.Tensor) or \
+            continuation.dtype not in (torch.uint8, torch.bool):
+        raise ValueError("mlm_mask_tokens: continuation must be a uint8 or bool tensor")
+    if continuation.dim() != 1 or continuation.shape[0] != V:
+        raise ValueError(f"mlm_mask_tokens: continuation of shape {tuple(continuation.shape)}, "
+                         f"expected [{V}] (vocab_size)")
+    if not continuation.is_contiguous() or continuation.device != tokens.device:
+        raise ValueError("mlm_mask_tokens: continuation must be contiguous and on the tokens' "
+                         "device")
+    seen = (continuation._version, continuation.data_ptr(), pad, cls, sep, mask_id)
+    if getattr(continuation, "_mlm_checked", None) == seen:
+        return
+    table = continuation.view(torch.uint8)
+    if int(table.max()) > 1:
+        raise ValueError("mlm_mask_tokens: continuation holds a value above 1")
+    special = torch.tensor([pad, cls, sep, mask_id], device=table.device)
+    if int(table[special].max()) != 0:
+        raise ValueError("mlm_mask_tokens: continuation flags one of pad_id, cls_id, sep_id, "
+                         "mask_id")
+    continuation._mlm_checked = seen
+
+
+def _mlm_select_words(t, cand, key, T, continuation, V):
+    """The whole-word choice of ``mlm_mask_tokens`` -> (selected positions [B, S], T' [B])."""
+    B, S = t.shape
+    dev = t.device
+    j = torch.arange(S, device=dev).unsqueeze(0)
+    table = continuation.view(torch.uint8)
+    piece = cand & (t < V) & (table[t.clamp(max=V - 1)] != 0)
+    after = torch.cat([torch.zeros(B, 1, dtype=torch.bool, device=dev), cand[:, :-1]], 1)
+    start = cand & ~(piece & after)
+    nw = start.sum(1)
+    # words are numbered in position order; column S collects what belongs to none
+    word = torch.where(cand, start.cumsum(1) - 1, torch.full_like(t, S))
+    length = torch.zeros(B, S + 1, dtype=torch.int64, device=dev)
+    length.scatter_add_(1, word, torch.ones_like(t))
+    pair = torch.full((B, S + 1), 1 << 62, dtype=torch.int64, device=dev)
+    pair.scatter_(1, torch.where(start, word, torch.full_like(t, S)), key * 1024 + j)
+    order = pair[:, :S].argsort(1)                        # the words in visiting order
+    length = length[:, :S].gather(1, order)
+    taken = torch.zeros_like(nw)
+    fits = torch.zeros(B, S, dtype=torch.bool, device=dev)
+    for k in range(int(nw.max()) if B else 0):            # the greedy fill, rank by rank
+        ok = (k < nw) & (taken < T) & (taken + length[:, k] <= T)
+        taken = taken + torch.where(ok, length[:, k], torch.zeros_like(taken))
+        fits[:, k] = ok
+    chosen = torch.zeros(B, S + 1, dtype=torch.bool, device=dev)
+    chosen.scatter_(1, order, fits)
+    chosen[:, S] = False
+    return chosen.gather(1, word), taken
+
+
 def mlm_mask_tokens(tokens, idx, seed, max_predictions, masking, example_stride=1,
-                    example_offset=0):
+                    example_offset=0, continuation=None):
     """Masked-LM example creation for a gathered batch of token rows, in integer arithmetic: the
     oracle of the ``mlm_mask_tokens`` kernel (csrc/kernels/mlm_mask.hip) and the CPU path; both
     produce the same bits.
@@ -554,8 +613,30 @@ def mlm_mask_tokens(tokens, idx, seed, max_predictions, masking, example_stride=
             d == 9: random_low + ((fmix32(h2 + 0x9E3779B1) * (vocab_size - random_low)) >> 32)
         every other position copies t[j]
 
-    An ``idx[b]`` outside [0, N) yields an all-pad row with weights 0."""
+    An ``idx[b]`` outside [0, N) yields an all-pad row with weights 0.
+
+    Whole-word masking: ``continuation`` is a uint8 / bool table [vocab_size] with 1 at the
+    continuation pieces of the vocabulary (WordPiece's ``##...``; pad_id, cls_id, sep_id and
+    mask_id must be 0; an id past the table is no continuation).  Everything above holds but
+    the choice of the selected positions, which becomes create_pretraining_data.py's
+    ``--do_whole_word_mask``:
+
+        candidate j starts a word iff continuation[t[j]] == 0, or j == 0, or j - 1 is no
+            candidate; otherwise it belongs to the word of the nearest start below it
+        words are visited in ascending (key[start], start); taken = 0; for each word:
+            stop if taken >= T;  skip the word if taken + len(word) > T;
+            else select every token of the word and add len(word) to taken
+        T' = taken (<= T; 0 when every word is longer than T); T == nc selects everything
+        the selected positions are listed in ascending j in the slots s < T'; slots s >= T' hold
+            0, 0, 0.0; each selected token draws its own 80 / 10 / 10 from its own key[j]
+
+    An all-zero table is the token rule to the bit.  Two differences from the script: the budget
+    is formed from ``nc`` as above (not from the row's length), and a continuation piece that does
+    not directly follow a candidate starts a word of its own (the script would glue it to the
+    last word across a ``[SEP]``; well-formed WordPiece rows hold no such piece)."""
     B, S, P, rule = _mlm_check(tokens, idx, seed, max_predictions, masking)
+    if continuation is not None:
+        _mlm_continuation_check(continuation, tokens, rule)
     V, pad, cls, sep, mask_id, low, q = rule
     N, dev = tokens.shape[0], tokens.device
     store = tokens.view(torch.int16) if tokens.dtype == torch.uint16 else tokens
@@ -575,11 +656,14 @@ def mlm_mask_tokens(tokens, idx, seed, max_predictions, masking, example_stride=
     cand = real & (t != cls) & (t != sep)
     nc = cand.sum(1)
     T = torch.minimum(torch.clamp((nc * q + 32768) >> 16, min=1), nc).clamp(max=P)
-    # (key, j) pairs as one integer; no candidate ranks below nc, so none is ever selected
-    pair = torch.where(cand, key * 1024 + j, torch.full_like(key, 1 << 62))
-    rank = torch.empty_like(pair)
-    rank.scatter_(1, pair.argsort(1), j.expand(B, S).contiguous())
-    sel = cand & (rank < T.unsqueeze(1))
+    if continuation is None:
+        # (key, j) pairs as one integer; no candidate ranks below nc, so none is ever selected
+        pair = torch.where(cand, key * 1024 + j, torch.full_like(key, 1 << 62))
+        rank = torch.empty_like(pair)
+        rank.scatter_(1, pair.argsort(1), j.expand(B, S).contiguous())
+        sel = cand & (rank < T.unsqueeze(1))
+    else:
+        sel, T = _mlm_select_words(t, cand, key, T, continuation, V)
 
     h2 = _fmix32((key + 0x85EBCA6B) & _M32)
     d = ((h2 & 0xFFFF) * 10) >> 16

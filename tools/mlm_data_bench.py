@@ -9,15 +9,21 @@ Kernel arms (uint16 tokens, a 1 GiB set so that rows come from HBM, random examp
 in ONE process, alternating call by call, timed with device events after a warm-up of every shape:
   (a) ops.mlm_mask_tokens: gather + masks + selection + replacement, six outputs, one launch;
   (b) reference.mlm_mask_tokens on the same device tensors: the same rule, bit for bit, as a
-      composition of torch ops (hashes in int64, a sort for the selection, scatters for the slots).
+      composition of torch ops (hashes in int64, a sort for the selection, scatters for the slots);
+  (c) ops.mlm_mask_tokens with a continuation table: the whole-word instantiation of the kernel
+      on the same rows and indices.  The table flags the top 19 % of the ids (BERT's vocabulary
+      holds 19 % of ## pieces), so a word is a random id below them and the flagged ids after it:
+      1.23 tokens on average.  Checked against reference.mlm_mask_tokens before it is timed.
 Shapes: B = 512, S = 128, P = 20 and B = 128, S = 512, P = 76.  The two arms' outputs are compared
 before anything is timed.  Prints one JSON line per shape: median / min / p10 / p90 of each arm
-in microseconds and arm (a)'s effective GB/s over the token bytes read plus the bytes written.
+in microseconds, arm (a)'s effective GB/s over the token bytes read plus the bytes written, and
+arm (c)'s median over arm (a)'s.
 
 --bert_base: BERT-base training steps at --batch, S = 128, P = 20, fed alternately by
-SyntheticMLM and by a DeviceTokenDataset, --rounds runs of --steps steps each in the order
-S T S T ..., one model, one process.  Prints every run's ms / step, each feed's median, and the
-spread (max - min) among the synthetic runs themselves.
+SyntheticMLM, by a DeviceTokenDataset and by a DeviceTokenDataset with a continuation table
+(whole-word masking), --rounds runs of --steps steps each in the order S T W S T W ..., one model,
+one process.  Prints every run's ms / step, each feed's median, and the spread (max - min) among
+the synthetic runs themselves.
 
 Rows are [CLS] a [SEP] b [SEP] pad...; --short_prob of them have a random length 20..S and the
 rest are full (create_pretraining_data.py's short_seq_prob, 0.1 there and here; 1.0 makes 42% of
@@ -44,13 +50,15 @@ def _stats(us):
 
 
 def _time_alternating(arms, calls, warmup):
+    """``arms``: (name, fn) pairs, called in this order ``calls`` times over; a name that comes
+    twice is one arm whose samples are pooled."""
     for _ in range(warmup):
-        for fn in arms.values():
+        for _, fn in arms:
             fn()
     torch.cuda.synchronize()
-    ev = {k: [] for k in arms}
+    ev = {k: [] for k, _ in arms}
     for _ in range(calls):
-        for k, fn in arms.items():
+        for k, fn in arms:
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
             fn()
@@ -79,11 +87,19 @@ def token_rows(N, S, masking, device, seed=1, shortest=20, short_prob=0.1):
     return torch.where(j >= L, torch.full_like(t, masking.pad_id), t).contiguous()
 
 
+def continuation_table(masking, device, share=0.19):
+    """uint8 [vocab_size] with the top ``share`` of the ids flagged as continuation pieces."""
+    table = torch.zeros(masking.vocab_size, dtype=torch.uint8, device=device)
+    table[int(masking.vocab_size * (1 - share)):] = 1
+    return table
+
+
 def bench_kernels(calls, warmup, set_bytes, short_prob):
     from distributedtensorflow_amd import ops
     from distributedtensorflow_amd.data import TokenMasking
     from distributedtensorflow_amd.ops import reference
     m = TokenMasking()
+    table = continuation_table(m, "cuda")
     for name, B, S, P in (("b512_s128_p20", 512, 128, 20), ("b128_s512_p76", 128, 512, 76)):
         N = set_bytes // (2 * S)
         tokens = token_rows(N, S, m, "cuda", short_prob=short_prob)
@@ -94,6 +110,12 @@ def bench_kernels(calls, warmup, set_bytes, short_prob):
         same = all(torch.equal(new_out[k], old_out[k]) for k in KEYS)
         if not same:
             raise SystemExit(f"mlm_data_bench: {name}: the kernel and the torch ops disagree")
+        word_out = ops.mlm_mask_tokens(tokens, idx, 12345, P, m, continuation=table)
+        word_ref = reference.mlm_mask_tokens(tokens, idx, 12345, P, m, continuation=table)
+        if not all(torch.equal(word_out[k], word_ref[k]) for k in KEYS):
+            raise SystemExit(f"mlm_data_bench: {name}: the whole-word kernel and the torch ops "
+                             "disagree")
+        filled = float(word_out["masked_lm_weights"].sum() / new_out["masked_lm_weights"].sum())
         sink = {}
         seeds = iter(range(1, 1 << 30))
 
@@ -103,7 +125,14 @@ def bench_kernels(calls, warmup, set_bytes, short_prob):
         def old():
             sink["y"] = reference.mlm_mask_tokens(tokens, idx, next(seeds), P, m)
 
-        res = _time_alternating({"mlm_mask_tokens": new, "torch_composition": old}, calls, warmup)
+        def words():
+            sink["z"] = ops.mlm_mask_tokens(tokens, idx, next(seeds), P, m, continuation=table)
+
+        # each kernel is timed right after a torch arm, as the token kernel always was: right
+        # after the other kernel it measured 17 us lower at both shapes (profiles/MLM_DATA.md)
+        res = _time_alternating([("mlm_mask_tokens", new), ("torch_composition", old),
+                                 ("mlm_mask_words", words), ("torch_composition", old)],
+                                calls, warmup)
         read, written = B * S * 2 + B * 8, 3 * B * S * 8 + B * P * 20
         a, t = res["mlm_mask_tokens"], res["torch_composition"]
         print(json.dumps({"shape": name, "B": B, "S": S, "P": P, "rows_in_set": N,
@@ -112,9 +141,12 @@ def bench_kernels(calls, warmup, set_bytes, short_prob):
                           "bytes_read": read, "bytes_written": written,
                           "new_GBps_at_median": round((read + written) / a["median_us"] / 1e3, 1),
                           "torch_over_new_at_median": round(t["median_us"] / a["median_us"], 1),
+                          "words_over_tokens_at_median": round(
+                              res["mlm_mask_words"]["median_us"] / a["median_us"], 2),
+                          "words_budget_filled": round(filled, 4),
                           **{f"{arm}.{k}": v for arm, st in res.items() for k, v in st.items()}}),
               flush=True)
-        del tokens, sink, new_out, old_out
+        del tokens, sink, new_out, old_out, word_out, word_ref
 
 
 def bench_bert_base(batch, steps, rounds, warmup, short_prob):
@@ -129,6 +161,9 @@ def bench_bert_base(batch, steps, rounds, warmup, short_prob):
     feeds = {
         "synthetic": dtf.data.SyntheticMLM(batch, S, max_predictions=P, device="cuda"),
         "device_tokens": DeviceTokenDataset(rows, batch, "cuda", m, P, shuffle=True),
+        "device_tokens_words": DeviceTokenDataset(
+            rows, batch, "cuda", m, P, shuffle=True,
+            continuation=continuation_table(m, "cpu").numpy()),
     }
     with OneDeviceStrategy("cuda").scope():
         model = bert.bert_base()
@@ -160,10 +195,12 @@ def bench_bert_base(batch, steps, rounds, warmup, short_prob):
     syn = runs["synthetic"]
     print(json.dumps({"model": "bert_base", "batch": batch, "seq_len": S, "max_predictions": P,
                       "short_prob": short_prob, "pad_share": round(float((rows == 0).mean()), 4),
-                      "steps_per_run": steps, "rounds": rounds, "order": "S T S T ...",
+                      "steps_per_run": steps, "rounds": rounds, "order": "S T W S T W ...",
                       "ms_per_step_runs": runs, "ms_per_step_median": med,
                       "device_tokens_minus_synthetic_ms": round(
                           med["device_tokens"] - med["synthetic"], 3),
+                      "words_minus_device_tokens_ms": round(
+                          med["device_tokens_words"] - med["device_tokens"], 3),
                       "synthetic_spread_ms": round(max(syn) - min(syn), 3)}), flush=True)
 
 
