@@ -458,6 +458,365 @@ void launch_augment_mix(const uint8_t* images, const int64_t* idx, const int* bo
                        flip, static_cast<const OutT*>(lut), partner, lam_q, cut,
                        static_cast<OutT*>(out), N, B, Hs, Ws, Ho, Wo, fill, tiles, chunks);
 }
+// ---- RandAugment inside the same launch: dtf_augment_rand_images
+//
+// Each row carries an output -> input affine map in Q16, aff = (a, b, c, d, e, f), and a chain of
+// L <= 4 pointwise ops (pops, ppar).  With V_b(v, u) the rule above for row b at output pixel
+// (oy = v, ox = u) (the row's "virtual image"), output pixel (b, oy, ox) is
+//   U = a (2 ox + 1) + b (2 oy + 1) + 2 c,  W = d (2 ox + 1) + e (2 oy + 1) + 2 f      (int64)
+//   u = U >> 17, v = W >> 17                           (PIL's nearest neighbour on pixel centres)
+//   x = V_b(v, u) if 0 <= u < Wo and 0 <= v < Ho else ra_fill
+//   x = op_k(x) for k = 0 .. L - 1:  1 Invert 255 - x;  2 Solarize x < m ? x : 255 - x;
+//       3 SolarizeAdd x < 128 ? min(255, x + m) : x;  4 Posterize x & m;
+//       5 Brightness clamp((x m) >> 16);  6 Color (C = 3) clamp((65536 g + m (x - g)) >> 16) with
+//       g = (19595 x0 + 38470 x1 + 7471 x2 + 32768) >> 16;  any other code: x
+// then the mix of augment_mix_kernel (the partner's row under its OWN map and chain), then lut.
+// ops/reference.py augment_rand_images is the same rule and the tests' oracle.
+//
+// A pixel's (u, v) is its own, so the axis tables cover ALL Wo columns and ALL Ho rows of the
+// virtual image (Ho, Wo <= 1024: 16 KB per side, an entry packed into two words), refilled per
+// item: the rule's divisions are still paid per row and column, and a pixel looks up x[u], y[v].
+// A row whose map is the identity fills only its chunk's columns and its tile's rows and skips
+// the map (the separable path).  As in augment_mix_kernel a side that is not used issues no
+// taps, and neither does a pixel that the map sends outside the virtual image.  The chain's
+// branches are block-uniform.  Parameters are clamped to their ranges when the plan is read, so
+// every value stays a byte whatever the plan holds.  The tail path makes one whole pixel per
+// thread (Color needs the three channels).
+constexpr int kRandMax = 1024;                    // Ho, Wo limit: the tables' length
+constexpr int kRandLayers = 4;
+constexpr int kAugStep = 1024;                    // table flag: tap 1 lies one stride after tap 0
+
+struct RandTables {                               // .x: tap 0's byte offset, .y: weight | flags
+  int2 x[kRandMax], y[kRandMax];
+};
+
+DTF_DEV int2 rand_entry(int o, int O, int side, int origin, int extent, int stride) {
+  const AugAxis a = aug_axis(o, O, side);
+  const int64_t t0 = (int64_t)origin + a.i0, t1 = (int64_t)origin + a.i1;
+  const bool ok0 = t0 >= 0 && t0 < extent, ok1 = t1 >= 0 && t1 < extent;
+  int2 e;
+  // tap 1 is tap 0 or the next pixel; where only tap 1 is inside it is pixel 0, offset 0
+  e.x = ok0 ? (int)t0 * stride : 0;
+  e.y = a.f | (ok0 ? kAugTap0 : 0) | (ok1 ? kAugTap1 : 0) |
+        (ok0 && ok1 && t1 != t0 ? kAugStep : 0);
+  return e;
+}
+
+// One side's tables: columns [c_lo, c_lo + c_n) and rows [r_lo, r_lo + r_n) of the virtual image.
+DTF_DEV void rand_fill_tables(RandTables& t, int tid, int r_lo, int r_n, int c_lo, int c_n,
+                              const int* __restrict__ box, bool fl, bool img_ok, int Hs, int Ws,
+                              int C, int Ho, int Wo) {
+  for (int i = tid; i < c_n; i += kAugThreads) {
+    const int ox = c_lo + i;
+    t.x[ox] = rand_entry(fl ? Wo - 1 - ox : ox, Wo, box[3], box[1], Ws, C);
+  }
+  for (int i = tid; i < r_n; i += kAugThreads) {
+    const int oy = r_lo + i;
+    int2 e = rand_entry(oy, Ho, box[2], box[0], Hs, Ws * C);
+    if (!img_ok) e.y &= 255;
+    t.y[oy] = e;
+  }
+}
+
+struct RandPlan {                                 // one row's plan, block-uniform
+  int a, b, c, d, e, f;
+  int code[kRandLayers], par[kRandLayers];
+  int n;                                          // layers up to the last that does something
+  bool ident;
+};
+
+DTF_DEV RandPlan rand_plan(const int* __restrict__ aff, const int* __restrict__ pops,
+                           const int* __restrict__ ppar, int L) {
+  RandPlan p;
+  p.a = aff[0]; p.b = aff[1]; p.c = aff[2]; p.d = aff[3]; p.e = aff[4]; p.f = aff[5];
+  p.ident = p.a == 65536 && p.b == 0 && p.c == 0 && p.d == 0 && p.e == 65536 && p.f == 0;
+  p.n = 0;
+#pragma unroll
+  for (int k = 0; k < kRandLayers; ++k) {
+    const int code = k < L ? pops[k] : 0;
+    int m = k < L ? ppar[k] : 0;
+    const int hi = code == 2 ? 256 : (code == 3 ? 128 : (1 << 18));
+    if (code != 4) m = m < 0 ? 0 : (m > hi ? hi : m);
+    p.code[k] = code;
+    p.par[k] = m;
+    if (code >= 1 && code <= 6) p.n = k + 1;
+  }
+  return p;
+}
+
+DTF_DEV int rand_pick(const int (&a)[kRandLayers], int k) {
+  return k == 0 ? a[0] : (k == 1 ? a[1] : (k == 2 ? a[2] : a[3]));
+}
+
+DTF_DEV int rand_byte(int t) { return t < 0 ? 0 : (t > 255 ? 255 : t); }
+
+// The pointwise chain on NP pixels of C channels.
+template <int C, int NP>
+DTF_DEV void rand_chain(const RandPlan& p, int (*x)[C]) {
+  for (int k = 0; k < p.n; ++k) {
+    const int code = rand_pick(p.code, k), m = rand_pick(p.par, k);
+    if (code == 1) {
+#pragma unroll
+      for (int i = 0; i < NP; ++i)
+#pragma unroll
+        for (int c = 0; c < C; ++c) x[i][c] = 255 - x[i][c];
+    } else if (code == 2) {
+#pragma unroll
+      for (int i = 0; i < NP; ++i)
+#pragma unroll
+        for (int c = 0; c < C; ++c) x[i][c] = x[i][c] < m ? x[i][c] : 255 - x[i][c];
+    } else if (code == 3) {
+#pragma unroll
+      for (int i = 0; i < NP; ++i)
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+          const int t = x[i][c] + m;
+          x[i][c] = x[i][c] < 128 ? (t > 255 ? 255 : t) : x[i][c];
+        }
+    } else if (code == 4) {
+#pragma unroll
+      for (int i = 0; i < NP; ++i)
+#pragma unroll
+        for (int c = 0; c < C; ++c) x[i][c] &= m;
+    } else if (code == 5) {
+#pragma unroll
+      for (int i = 0; i < NP; ++i)
+#pragma unroll
+        for (int c = 0; c < C; ++c) x[i][c] = rand_byte((x[i][c] * m) >> 16);   // <= 255 * 2^18
+    } else if (code == 6) {
+      if constexpr (C == 3) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+          const int g = (19595 * x[i][0] + 38470 * x[i][1] + 7471 * x[i][2] + 32768) >> 16;
+#pragma unroll
+          for (int c = 0; c < C; ++c)
+            x[i][c] = rand_byte((65536 * g + m * (x[i][c] - g)) >> 16);         // |.| < 2^27
+        }
+      }
+    }
+  }
+}
+
+// V(v, u) of the C channels, (u, v) inside the virtual image.  VEC: each tap is one load of the
+// pixel's channels; otherwise one byte per tap and channel (offsets of taps outside are inside
+// the image, so every load is).
+template <int C, bool VEC>
+DTF_DEV void rand_fetch(const uint8_t* __restrict__ img, const RandTables& t, int u, int v,
+                        int ystride, uint32_t last4, uint32_t fillw, int fill, int* x) {
+  const int2 ex = t.x[u], ey = t.y[v];
+  const int fx = ex.y & 255, fy = ey.y & 255;
+  const bool c0_ok = (ex.y & kAugTap0) != 0, c1_ok = (ex.y & kAugTap1) != 0;
+  const bool r0_ok = (ey.y & kAugTap0) != 0, r1_ok = (ey.y & kAugTap1) != 0;
+  const uint32_t o0 = (uint32_t)ex.x, o1 = o0 + ((ex.y & kAugStep) ? (uint32_t)C : 0u);
+  const uint32_t ro0 = (uint32_t)ey.x, ro1 = ro0 + ((ey.y & kAugStep) ? (uint32_t)ystride : 0u);
+  if constexpr (VEC) {
+    const uint32_t w00 = r0_ok && c0_ok ? aug_tap<C>(img, ro0 + o0, last4) : fillw;
+    const uint32_t w01 = r0_ok && c1_ok ? aug_tap<C>(img, ro0 + o1, last4) : fillw;
+    const uint32_t w10 = r1_ok && c0_ok ? aug_tap<C>(img, ro1 + o0, last4) : fillw;
+    const uint32_t w11 = r1_ok && c1_ok ? aug_tap<C>(img, ro1 + o1, last4) : fillw;
+#pragma unroll
+    for (int c = 0; c < C; ++c)
+      x[c] = aug_blend((w00 >> (8 * c)) & 255, (w01 >> (8 * c)) & 255, (w10 >> (8 * c)) & 255,
+                       (w11 >> (8 * c)) & 255, fx, fy);
+  } else {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const int v00 = img[ro0 + o0 + c], v01 = img[ro0 + o1 + c];
+      const int v10 = img[ro1 + o0 + c], v11 = img[ro1 + o1 + c];
+      const int p00 = r0_ok && c0_ok ? v00 : fill, p01 = r0_ok && c1_ok ? v01 : fill;
+      const int p10 = r1_ok && c0_ok ? v10 : fill, p11 = r1_ok && c1_ok ? v11 : fill;
+      x[c] = aug_blend(p00, p01, p10, p11, fx, fy);
+    }
+  }
+}
+
+// One side's values after the map and the chain, for the NP output pixels (oy, ox .. ox + NP).
+template <int C, bool VEC, int NP>
+DTF_DEV void rand_side(const RandPlan& p, const uint8_t* __restrict__ img, const RandTables& t,
+                       int ox, int oy, int Ho, int Wo, int ystride, uint32_t last4,
+                       uint32_t fillw, int fill, int ra_fill, int (*x)[C]) {
+  if (p.ident) {
+#pragma unroll
+    for (int i = 0; i < NP; ++i)
+      rand_fetch<C, VEC>(img, t, ox + i, oy, ystride, last4, fillw, fill, x[i]);
+  } else {
+    // |a (2 ox + 1)| < 2^31 * 2^11: int64 holds the sums
+    const int64_t X = 2 * ox + 1, Y = 2 * oy + 1;
+    int64_t U = (int64_t)p.a * X + (int64_t)p.b * Y + 2 * (int64_t)p.c;
+    int64_t W = (int64_t)p.d * X + (int64_t)p.e * Y + 2 * (int64_t)p.f;
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const int64_t u = U >> 17, v = W >> 17;
+      if (u >= 0 && u < Wo && v >= 0 && v < Ho) {
+        rand_fetch<C, VEC>(img, t, (int)u, (int)v, ystride, last4, fillw, fill, x[i]);
+      } else {
+#pragma unroll
+        for (int c = 0; c < C; ++c) x[i][c] = ra_fill;
+      }
+      U += 2 * (int64_t)p.a;
+      W += 2 * (int64_t)p.d;
+    }
+  }
+  rand_chain<C, NP>(p, x);
+}
+
+template <typename OutT, int C, bool VEC, bool MIX>
+__global__ void __launch_bounds__(kAugThreads)
+augment_rand_kernel(const uint8_t* __restrict__ images, const int64_t* __restrict__ idx,
+                    const int* __restrict__ boxes, const uint8_t* __restrict__ flip,
+                    const OutT* __restrict__ lut, const int* __restrict__ aff,
+                    const int* __restrict__ pops, const int* __restrict__ ppar,
+                    const int* __restrict__ partner, const int* __restrict__ lam_q,
+                    const int* __restrict__ cut, OutT* __restrict__ out, long N, int B, int Hs,
+                    int Ws, int Ho, int Wo, int L, int fill, int ra_fill, int tiles, int chunks) {
+  constexpr int NP = VEC ? 8 : 1;                // pixels per thread
+  __shared__ OutT s_lut[C * 256];
+  __shared__ RandTables s_t[MIX ? 2 : 1];        // row b's and, under a mix, its partner's
+  RandTables& s_a = s_t[0];
+  RandTables& s_b = s_t[MIX ? 1 : 0];
+  const int tid = threadIdx.x;
+  for (int i = tid; i < C * 256; i += kAugThreads) s_lut[i] = lut[i];
+
+  const uint32_t per_b = (uint32_t)tiles * (uint32_t)chunks;
+  const uint32_t items = (uint32_t)B * per_b;                        // < 2^31: launcher
+  const int64_t row_elems = (int64_t)Wo * C;
+  const int64_t img_bytes = (int64_t)Hs * Ws * C;
+  const int ystride = Ws * C;
+  const uint32_t last4 = (uint32_t)(Hs * Ws * C - 4);               // vector path: >= 0, launcher
+  const uint32_t fillw = (uint32_t)fill * 0x010101u;
+  for (uint32_t it = blockIdx.x; it < items; it += gridDim.x) {
+    const int b = (int)(it / per_b);
+    const int rem = (int)(it - (uint32_t)b * per_b);
+    const int tile = rem / chunks, chunk = rem - tile * chunks;
+    const int oy0 = tile * kAugRows, px0 = chunk * kAugCols;
+    const int rows = Ho - oy0 < kAugRows ? Ho - oy0 : kAugRows;
+    const int cols = Wo - px0 < kAugCols ? Wo - px0 : kAugCols;
+
+    // the mixing plan of row b, block-uniform, as in augment_mix_kernel
+    int p = b, q = 65536;
+    int cy0 = 0, cy1 = 0, cx0 = 0, cx1 = 0;
+    bool need_b = false;
+    if constexpr (MIX) {
+      const int pr = partner[b];
+      const bool mixed = pr >= 0 && pr < B && pr != b;
+      p = mixed ? pr : b;
+      q = lam_q[b];
+      q = !mixed || q > 65536 ? 65536 : (q < 0 ? 0 : q);
+      if (mixed && cut[4 * b + 2] > 0 && cut[4 * b + 3] > 0) {
+        const int64_t y = cut[4 * b], x = cut[4 * b + 1];
+        const int64_t ye = y + cut[4 * b + 2], xe = x + cut[4 * b + 3];
+        cy0 = (int)(y < 0 ? 0 : (y > Ho ? Ho : y));
+        cx0 = (int)(x < 0 ? 0 : (x > Wo ? Wo : x));
+        cy1 = (int)(ye < 0 ? 0 : (ye > Ho ? Ho : ye));
+        cx1 = (int)(xe < 0 ? 0 : (xe > Wo ? Wo : xe));
+        if (cx1 <= cx0) cy1 = cy0;
+      }
+      const bool box_here = cy0 < oy0 + rows && cy1 > oy0 && cx0 < px0 + cols && cx1 > px0 &&
+                            cy1 > cy0;
+      need_b = q < 65536 || box_here;
+    }
+
+    const RandPlan pa = rand_plan(aff + 6 * b, pops + (int64_t)L * b, ppar + (int64_t)L * b, L);
+    RandPlan pb = pa;
+    if (need_b) pb = rand_plan(aff + 6 * p, pops + (int64_t)L * p, ppar + (int64_t)L * p, L);
+    const int64_t na = idx[b], nb = need_b ? idx[p] : na;
+    const bool a_ok = na >= 0 && na < N, b_ok = nb >= 0 && nb < N;   // a bad index reads as fill
+    const uint8_t* img_a = images + (a_ok ? na : 0) * img_bytes;     // block-uniform
+    const uint8_t* img_b = images + (b_ok ? nb : 0) * img_bytes;
+
+    __syncthreads();                 // the previous item's table reads (and the LUT staging)
+    rand_fill_tables(s_a, tid, pa.ident ? oy0 : 0, pa.ident ? rows : Ho, pa.ident ? px0 : 0,
+                     pa.ident ? cols : Wo, boxes + 4 * b, flip[b] != 0, a_ok, Hs, Ws, C, Ho, Wo);
+    if (need_b)
+      rand_fill_tables(s_b, tid, pb.ident ? oy0 : 0, pb.ident ? rows : Ho, pb.ident ? px0 : 0,
+                       pb.ident ? cols : Wo, boxes + 4 * p, flip[p] != 0, b_ok, Hs, Ws, C, Ho,
+                       Wo);
+    __syncthreads();
+
+    const int gpc = cols / NP;                            // this chunk's groups of a row
+    const float inv_gpc = 1.0f / (float)gpc;
+    for (int k = tid; k < rows * gpc; k += kAugThreads) {
+      int r = (int)(((float)k + 0.5f) * inv_gpc);          // k / gpc, r < 16: fixed up below
+      r = r * gpc > k ? r - 1 : r;
+      r = (r + 1) * gpc <= k ? r + 1 : r;
+      const int g = k - r * gpc;
+      const int oy = oy0 + r, gx = px0 + g * NP;
+      // the box's columns inside this group of pixels: [lo, hi)
+      const int lo = cx0 > gx ? cx0 : gx, hi = cx1 < gx + NP ? cx1 : gx + NP;
+      const int n_in = oy >= cy0 && oy < cy1 && hi > lo ? hi - lo : 0;
+      const bool use_a = n_in < NP && q > 0, use_b = n_in > 0 || q < 65536;
+
+      int xa[NP][C], xb[NP][C];
+#pragma unroll
+      for (int i = 0; i < NP; ++i)
+#pragma unroll
+        for (int c = 0; c < C; ++c) xa[i][c] = xb[i][c] = 0;
+      if (use_a)
+        rand_side<C, VEC, NP>(pa, img_a, s_a, gx, oy, Ho, Wo, ystride, last4, fillw, fill,
+                              ra_fill, xa);
+      if (MIX && use_b)
+        rand_side<C, VEC, NP>(pb, img_b, s_b, gx, oy, Ho, Wo, ystride, last4, fillw, fill,
+                              ra_fill, xb);
+
+      OutT res[NP * C];
+#pragma unroll
+      for (int i = 0; i < NP; ++i) {
+        const bool inside = n_in > 0 && gx + i >= lo && gx + i < hi;
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+          res[i * C + c] = s_lut[c * 256 + (MIX ? aug_mix(xa[i][c], xb[i][c], q, inside)
+                                                : xa[i][c])];
+      }
+
+      OutT* dst = out + ((int64_t)b * Ho + oy) * row_elems + (int64_t)gx * C;
+      if constexpr (!VEC) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) dst[c] = res[c];
+      } else if constexpr (sizeof(OutT) == 2) {
+#pragma unroll
+        for (int w4 = 0; w4 < C; ++w4) {
+          const OutT* h = res + 8 * w4;
+          uint4 w;                     // the table already holds bf16 bits: pack them as they are
+          w.x = (uint32_t)h[0] | ((uint32_t)h[1] << 16);
+          w.y = (uint32_t)h[2] | ((uint32_t)h[3] << 16);
+          w.z = (uint32_t)h[4] | ((uint32_t)h[5] << 16);
+          w.w = (uint32_t)h[6] | ((uint32_t)h[7] << 16);
+          reinterpret_cast<uint4*>(dst)[w4] = w;
+        }
+      } else {
+#pragma unroll
+        for (int w4 = 0; w4 < 2 * C; ++w4)
+          reinterpret_cast<float4*>(dst)[w4] =
+              make_float4(res[4 * w4], res[4 * w4 + 1], res[4 * w4 + 2], res[4 * w4 + 3]);
+      }
+    }
+  }
+}
+
+template <typename OutT, int C>
+void launch_augment_rand(const uint8_t* images, const int64_t* idx, const int* boxes,
+                         const uint8_t* flip, const void* lut, const int* aff, const int* pops,
+                         const int* ppar, int L, const int* partner, const int* lam_q,
+                         const int* cut, void* out, long N, int B, int Hs, int Ws, int Ho, int Wo,
+                         int fill, int ra_fill, int max_blocks, hipStream_t st) {
+  const bool vec = (Wo * C) % 8 == 0 && (long)Hs * Ws * C >= 4;      // as launch_augment
+  const int tiles = (Ho + kAugRows - 1) / kAugRows, chunks = (Wo + kAugCols - 1) / kAugCols;
+  const long items = (long)B * tiles * chunks;
+  if (items >= 2147483647L) throw std::runtime_error("augment_rand_images: batch too large");
+  const long cap = max_blocks > 0 ? max_blocks : kAugDefaultBlocks;
+  const dim3 grid((unsigned)(items < cap ? items : cap)), block(kAugThreads);
+#define DTF_RAND(VEC, MIX)                                                                      \
+  hipLaunchKernelGGL((augment_rand_kernel<OutT, C, VEC, MIX>), grid, block, 0, st, images, idx, \
+                     boxes, flip, static_cast<const OutT*>(lut), aff, pops, ppar, partner,      \
+                     lam_q, cut, static_cast<OutT*>(out), N, B, Hs, Ws, Ho, Wo, L, fill,        \
+                     ra_fill, tiles, chunks)
+  if (partner != nullptr) {
+    if (vec) DTF_RAND(true, true); else DTF_RAND(false, true);
+  } else {
+    if (vec) DTF_RAND(true, false); else DTF_RAND(false, false);
+  }
+#undef DTF_RAND
+}
 }  // namespace
 
 void dtf_augment_images(const uint8_t* images, const int64_t* idx, const int* boxes,
@@ -502,6 +861,39 @@ void dtf_augment_mix_images(const uint8_t* images, const int64_t* idx, const int
 #define DTF_AUG(T, CC)                                                                          \
   launch_augment_mix<T, CC>(images, idx, boxes, flip, lut, partner, lam_q, cut, out, N, B, Hs,  \
                             Ws, Ho, Wo, fill, max_blocks, st)
+  if (out_bf16) {
+    if (C == 3) DTF_AUG(bf16_t, 3); else DTF_AUG(bf16_t, 1);
+  } else {
+    if (C == 3) DTF_AUG(float, 3); else DTF_AUG(float, 1);
+  }
+#undef DTF_AUG
+}
+
+void dtf_augment_rand_images(const uint8_t* images, const int64_t* idx, const int* boxes,
+                             const uint8_t* flip, const void* lut, const int* aff,
+                             const int* pops, const int* ppar, int L, const int* partner,
+                             const int* lam_q, const int* cut, void* out, long N, int B, int Hs,
+                             int Ws, int C, int Ho, int Wo, int fill, int ra_fill, int out_bf16,
+                             int max_blocks, hipStream_t st) {
+  if (C != 1 && C != 3) throw std::runtime_error("augment_rand_images: C must be 1 or 3");
+  if (N < 1 || Hs < 1 || Ws < 1) throw std::runtime_error("augment_rand_images: empty image set");
+  if (B < 0 || Ho < 1 || Wo < 1) throw std::runtime_error("augment_rand_images: bad output shape");
+  // the axis tables hold every column and row of the output
+  if (Ho > kRandMax || Wo > kRandMax)
+    throw std::runtime_error("augment_rand_images: output sides are at most 1024");
+  if ((long)Hs * Ws * C > 2147483647L)
+    throw std::runtime_error("augment_rand_images: one image must stay below 2 GiB");
+  if (L < 1 || L > kRandLayers)
+    throw std::runtime_error("augment_rand_images: 1 to 4 pointwise layers");
+  if (fill < 0 || fill > 255 || ra_fill < 0 || ra_fill > 255)
+    throw std::runtime_error("augment_rand_images: fill and ra_fill must be one byte");
+  if ((partner == nullptr) != (lam_q == nullptr) || (partner == nullptr) != (cut == nullptr))
+    throw std::runtime_error("augment_rand_images: partner, lam_q and cut go together");
+  if (max_blocks < 0) throw std::runtime_error("augment_rand_images: negative max_blocks");
+  if (B == 0) return;
+#define DTF_AUG(T, CC)                                                                          \
+  launch_augment_rand<T, CC>(images, idx, boxes, flip, lut, aff, pops, ppar, L, partner, lam_q, \
+                             cut, out, N, B, Hs, Ws, Ho, Wo, fill, ra_fill, max_blocks, st)
   if (out_bf16) {
     if (C == 3) DTF_AUG(bf16_t, 3); else DTF_AUG(bf16_t, 1);
   } else {

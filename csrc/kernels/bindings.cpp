@@ -164,6 +164,19 @@ PYBIND11_MODULE(_dtf_hip, m) {
                            S(st));
     check_launch("augment_mix_images");
   });
+  // partner = lam_q = cut = 0: unmixed
+  m.def("augment_rand_images", [](uintptr_t images, uintptr_t idx, uintptr_t boxes,
+                                  uintptr_t flip, uintptr_t lut, uintptr_t aff, uintptr_t pops,
+                                  uintptr_t ppar, int L, uintptr_t partner, uintptr_t lam_q,
+                                  uintptr_t cut, uintptr_t out, long N, int B, int Hs, int Ws,
+                                  int C, int Ho, int Wo, int fill, int ra_fill, int out_bf16,
+                                  int max_blocks, uintptr_t st) {
+    dtf_augment_rand_images(P<uint8_t>(images), P<int64_t>(idx), P<int>(boxes), P<uint8_t>(flip),
+                            P<void>(lut), P<int>(aff), P<int>(pops), P<int>(ppar), L,
+                            P<int>(partner), P<int>(lam_q), P<int>(cut), P<void>(out), N, B, Hs,
+                            Ws, C, Ho, Wo, fill, ra_fill, out_bf16, max_blocks, S(st));
+    check_launch("augment_rand_images");
+  });
   // rule = [vocab_size, pad_id, cls_id, sep_id, mask_id, random_low, prob_q16];
   // outs = [input_ids, segment_ids, input_mask, masked_lm_positions, masked_lm_ids,
   //         masked_lm_weights]; continuation: uint8 [vocab_size], or 0 for the token rule

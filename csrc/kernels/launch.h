@@ -299,6 +299,15 @@ void dtf_augment_mix_images(const uint8_t* images, const int64_t* idx, const int
                             const int* lam_q, const int* cut, void* out, long N, int B, int Hs,
                             int Ws, int C, int Ho, int Wo, int fill, int out_bf16, int max_blocks,
                             hipStream_t st);
+// the same with RandAugment: row b's output -> input affine map aff[b] = (a, b, c, d, e, f) in
+// Q16 and its L <= 4 pointwise ops (pops[b], ppar[b]); Ho, Wo <= 1024; partner / lam_q / cut all
+// null: unmixed
+void dtf_augment_rand_images(const uint8_t* images, const int64_t* idx, const int* boxes,
+                             const uint8_t* flip, const void* lut, const int* aff,
+                             const int* pops, const int* ppar, int L, const int* partner,
+                             const int* lam_q, const int* cut, void* out, long N, int B, int Hs,
+                             int Ws, int C, int Ho, int Wo, int fill, int ra_fill, int out_bf16,
+                             int max_blocks, hipStream_t st);
 
 // ---- mlm_mask.hip
 // the masking settings (data.TokenMasking), a kernel argument by value

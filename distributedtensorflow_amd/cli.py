@@ -116,6 +116,15 @@ def build_parser():
     p.add_argument("--cutmix_alpha", type=float, default=0.0,
                    help="with --image_data: CutMix, box area share ~ Beta(A, A); with "
                         "--mixup_alpha too, each batch draws one of the two")
+    p.add_argument("--randaugment", type=int, default=0, metavar="N",
+                   help="with --image_data: RandAugment of each training example inside the "
+                        "augmentation kernel, N layers (1 to 4; 0 = off)")
+    p.add_argument("--ra_magnitude", type=float, default=9.0,
+                   help="--randaugment: the magnitude, 0 to 10")
+    p.add_argument("--ra_mstd", type=float, default=0.5,
+                   help="--randaugment: standard deviation of the per-op magnitude noise")
+    p.add_argument("--ra_prob", type=float, default=0.5,
+                   help="--randaugment: the chance that a layer's op is applied")
     p.add_argument("--num_classes", type=int, default=None,
                    help="classes of the --image_data set (default: 1000 for ResNet, 10 for MNIST "
                         "models)")
@@ -158,6 +167,15 @@ def check_data_args(args):
             raise SystemExit(f"--mixup_alpha / --cutmix_alpha: {args.model} has no two-label loss")
         if not args.image_data:
             raise SystemExit("--mixup_alpha / --cutmix_alpha need --image_data")
+    if args.randaugment:
+        if args.model.startswith("bert"):
+            raise SystemExit(f"--randaugment: {args.model} is not an image model")
+        if not args.image_data:
+            raise SystemExit("--randaugment needs --image_data")
+        if not 1 <= args.randaugment <= 4:
+            raise SystemExit("--randaugment takes 1 to 4 layers")
+        if not 0 <= args.ra_magnitude <= 10 or args.ra_mstd < 0 or not 0 <= args.ra_prob <= 1:
+            raise SystemExit("--ra_magnitude is in [0, 10], --ra_mstd >= 0, --ra_prob in [0, 1]")
 
 
 DEFAULTS = {   # (batch, optimizer, learning rate) per model
@@ -453,6 +471,9 @@ def run(args):
     for k in ("mixup_alpha", "cutmix_alpha"):
         if getattr(args, k):
             result[k] = getattr(args, k)
+    if args.randaugment:
+        for k in ("randaugment", "ra_magnitude", "ra_mstd", "ra_prob"):
+            result[k] = getattr(args, k)
     if args.whole_word_mask:
         result["whole_word_mask"] = True
     steps_done = global_step.value() - (first_step or 0)
@@ -485,7 +506,7 @@ def _image_dataset(args, split, num_classes, batch, device, dtype, shards, shard
     """--image_data: the HBM-resident ``split`` of DIR as a DeviceImageDataset.  ResNets get
     --image_size outputs under the ImageNet channel statistics, the MNIST models 28 x 28 x 1
     scaled to [0, 1]; the batch shrinks to the shard where that is smaller."""
-    from .data import DeviceImageDataset, ImageAugment, ImageMix, images
+    from .data import DeviceImageDataset, ImageAugment, ImageMix, ImageRandAugment, images
     from .data.images import IMAGENET_MEAN, IMAGENET_STD
     imgs, labels = images.load_arrays(args.image_data, split, num_classes)
     C = imgs.shape[3]
@@ -505,12 +526,16 @@ def _image_dataset(args, split, num_classes, batch, device, dtype, shards, shard
     mix = None
     if split == "train" and (args.mixup_alpha or args.cutmix_alpha):
         mix = ImageMix(args.mixup_alpha, args.cutmix_alpha)
+    rand = None
+    if split == "train" and args.randaugment:
+        rand = ImageRandAugment(args.randaugment, args.ra_magnitude, args.ra_mstd, args.ra_prob)
     return DeviceImageDataset(imgs, labels, batch, device, aug, dtype=dtype,
                               shuffle=split == "train", seed=args.seed + stream,
                               aug_seed=args.seed + 1000003 * (stream + 1),
                               num_shards=shards, shard_index=shard_index,
                               flatten=args.model == "mnist_mlp", mix=mix,
-                              mix_seed=args.seed + 2000003 * (stream + 1))
+                              mix_seed=args.seed + 2000003 * (stream + 1), rand=rand,
+                              rand_seed=args.seed + 3000017 * (stream + 1))
 
 
 def _token_dataset(args, split, batch, device, shards, shard_index):

@@ -4,12 +4,14 @@ on-device masked-LM example creation), synthetic ImageNet / MLM generators for b
 from . import images, mnist, tokens
 from .dataset import Dataset, Iterator, NativeBatchDataset
 from .device import DeviceArrayDataset
-from .images import DeviceImageDataset, ImageAugment, ImageMix, MixedLabels, mix_plan
+from .images import (DeviceImageDataset, ImageAugment, ImageMix, ImageRandAugment, MixedLabels,
+                     mix_plan, randaugment_plan)
 from .synthetic import SyntheticImageNet, SyntheticMLM
 from .tokens import (DeviceTokenDataset, TokenMasking, load_continuation, load_token_arrays,
                      wordpiece_continuation)
 
 __all__ = ["images", "mnist", "tokens", "Dataset", "DeviceArrayDataset", "DeviceImageDataset",
-           "DeviceTokenDataset", "ImageAugment", "ImageMix", "Iterator", "MixedLabels",
-           "NativeBatchDataset", "SyntheticImageNet", "SyntheticMLM", "TokenMasking",
-           "load_continuation", "load_token_arrays", "mix_plan", "wordpiece_continuation"]
+           "DeviceTokenDataset", "ImageAugment", "ImageMix", "ImageRandAugment", "Iterator",
+           "MixedLabels", "NativeBatchDataset", "SyntheticImageNet", "SyntheticMLM",
+           "TokenMasking", "load_continuation", "load_token_arrays", "mix_plan",
+           "randaugment_plan", "wordpiece_continuation"]

@@ -21,6 +21,10 @@ Sample mixing (:class:`ImageMix`: Mixup, CutMix) happens in the same kernel
 (``ops.augment_mix_images``): :func:`mix_plan` turns the draws of a third CPU generator into each
 row's partner, blend weight and cut box, and the batch's labels become
 :class:`MixedLabels` for ``ops.mixed_softmax_cross_entropy``.
+
+RandAugment (:class:`ImageRandAugment`) happens in the same kernel too
+(``ops.augment_rand_images``): :func:`randaugment_plan` turns the draws of a fourth CPU generator
+into each row's composed affine map and its pointwise ops.
 """
 from __future__ import annotations
 
@@ -236,6 +240,128 @@ def mix_plan(u, g, B, out_hw, mix):
             lam.to(torch.float32).expand(B).contiguous())
 
 
+# ----------------------------------------------------------------------------- RandAugment
+
+RAND_OPS = ("rotate", "shear_x", "shear_y", "translate_x", "translate_y", "invert", "solarize",
+            "solarize_add", "posterize", "brightness", "color")
+_RAND_GEOMETRIC = 5                 # the first five of RAND_OPS resample; the others are pointwise
+# the pointwise op codes of ops.augment_rand_images, by position in RAND_OPS
+_RAND_CODE = {5: 1, 6: 2, 7: 3, 8: 4, 9: 5, 10: 6}
+
+
+class ImageRandAugment:
+    """RandAugment (Cubuk et al. 2020) of a :class:`DeviceImageDataset`, with the semantics of
+    timm's ``rand-m{magnitude}-mstd{mstd}-inc1``: each of ``num_layers`` layers picks one of
+    ``ops`` uniformly, applies it with chance ``prob`` at level
+    ``clamp(magnitude + mstd * N(0, 1), 0, 10) / 10`` under the "increasing" magnitude maps and
+    a random sign.  ``ops``: names out of :data:`RAND_OPS` (default: all eleven, timm's
+    increasing set without AutoContrast, Equalize, Contrast and Sharpness).  ``translate``: the
+    largest shift as a share of the output's side."""
+
+    def __init__(self, num_layers=2, magnitude=9.0, mstd=0.5, prob=0.5, ops=None, translate=0.45):
+        self.num_layers = int(num_layers)
+        self.magnitude, self.mstd = float(magnitude), float(mstd)
+        self.prob, self.translate = float(prob), float(translate)
+        if not 1 <= self.num_layers <= 4 or self.num_layers != num_layers:
+            raise ValueError("ImageRandAugment: num_layers must be 1, 2, 3 or 4")
+        if not 0 <= self.magnitude <= 10:
+            raise ValueError("ImageRandAugment: magnitude must be in [0, 10]")
+        if not (self.mstd >= 0 and math.isfinite(self.mstd)):
+            raise ValueError("ImageRandAugment: mstd must be finite and >= 0")
+        if not 0 <= self.prob <= 1:
+            raise ValueError("ImageRandAugment: prob must be in [0, 1]")
+        if not math.isfinite(self.translate):
+            raise ValueError("ImageRandAugment: translate must be finite")
+        self.ops = tuple(RAND_OPS if ops is None else ops)
+        unknown = [o for o in self.ops if o not in RAND_OPS]
+        if unknown or not self.ops:
+            raise ValueError(f"ImageRandAugment: ops {unknown or self.ops} not in {RAND_OPS}")
+
+    def draw(self, B, generator):
+        """The draws of one batch from ``generator`` (CPU) -> (u, z) for
+        :func:`randaugment_plan`: ``u`` float64 [B, L, 3] uniforms, ``z`` float64 [B, L] standard
+        normals (drawn whatever ``mstd`` is, so the stream does not depend on it)."""
+        u = torch.rand(B, self.num_layers, 3, generator=generator, dtype=torch.float64,
+                       device="cpu")
+        z = torch.randn(B, self.num_layers, generator=generator, dtype=torch.float64,
+                        device="cpu")
+        return u, z
+
+
+def randaugment_plan(u, z, out_hw, ra):
+    """The RandAugment plan of one batch from supplied draws (:meth:`ImageRandAugment.draw`),
+    computed on the host in float64 -> (aff int32 [B, 6], pops int32 [B, L], ppar int32 [B, L]),
+    the arguments of ``ops.augment_rand_images``.
+
+    Per example and layer k: the op is ``ops[min(floor(u0 K), K - 1)]`` of the K ops, applied iff
+    ``u1 < prob``; ``sign = -1`` iff ``u2 >= 0.5``;
+    ``l = clamp(magnitude + mstd z, 0, 10) / 10``.  Magnitudes (timm's increasing maps): Rotate
+    ``sign 30 l`` degrees; ShearX / ShearY ``sign 0.3 l``; TranslateX / TranslateY
+    ``sign translate l Wo`` (``Ho``) pixels; Solarize ``m = 256 - floor(256 l)``; SolarizeAdd
+    ``m = min(128, floor(110 l))``; Posterize ``bits = max(0, 4 - floor(4 l))``,
+    ``m = 256 - (1 << (8 - bits))``; Brightness / Color factor ``max(0.1, 1 + sign 0.9 l)``,
+    ``m = floor(65536 factor + 0.5)``.
+
+    A geometric op is its inverse (output -> input) matrix in pixel-centre coordinates, PIL's
+    convention: ShearX s ``(1, s, 0, 0, 1, 0)``, ShearY s ``(1, 0, 0, s, 1, 0)``, TranslateX t
+    ``(1, 0, t, 0, 1, 0)``, TranslateY t ``(1, 0, 0, 0, 1, t)``, Rotate by theta degrees about
+    ``(cx, cy) = (Wo / 2, Ho / 2)`` with ``r = -theta pi / 180``:
+    ``(cos r, sin r, cx - cx cos r - cy sin r, -sin r, cos r, cy + cx sin r - cy cos r)``.  The
+    geometric ops of an example compose in layer order, ``M = M_g1 M_g2 ...`` (the last op's map
+    meets the output pixel first), and each of M's six entries becomes
+    ``floor(65536 value + 0.5)``.  Layers that were geometric or not applied hold code 0."""
+    Ho, Wo = (int(v) for v in out_hw)
+    L = ra.num_layers
+    if u.dim() != 3 or tuple(u.shape[1:]) != (L, 3) or tuple(z.shape) != (u.shape[0], L):
+        raise ValueError(f"randaugment_plan: u must be [B, {L}, 3] and z [B, {L}]")
+    u, z = u.to(torch.float64), z.to(torch.float64)   # formed on the host, whatever the default
+    B, K = u.shape[0], len(ra.ops)
+    kinds = torch.tensor([RAND_OPS.index(o) for o in ra.ops], dtype=torch.int64, device="cpu")
+    kind = kinds[torch.clamp(torch.floor(u[..., 0] * K), max=K - 1).long()]        # [B, L]
+    applied = u[..., 1] < ra.prob
+    one = torch.ones(B, L, dtype=torch.float64, device="cpu")
+    zero = torch.zeros_like(one)
+    sign = torch.where(u[..., 2] >= 0.5, -one, one)
+    l = torch.clamp(ra.magnitude + ra.mstd * z, 0.0, 10.0) / 10.0
+
+    def on(k):
+        return applied & (kind == RAND_OPS.index(k))
+
+    # ---- the geometric ops: each layer's matrix (the identity where it has none)
+    r = -(sign * 30.0 * l) * (math.pi / 180.0)
+    cs, sn = torch.cos(r), torch.sin(r)
+    cx, cy = Wo / 2.0, Ho / 2.0
+    shear, shift = sign * 0.3 * l, sign * ra.translate * l
+    rot = on("rotate")
+    a = torch.where(rot, cs, one)
+    b = torch.where(rot, sn, torch.where(on("shear_x"), shear, zero))
+    c = torch.where(rot, cx - cx * cs - cy * sn, torch.where(on("translate_x"), shift * Wo, zero))
+    d = torch.where(rot, -sn, torch.where(on("shear_y"), shear, zero))
+    e = torch.where(rot, cs, one)
+    f = torch.where(rot, cy + cx * sn - cy * cs, torch.where(on("translate_y"), shift * Ho, zero))
+    A, Bm, Cm, D, E, F = a[:, 0], b[:, 0], c[:, 0], d[:, 0], e[:, 0], f[:, 0]
+    for k in range(1, L):                                  # M = M M_k, entry by entry
+        a2, b2, c2, d2, e2, f2 = a[:, k], b[:, k], c[:, k], d[:, k], e[:, k], f[:, k]
+        A, Bm, Cm, D, E, F = (A * a2 + Bm * d2, A * b2 + Bm * e2, A * c2 + Bm * f2 + Cm,
+                              D * a2 + E * d2, D * b2 + E * e2, D * c2 + E * f2 + F)
+    aff = torch.floor(torch.stack([A, Bm, Cm, D, E, F], dim=1) * 65536.0 + 0.5)
+
+    # ---- the pointwise ops
+    bits = torch.clamp(4.0 - torch.floor(4.0 * l), min=0.0)
+    factor = torch.floor(torch.clamp(1.0 + sign * 0.9 * l, min=0.1) * 65536.0 + 0.5)
+    par = {"invert": zero, "solarize": 256.0 - torch.floor(256.0 * l),
+           "solarize_add": torch.clamp(torch.floor(110.0 * l), max=128.0),
+           "posterize": 256.0 - torch.pow(2.0, 8.0 - bits), "brightness": factor,
+           "color": factor}
+    pops, ppar = zero, zero
+    for i, code in _RAND_CODE.items():
+        hit = on(RAND_OPS[i])
+        pops = torch.where(hit, zero + code, pops)
+        ppar = torch.where(hit, par[RAND_OPS[i]], ppar)
+    return (aff.to(torch.int32).contiguous(), pops.to(torch.int32).contiguous(),
+            ppar.to(torch.int32).contiguous())
+
+
 # ----------------------------------------------------------------------------- the dataset
 
 class ImageAugment:
@@ -297,13 +423,19 @@ class DeviceImageDataset(DeviceArrayDataset):
     come from a third CPU generator (``mix_seed``), so example order and crops are those of the
     unmixed dataset.  ``single_pass()`` never mixes.
 
+    ``rand``: an :class:`ImageRandAugment`.  Training batches then go through
+    ``ops.augment_rand_images`` (with the mixing plan when ``mix`` is set too); the plan's draws
+    come from a fourth CPU generator (``rand_seed``), so example order, crops, flips and the mix
+    are those of the same dataset without it.  ``single_pass()`` never applies it.
+
     Upload: the (possibly memory-mapped) array is copied ``chunk_bytes`` at a time into a
     preallocated device tensor, the shard selection applied per chunk, so the host never holds
     a second copy of the set.  ``flatten``: batches are [B, Ho * Wo * C] (the MLP's input)."""
 
     def __init__(self, images, labels, batch_size, device, augment, dtype=None, shuffle=False,
                  seed=0, aug_seed=0, num_shards=1, shard_index=0, drop_remainder=True,
-                 chunk_bytes=256 << 20, flatten=False, mix=None, mix_seed=0):
+                 chunk_bytes=256 << 20, flatten=False, mix=None, mix_seed=0, rand=None,
+                 rand_seed=0):
         device = torch.device(device)
         if images.dtype != np.uint8 or images.ndim != 4 or images.shape[3] not in (1, 3):
             raise ValueError("DeviceImageDataset: images must be uint8 [N, H, W, C], C in (1, 3)")
@@ -344,6 +476,14 @@ class DeviceImageDataset(DeviceArrayDataset):
         if mix is not None:
             self._mix_gen = torch.Generator(device="cpu")
             self._mix_gen.manual_seed(mix_seed)
+        if rand is not None and not isinstance(rand, ImageRandAugment):
+            raise ValueError("DeviceImageDataset: rand must be an ImageRandAugment")
+        if rand is not None and max(augment.out_hw) > 1024:
+            raise ValueError("DeviceImageDataset: rand needs output sides of at most 1024")
+        self.rand = rand
+        if rand is not None:
+            self._rand_gen = torch.Generator(device="cpu")
+            self._rand_gen.manual_seed(rand_seed)
 
     @staticmethod
     def _upload(images, device, num_shards, shard_index, chunk_bytes):
@@ -406,6 +546,39 @@ class DeviceImageDataset(DeviceArrayDataset):
         return x, MixedLabels(labels, labels.index_select(0, partner.long()),
                               plan[:, 6].contiguous().view(torch.float32))
 
+    def _train_rand(self, idx):
+        """One training batch under RandAugment: its plan rides the boxes' copy as 6 + 2 L more
+        int32 columns (the map, the op codes, their parameters), ahead of the mixing plan's 7
+        when there is a mix."""
+        from .. import ops
+        B, L = idx.numel(), self.rand.num_layers
+        cols = list(randaugment_plan(*self.rand.draw(B, self._rand_gen), self.augment.out_hw,
+                                     self.rand))
+        if self.mix is not None:
+            partner, lam_q, cut, lam = mix_plan(*self.mix.draw(B, self._mix_gen), B,
+                                                self.augment.out_hw, self.mix)
+            cols += [partner.unsqueeze(1), lam_q.unsqueeze(1), cut,
+                     lam.view(torch.int32).unsqueeze(1)]
+        boxes, flip, plan = self._train_boxes(B, torch.cat(cols, dim=1))
+        rand = (plan[:, :6].contiguous(), plan[:, 6:6 + L].contiguous(),
+                plan[:, 6 + L:6 + 2 * L].contiguous())
+        labels = self.labels.index_select(0, idx)
+        if self.mix is None:
+            x = ops.augment_rand_images(self.images, idx.contiguous(), boxes, flip, self._lut,
+                                        self.augment.out_hw, *rand, fill=self.augment.fill)
+        else:
+            plan = plan[:, 6 + 2 * L:]
+            partner = plan[:, 0].contiguous()
+            x = ops.augment_rand_images(self.images, idx.contiguous(), boxes, flip, self._lut,
+                                        self.augment.out_hw, *rand, partner,
+                                        plan[:, 1].contiguous(), plan[:, 2:6].contiguous(),
+                                        fill=self.augment.fill)
+            labels = MixedLabels(labels, labels.index_select(0, partner.long()),
+                                 plan[:, 6].contiguous().view(torch.float32))
+        if self.flatten:
+            x = x.reshape(B, -1)
+        return x, labels
+
     def single_pass(self, batch_size=None):
         """This shard's examples in order, once, the remainder batch included, under the
         evaluation transform (centre crop, no flip).  Touches neither generator nor the
@@ -418,6 +591,8 @@ class DeviceImageDataset(DeviceArrayDataset):
     def _gather(self, idx, train=True):
         from .. import ops
         B = idx.numel()
+        if train and self.rand is not None:
+            return self._train_rand(idx)
         if train and self.mix is not None:
             return self._train_mixed(idx)
         if train:

@@ -358,6 +358,24 @@ def augment_mix_images(images, idx, boxes, flip, lut, out_hw, partner, lam_q, cu
                                         fill)
 
 
+def augment_rand_images(images, idx, boxes, flip, lut, out_hw, aff, pops, ppar, partner=None,
+                        lam_q=None, cut=None, fill=0, ra_fill=128, max_blocks=0):
+    """:func:`augment_images` (with ``partner`` / ``lam_q`` / ``cut``, all given or all None:
+    :func:`augment_mix_images`) with RandAugment in the same pass: row b's virtual image (its
+    crop, resize and flip) is resampled through the output -> input affine map ``aff[b]`` =
+    (a, b, c, d, e, f) in Q16, nearest neighbour on pixel centres, reading ``ra_fill`` outside
+    it, and then passes through the pointwise ops ``pops[b]`` with parameters ``ppar[b]``
+    (int32 [B, L], L <= 4: 0 none, 1 Invert, 2 Solarize, 3 SolarizeAdd, 4 Posterize,
+    5 Brightness, 6 Color).  A partner's row is formed under its own map and ops.  Integer
+    arithmetic, so both backends give the same bits; the rule is spelled out in
+    :func:`reference.augment_rand_images`.  ``max_blocks``: grid cap of the kernel (0 = default)."""
+    if _use_native(images):
+        return _native().augment_rand_images(images, idx, boxes, flip, lut, out_hw, aff, pops,
+                                             ppar, partner, lam_q, cut, fill, ra_fill, max_blocks)
+    return reference.augment_rand_images(images, idx, boxes, flip, lut, out_hw, aff, pops, ppar,
+                                         partner, lam_q, cut, fill, ra_fill)
+
+
 def mlm_mask_tokens(tokens, idx, seed, max_predictions, masking, example_stride=1,
                     example_offset=0, continuation=None):
     """One batch of an HBM-resident token set -> BERT's masked-LM inputs: gather ``idx`` from
@@ -442,7 +460,7 @@ _OPS = ("conv2d", "conv2d_bias_relu", "batch_norm", "batch_norm_add_batch_norm",
         "dense_gelu_dense", "relu", "max_pool2d", "global_avg_pool", "sparse_softmax_cross_entropy",
         "softmax_cross_entropy_clipped_sum", "gelu", "attention", "dropout", "attention_qkv",
         "mlm_loss", "eval_rows", "in_top_k", "augment_images", "mlm_mask_tokens",
-        "augment_mix_images", "mixed_softmax_cross_entropy")
+        "augment_mix_images", "mixed_softmax_cross_entropy", "augment_rand_images")
 _FENCED = _OPS
 for _name in _OPS:
     globals()[_name] = _dispatch(_name, globals()[_name], True)
@@ -456,5 +474,5 @@ __all__ = [
     "bias_dropout_add_layer_norm", "embedding_layer_norm", "bias_gelu", "bias_gelu_dense",
     "dense_gelu_dense", "attention_qkv", "mlm_loss", "eval_rows", "in_top_k", "augment_images",
     "mlm_mask_tokens", "ema_update", "grad_accumulate", "augment_mix_images",
-    "mixed_softmax_cross_entropy",
+    "mixed_softmax_cross_entropy", "augment_rand_images",
 ]

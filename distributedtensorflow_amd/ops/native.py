@@ -2088,6 +2088,31 @@ def augment_mix_images(images, idx, boxes, flip, lut, out_hw, partner, lam_q, cu
     return out
 
 
+def augment_rand_images(images, idx, boxes, flip, lut, out_hw, aff, pops, ppar, partner=None,
+                        lam_q=None, cut=None, fill=0, ra_fill=128, max_blocks=0):
+    """``augment_images`` / ``augment_mix_images`` with RandAugment (a per-row affine map and a
+    chain of pointwise ops) in the SAME launch (csrc/kernels/augment.hip; the rule:
+    ops/reference.py augment_rand_images, bit for bit).  An unknown op code acts as none and
+    parameters are clamped to their ranges, rather than raising (no device sync to check either
+    here); indices and partners out of range read as in the other two kernels."""
+    from .reference import _augment_rand_check
+    if not images.is_cuda:
+        raise ValueError("native augment_rand_images needs GPU tensors")
+    B, Ho, Wo, L = _augment_rand_check(images, idx, boxes, flip, lut, out_hw, aff, pops, ppar,
+                                       partner, lam_q, cut, fill, ra_fill)
+    N, Hs, Ws, C = images.shape
+    out = torch.empty(B, Ho, Wo, C, device=images.device, dtype=lut.dtype)
+    mix = [0, 0, 0] if partner is None else \
+        [t.contiguous().data_ptr() for t in (partner, lam_q, cut)]
+    _K.augment_rand_images(images.data_ptr(), idx.contiguous().data_ptr(),
+                           boxes.contiguous().data_ptr(), flip.contiguous().data_ptr(),
+                           lut.contiguous().data_ptr(), aff.data_ptr(), pops.data_ptr(),
+                           ppar.data_ptr(), L, *mix, out.data_ptr(), N, B, Hs, Ws, C, Ho, Wo,
+                           int(fill), int(ra_fill), int(lut.dtype == _BF16), int(max_blocks),
+                           _st())
+    return out
+
+
 def mlm_mask_tokens(tokens, idx, seed, max_predictions, masking, example_stride=1,
                     example_offset=0, max_blocks=0, continuation=None):
     """Masked-LM example creation of one batch in ONE launch (csrc/kernels/mlm_mask.hip; the

@@ -493,6 +493,132 @@ def augment_mix_images(images, idx, boxes, flip, lut, out_hw, partner, lam_q, cu
     return lut[torch.arange(images.shape[3], device=dev).view(1, 1, 1, -1), v.long()]
 
 
+RAND_MAX_SIDE = 1024          # the kernel's axis tables hold every output row and column
+RAND_MAX_LAYERS = 4
+RAND_IDENTITY = (65536, 0, 0, 0, 65536, 0)
+# pointwise op codes of augment_rand_images and the inclusive range of each one's parameter
+RAND_NONE, RAND_INVERT, RAND_SOLARIZE, RAND_SOLARIZE_ADD, RAND_POSTERIZE, RAND_BRIGHTNESS, \
+    RAND_COLOR = range(7)
+RAND_PARAM_RANGE = {RAND_SOLARIZE: (0, 256), RAND_SOLARIZE_ADD: (0, 128), RAND_POSTERIZE: (0, 255),
+                    RAND_BRIGHTNESS: (0, 1 << 18), RAND_COLOR: (0, 1 << 18)}
+
+
+def _augment_rand_check(images, idx, boxes, flip, lut, out_hw, aff, pops, ppar, partner, lam_q,
+                        cut, fill, ra_fill):
+    """Shared argument validation of ``augment_rand_images`` (both backends) -> (B, Ho, Wo, L)."""
+    mix = (partner, lam_q, cut)
+    if any(t is None for t in mix) and not all(t is None for t in mix):
+        raise ValueError("augment_rand_images: partner, lam_q and cut are all given or all None")
+    B, Ho, Wo = _augment_check(images, idx, boxes, flip, lut, out_hw, fill,
+                               None if partner is None else mix)
+    if Ho > RAND_MAX_SIDE or Wo > RAND_MAX_SIDE:
+        raise ValueError(f"augment_rand_images: output sides are at most {RAND_MAX_SIDE}")
+    if aff.dtype != torch.int32 or tuple(aff.shape) != (B, 6):
+        raise ValueError("augment_rand_images: aff must be int32 [B, 6] = (a, b, c, d, e, f)")
+    if pops.dtype != torch.int32 or pops.dim() != 2 or pops.shape[0] != B:
+        raise ValueError("augment_rand_images: pops must be int32 [B, L]")
+    L = pops.shape[1]
+    if not 1 <= L <= RAND_MAX_LAYERS:
+        raise ValueError(f"augment_rand_images: {L} layers outside [1, {RAND_MAX_LAYERS}]")
+    if ppar.dtype != torch.int32 or tuple(ppar.shape) != (B, L):
+        raise ValueError("augment_rand_images: ppar must be int32 [B, L]")
+    for t in (aff, pops, ppar):
+        if t.device != images.device:
+            raise ValueError("augment_rand_images: every argument lives on the images' device")
+        if not t.is_contiguous():
+            raise ValueError("augment_rand_images: aff, pops and ppar must be contiguous")
+    if not 0 <= int(ra_fill) <= 255:
+        raise ValueError("augment_rand_images: ra_fill must be one byte")
+    return B, Ho, Wo, L
+
+
+def _augment_rand_v(images, idx, boxes, flip, out_hw, aff, pops, ppar, fill, ra_fill):
+    """Steps 1 and 2 of the rule of ``augment_rand_images`` (the map and the pointwise chain) ->
+    int32 [B, Ho, Wo, C] (checked arguments)."""
+    B, (Ho, Wo) = idx.numel(), (int(v) for v in out_hw)
+    C, dev = images.shape[3], images.device
+    virt = _augment_v(images, idx, boxes, flip, out_hw, fill)
+    a, b, c, d, e, f = (aff[:, i].long().view(B, 1, 1) for i in range(6))
+    X = 2 * torch.arange(Wo, device=dev).view(1, 1, Wo) + 1
+    Y = 2 * torch.arange(Ho, device=dev).view(1, Ho, 1) + 1
+    u = (a * X + b * Y + 2 * c) >> 17
+    v = (d * X + e * Y + 2 * f) >> 17
+    inside = (u >= 0) & (u < Wo) & (v >= 0) & (v < Ho)
+    rows = torch.arange(B, device=dev).view(B, 1, 1)
+    x = virt[rows, v.clamp(0, Ho - 1), u.clamp(0, Wo - 1)]               # [B, Ho, Wo, C]
+    x = torch.where(inside.unsqueeze(3), x, x.new_tensor(int(ra_fill)))
+    for k in range(pops.shape[1]):
+        code = pops[:, k].view(B, 1, 1, 1)
+        m = ppar[:, k].view(B, 1, 1, 1)
+        y = torch.where(code == RAND_INVERT, 255 - x, x)
+        y = torch.where(code == RAND_SOLARIZE, torch.where(x < m, x, 255 - x), y)
+        y = torch.where(code == RAND_SOLARIZE_ADD,
+                        torch.where(x < 128, (x + m).clamp(max=255), x), y)
+        y = torch.where(code == RAND_POSTERIZE, x & m, y)
+        y = torch.where(code == RAND_BRIGHTNESS, ((x * m) >> 16).clamp(0, 255), y)
+        if C == 3:
+            g = (19595 * x[..., 0:1] + 38470 * x[..., 1:2] + 7471 * x[..., 2:3] + 32768) >> 16
+            y = torch.where(code == RAND_COLOR, ((65536 * g + m * (x - g)) >> 16).clamp(0, 255), y)
+        x = y
+    return x
+
+
+def augment_rand_images(images, idx, boxes, flip, lut, out_hw, aff, pops, ppar, partner=None,
+                        lam_q=None, cut=None, fill=0, ra_fill=128):
+    """``augment_images`` / ``augment_mix_images`` with RandAugment: per row an output -> input
+    affine map and a chain of pointwise ops, in integer arithmetic: the oracle of the
+    ``augment_rand_images`` kernel and the CPU path; both produce the same bits.
+
+    ``aff`` int32 [B, 6] = (a, b, c, d, e, f) in Q16; ``pops`` / ``ppar`` int32 [B, L], the op
+    codes and their parameters, 1 <= L <= 4.  Let V_b(v, u) be the ``v`` of ``augment_images``
+    for row b at output pixel (oy = v, ox = u) (the row's virtual image).  For output pixel
+    (b, oy, ox):
+
+        U = a (2 ox + 1) + b (2 oy + 1) + 2 c,  W = d (2 ox + 1) + e (2 oy + 1) + 2 f    (int64)
+        u = U >> 17, v = W >> 17          (floor: PIL's nearest-neighbour affine transform on
+                                           pixel centres; (65536, 0, 0, 0, 65536, 0) is u = ox,
+                                           v = oy)
+        x_c = V_b(v, u)[c] if 0 <= u < Wo and 0 <= v < Ho else ra_fill
+        for k = 0 .. L - 1, with m = ppar[b, k] and code pops[b, k]:
+            0 none         x
+            1 Invert       255 - x
+            2 Solarize     x if x < m else 255 - x                      m in [0, 256]
+            3 SolarizeAdd  min(255, x + m) if x < 128 else x            m in [0, 128]
+            4 Posterize    x & m                                        m a byte mask
+            5 Brightness   clamp((x m) >> 16, 0, 255)                   m = factor in Q16 <= 2^18
+            6 Color        C = 3: g = (19595 x_0 + 38470 x_1 + 7471 x_2 + 32768) >> 16 (PIL's L),
+                           x_c = clamp((65536 g + m (x_c - g)) >> 16, 0, 255); C = 1: x
+        with a partner: the mix of ``augment_mix_images`` of this value for row b and for row
+        p = partner[b] (p's own index, box, flip, aff, pops and ppar) at the same output pixel
+        out = lut[c][value]
+
+    The identity map with all-zero ``pops`` is ``augment_images`` (with a partner
+    ``augment_mix_images``) to the bit.  A code outside 0..6 or a parameter outside its range
+    raises here (the kernel treats an unknown code as none and clamps the parameters)."""
+    B, Ho, Wo, L = _augment_rand_check(images, idx, boxes, flip, lut, out_hw, aff, pops, ppar,
+                                       partner, lam_q, cut, fill, ra_fill)
+    dev = images.device
+    if B and (int(pops.min()) < 0 or int(pops.max()) > RAND_COLOR):
+        raise ValueError("augment_rand_images: op code outside 0..6")
+    for code, (lo, hi) in RAND_PARAM_RANGE.items():
+        m = ppar[pops == code]
+        if m.numel() and (int(m.min()) < lo or int(m.max()) > hi):
+            raise ValueError(f"augment_rand_images: parameter of op {code} outside [{lo}, {hi}]")
+    if partner is not None and B and (int(partner.min()) < 0 or int(partner.max()) >= B):
+        raise ValueError("augment_rand_images: partner outside the batch")
+    v = _augment_rand_v(images, idx, boxes, flip, out_hw, aff, pops, ppar, fill, ra_fill)
+    if partner is not None:
+        va, vb = v, v[partner.long()]             # row p at the same output pixel
+        q = lam_q.clamp(0, 65536).view(B, 1, 1, 1)
+        c = cut.long()
+        oy = torch.arange(Ho, device=dev).view(1, Ho, 1)
+        ox = torch.arange(Wo, device=dev).view(1, 1, Wo)
+        y0, x0, h, w = (c[:, i].view(B, 1, 1) for i in range(4))
+        inside = (oy >= y0) & (oy < y0 + h) & (ox >= x0) & (ox < x0 + w) & (h > 0) & (w > 0)
+        v = torch.where(inside.unsqueeze(3), vb, (q * va + (65536 - q) * vb + 32768) >> 16)
+    return lut[torch.arange(images.shape[3], device=dev).view(1, 1, 1, -1), v.long()]
+
+
 MLM_MAX_SEQ = 512
 
 
