@@ -412,12 +412,14 @@ void dtf_attn_set_wide(int v);
 void dtf_attn_set_keep(int v);
 long dtf_attn_keep_words(int B, int S, int H, float p);
 void dtf_attn_fwd(const bf16_t* qkv, const float* mask, bf16_t* out, float* lse, int B, int S,
-                  int H, float scale, float p, uint32_t seed, hipStream_t st, uint32_t* keep);
+                  int H, float scale, float p, uint32_t seed, hipStream_t st, uint32_t* keep,
+                  int causal);
 void dtf_attn_set_fused(int v);
 int dtf_attn_bwd_fused(int S);
 void dtf_attn_bwd(const bf16_t* qkv, const float* mask, const bf16_t* out, const bf16_t* dout,
                   const float* lse, float* delta, bf16_t* dqkv, int B, int S, int H, float scale,
-                  float p, uint32_t seed, hipStream_t st, float* colpart, const uint32_t* keep);
+                  float p, uint32_t seed, hipStream_t st, float* colpart, const uint32_t* keep,
+                  int causal);
 int dtf_pos_type_grad_ws_floats(int S, int H, int NT);
 void dtf_pos_type_grad(const bf16_t* ds, const int64_t* tt, int B, int S, int H, int NT,
                        float* dpos, float* dtyp, float* ws, hipStream_t st);

@@ -766,6 +766,24 @@ DTF_DEV void store4_scaled(bf16_t* p, const f32x4_t& v, float s) {
   store4(p, f);
 }
 
+// first row (query or key) of wave w's 16 within its block, as a scalar: the causal kernels
+// branch on it, and the branch must be wave-uniform
+template <int NW>
+DTF_DEV int attn_wave_row0(int bx, int w) {
+  return bx * 16 * NW + __builtin_amdgcn_readfirstlane(w) * 16;
+}
+// The row block a causal block takes: blockIdx.x rotated by head and batch.  A causal block's
+// work grows with its row block, and consecutive workgroups go round-robin over the 8 XCDs: with
+// 2, 4 or 8 row blocks per (b, h) the linear workgroup id modulo 8 fixes the row block, so an
+// unrotated grid hands every heaviest block to the same XCDs, which then take as long as the
+// non-causal kernel while the others idle.  Rotated, each XCD gets every row block equally often
+// (profiles/CAUSAL.md).  Per (b, h) the map is a bijection of the row blocks and block-uniform:
+// it changes which block computes which rows, nothing in the arithmetic.
+template <bool CAUSAL>
+DTF_DEV int attn_row_block() {
+  return CAUSAL ? (int)((blockIdx.x + blockIdx.y + blockIdx.z) % gridDim.x) : (int)blockIdx.x;
+}
+
 // cooperative CH-row x 64-col loads of two operands (NT threads, 16 B per chunk)
 template <int NT, int CH>
 DTF_DEV void load_two_tiles(bf16_t* d0, const bf16_t* s0, long ld0, bf16_t* d1, const bf16_t* s1,
@@ -784,7 +802,19 @@ DTF_DEV void load_two_tiles(bf16_t* d0, const bf16_t* s0, long ld0, bf16_t* d1, 
 // Launch shapes: NW waves x 16 rows per block, K/V (or Q/dO) staged CH rows at a time.  <8, 128>
 // (S % 128 == 0, e.g. BERT's 128) covers a whole 128-token sequence per block, so each (b, h)
 // reads its K/V once instead of once per 64-query block and syncs once per 128 keys.
-template <bool DROP, int NW, int CH>
+//
+// CAUSAL: query q sees key k iff k <= q (the additive key mask still applies on top).  Tiles
+// above the diagonal are skipped, not merely masked: the key-chunk loop ends at the block's last
+// query (block-uniform), and inside a chunk a wave skips every 64-key sub-tile that starts above
+// its 16 queries (wave-uniform; there is no barrier inside the sub loop).  Inside the diagonal
+// sub-tile a hidden score is selected to -inf.  The running maximum still stays finite: a wave's
+// 16 queries lie inside one 64-aligned range, so every sub-tile it processes starts at or below
+// all of them, and the first one it processes holds key 0, which every query sees -- mloc is
+// finite from the first sub-tile on and exp2f(-inf - mnew) is an exact 0.  (Through the public
+// mask an -inf row has no such guarantee, which is why that mask must stay finite.)  The key order
+// and every accumulation order are those of the non-causal kernel, so a query that sees every key
+// (q = S - 1) gets the same bits from both.  The dropout index stays (bh S + q) S + k.
+template <bool DROP, int NW, int CH, bool CAUSAL>
 __global__ void __launch_bounds__(64 * NW)
 attn_fwd_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ mask,
                 bf16_t* __restrict__ out, float* __restrict__ lse, const AttnGeom g) {
@@ -794,7 +824,8 @@ attn_fwd_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ mask,
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, gq = lane >> 4, li = lane & 15;
   const int h = blockIdx.y, b = blockIdx.z, S = g.S, H = g.H;
   const long tok0 = (long)b * S;
-  const int q = blockIdx.x * 16 * NW + w * 16 + li;
+  const int bx = attn_row_block<CAUSAL>();
+  const int q = bx * 16 * NW + w * 16 + li;
   const bf16_t* qrow = qkv + (tok0 + q) * g.ld + h * AD;
   const bf16x8_t bq0 = *(const bf16x8_t*)(qrow + 8 * gq);
   const bf16x8_t bq1 = *(const bf16x8_t*)(qrow + 32 + 8 * gq);
@@ -805,8 +836,10 @@ attn_fwd_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ mask,
   f32x4_t acc[4];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) acc[dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  const int kend = CAUSAL ? (bx + 1) * 16 * NW : S;      // past the block's last query
+  const int qw = attn_wave_row0<NW>(bx, w);              // the wave's first query
 
-  for (int kc = 0; kc < S; kc += CH) {
+  for (int kc = 0; kc < kend; kc += CH) {
     __syncthreads();
     load_two_tiles<64 * NW, CH>(Ks, qkv + (tok0 + kc) * g.ld + (H + h) * AD, g.ld,
                                 Vs, qkv + (tok0 + kc) * g.ld + (2 * H + h) * AD, g.ld, tid);
@@ -814,6 +847,7 @@ attn_fwd_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ mask,
     __syncthreads();
 #pragma unroll
     for (int sub = 0; sub < CH; sub += 64) {
+      if (CAUSAL && kc + sub > qw) continue;
       const bf16_t* Kb = Ks + sub * ALD;
       const bf16_t* Vb = Vs + sub * ALD;
       f32x4_t s[4];
@@ -830,6 +864,7 @@ attn_fwd_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ mask,
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           s[t][r] = s[t][r] * c + Ms[sub + 16 * t + 4 * gq + r];
+          if (CAUSAL && kc + sub + 16 * t + 4 * gq + r > q) s[t][r] = -INFINITY;
           mloc = fmaxf(mloc, s[t][r]);
         }
       mloc = fmaxf(mloc, __shfl_xor(mloc, 16, 64));
@@ -848,7 +883,7 @@ attn_fwd_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ mask,
           if (DROP) {
             const bool kp = keep_elem(g.seed, kbase + kc + sub + 16 * t + 4 * gq + r, g.thr);
             s[t][r] = kp ? p * g.inv_keep : 0.f;
-            if constexpr (CH == 128) kbits |= (uint32_t)kp << ((sub >> 6) * 16 + 4 * t + r);
+            if constexpr (CH == 128 && !CAUSAL) kbits |= (uint32_t)kp << ((sub >> 6) * 16 + 4 * t + r);
           } else {
             s[t][r] = p;
           }
@@ -871,11 +906,14 @@ attn_fwd_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ mask,
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) store4_scaled(orow + 16 * dt + 4 * gq, acc[dt], inv);
   if (gq == 0) lse[((long)b * H + h) * S + q] = m + log2f(l);
-  if constexpr (DROP && CH == 128)
+  if constexpr (DROP && CH == 128 && !CAUSAL)
     if (g.keep) g.keep[(((long)b * H + h) * S + q) * 4 + gq] = kbits;
 }
 
-template <bool DROP, int NW, int CH>
+// CAUSAL: a key sees no query below it, so the query-chunk loop starts at the chunk that holds
+// the block's first key and a wave skips every 64-query sub-tile that ends below its 16 keys; in
+// the diagonal sub-tile a hidden pair's p is exactly 0.
+template <bool DROP, int NW, int CH, bool CAUSAL>
 __global__ void __launch_bounds__(64 * NW)
 attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ mask,
                     const bf16_t* __restrict__ dO, const float* __restrict__ lse,
@@ -886,7 +924,8 @@ attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ ma
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, gq = lane >> 4, li = lane & 15;
   const int h = blockIdx.y, b = blockIdx.z, S = g.S, H = g.H;
   const long tok0 = (long)b * S;
-  const int k = blockIdx.x * 16 * NW + w * 16 + li;       // this lane's key
+  const int bx = attn_row_block<CAUSAL>();
+  const int k = bx * 16 * NW + w * 16 + li;               // this lane's key
   const bf16_t* krow = qkv + (tok0 + k) * g.ld + (H + h) * AD;
   const bf16_t* vrow = qkv + (tok0 + k) * g.ld + (2 * H + h) * AD;
   const bf16x8_t bk0 = *(const bf16x8_t*)(krow + 8 * gq), bk1 = *(const bf16x8_t*)(krow + 32 + 8 * gq);
@@ -898,7 +937,10 @@ attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ ma
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) dv[dt] = dk[dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
-  for (int qc = 0; qc < S; qc += CH) {
+  const int qbeg = CAUSAL ? bx * 16 * NW / CH * CH : 0;
+  const int kw = attn_wave_row0<NW>(bx, w) & ~63;           // 64-aligned range of the wave's keys
+
+  for (int qc = qbeg; qc < S; qc += CH) {
     __syncthreads();
     load_two_tiles<64 * NW, CH>(Qs, qkv + (tok0 + qc) * g.ld + h * AD, g.ld,
                                 Os, dO + (tok0 + qc) * (long)(H * AD) + h * AD, H * AD, tid);
@@ -909,6 +951,7 @@ attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ ma
     __syncthreads();
 #pragma unroll
     for (int sub = 0; sub < CH; sub += 64) {
+      if (CAUSAL && qc + sub < kw) continue;
       const bf16_t* Qb = Qs + sub * ALD;
       const bf16_t* Ob = Os + sub * ALD;
       f32x4_t P[4], dS[4];
@@ -923,7 +966,9 @@ attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ ma
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int qq = sub + 16 * qt + 4 * gq + r;
-          const float p = exp2f(s[r] * c + mk - Ls[qq]);
+          float e = s[r] * c + mk - Ls[qq];
+          if (CAUSAL && qc + qq < k) e = -INFINITY;
+          const float p = exp2f(e);
           if (DROP) {
             const bool kp = keep_elem(g.seed, (uint32_t)((bh * S + qc + qq) * S + k), g.thr);
             P[qt][r] = kp ? p * g.inv_keep : 0.f;
@@ -957,7 +1002,9 @@ attn_bwd_dkv_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ ma
   }
 }
 
-template <bool DROP, int NW, int CH>
+// CAUSAL: the key-chunk loop and the sub-tile skip of the causal forward; a hidden key's p is
+// exactly 0.
+template <bool DROP, int NW, int CH, bool CAUSAL>
 __global__ void __launch_bounds__(64 * NW)
 attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ mask,
                    const bf16_t* __restrict__ dO, const float* __restrict__ lse,
@@ -969,7 +1016,8 @@ attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ mas
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, gq = lane >> 4, li = lane & 15;
   const int h = blockIdx.y, b = blockIdx.z, S = g.S, H = g.H;
   const long tok0 = (long)b * S;
-  const int q = blockIdx.x * 16 * NW + w * 16 + li;
+  const int bx = attn_row_block<CAUSAL>();
+  const int q = bx * 16 * NW + w * 16 + li;
   const bf16_t* qrow = qkv + (tok0 + q) * g.ld + h * AD;
   const bf16_t* orow = dO + (tok0 + q) * (long)(H * AD) + h * AD;
   const bf16x8_t bq0 = *(const bf16x8_t*)(qrow + 8 * gq), bq1 = *(const bf16x8_t*)(qrow + 32 + 8 * gq);
@@ -1001,8 +1049,10 @@ attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ mas
   f32x4_t dq[4];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt) dq[dt] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  const int kend = CAUSAL ? (bx + 1) * 16 * NW : S;
+  const int qw = attn_wave_row0<NW>(bx, w);
 
-  for (int kc = 0; kc < S; kc += CH) {
+  for (int kc = 0; kc < kend; kc += CH) {
     __syncthreads();
     load_two_tiles<64 * NW, CH>(Ks, qkv + (tok0 + kc) * g.ld + (H + h) * AD, g.ld,
                                 Vs, qkv + (tok0 + kc) * g.ld + (2 * H + h) * AD, g.ld, tid);
@@ -1010,6 +1060,7 @@ attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ mas
     __syncthreads();
 #pragma unroll
     for (int sub = 0; sub < CH; sub += 64) {
+      if (CAUSAL && kc + sub > qw) continue;
       const bf16_t* Kb = Ks + sub * ALD;
       const bf16_t* Vb = Vs + sub * ALD;
       f32x4_t dS[4];
@@ -1024,7 +1075,12 @@ attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ mas
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = sub + 16 * t + 4 * gq + r;
-          const float p = exp2f(s[r] * c + Ms[key] - lq);
+          // (the select sits on the exponent, after the LDS read: p is an exact 0 and dS a
+          // signed 0.  Selecting dS itself cost 50-100 VGPRs in this kernel, and a select with
+          // the LDS read in one arm became a branch per element.)
+          float e = s[r] * c + Ms[key] - lq;
+          if (CAUSAL && kc + key > q) e = -INFINITY;
+          const float p = exp2f(e);
           float dpu = dp[r];
           if (DROP) dpu = keep_elem(g.seed, kbase + kc + key, g.thr) ? dpu * g.inv_keep : 0.f;
           dS[t][r] = p * (dpu - dl);
@@ -1549,21 +1605,21 @@ void dtf_attn_set_wide(int v) { g_attn_wide = v; }
 
 // (the 8-wave forward takes 120 VGPRs: two blocks per CU; forcing 6 or 8 waves per SIMD spills
 // and is 13-39 % slower with dropout, profiles/measurements/r4_attention_fwd_occupancy.jsonl)
-template <int NW, int CH>
+template <int NW, int CH, bool CAUSAL>
 static void attn_fwd_launch(const bf16_t* qkv, const float* mask, bf16_t* out, float* lse,
                             const AttnGeom& g, hipStream_t st) {
   const dim3 grid(g.S / (16 * NW), g.H, g.B);
   if (g.thr)
-    hipLaunchKernelGGL((attn_fwd_kernel<true, NW, CH>), grid, dim3(64 * NW), 0, st, qkv, mask,
-                       out, lse, g);
+    hipLaunchKernelGGL((attn_fwd_kernel<true, NW, CH, CAUSAL>), grid, dim3(64 * NW), 0, st, qkv,
+                       mask, out, lse, g);
   else
-    hipLaunchKernelGGL((attn_fwd_kernel<false, NW, CH>), grid, dim3(64 * NW), 0, st, qkv, mask,
-                       out, lse, g);
+    hipLaunchKernelGGL((attn_fwd_kernel<false, NW, CH, CAUSAL>), grid, dim3(64 * NW), 0, st, qkv,
+                       mask, out, lse, g);
 }
 
 // dK/dV always runs the 4-wave shape: its 8-wave build needs 167 VGPRs with dropout (one block
 // per CU) and measured 8 % slower on BERT-base; dQ gains 10 % from the 8-wave shape.
-template <int NW, int CH>
+template <int NW, int CH, bool CAUSAL>
 static void attn_bwd_launch(const bf16_t* qkv, const float* mask, const bf16_t* out,
                             const bf16_t* dout, const float* lse, float* delta, bf16_t* dqkv,
                             const AttnGeom& g, hipStream_t st) {
@@ -1571,15 +1627,15 @@ static void attn_bwd_launch(const bf16_t* qkv, const float* mask, const bf16_t* 
   // the dK/dV kernel then reads
   const dim3 grid(g.S / (16 * NW), g.H, g.B), grid4(g.S / 64, g.H, g.B);
   if (g.thr) {
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<true, NW, CH>), grid, dim3(64 * NW), 0, st, qkv, mask,
-                       dout, lse, delta, dqkv, g, out);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, 4, 64>), grid4, dim3(256), 0, st, qkv, mask,
-                       dout, lse, delta, dqkv, g);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<true, NW, CH, CAUSAL>), grid, dim3(64 * NW), 0, st,
+                       qkv, mask, dout, lse, delta, dqkv, g, out);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<true, 4, 64, CAUSAL>), grid4, dim3(256), 0, st, qkv,
+                       mask, dout, lse, delta, dqkv, g);
   } else {
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<false, NW, CH>), grid, dim3(64 * NW), 0, st, qkv,
-                       mask, dout, lse, delta, dqkv, g, out);
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, 4, 64>), grid4, dim3(256), 0, st, qkv, mask,
-                       dout, lse, delta, dqkv, g);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<false, NW, CH, CAUSAL>), grid, dim3(64 * NW), 0, st,
+                       qkv, mask, dout, lse, delta, dqkv, g, out);
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<false, 4, 64, CAUSAL>), grid4, dim3(256), 0, st, qkv,
+                       mask, dout, lse, delta, dqkv, g);
   }
 }
 
@@ -1595,13 +1651,21 @@ long dtf_attn_keep_words(int B, int S, int H, float p) {
 }
 
 void dtf_attn_fwd(const bf16_t* qkv, const float* mask, bf16_t* out, float* lse, int B, int S,
-                  int H, float scale, float p, uint32_t seed, hipStream_t st, uint32_t* keep) {
+                  int H, float scale, float p, uint32_t seed, hipStream_t st, uint32_t* keep,
+                  int causal) {
   AttnGeom g = attn_geom(B, S, H, scale, p, seed);
+  if (causal) {
+    // the keep bits feed the fused S == 128 backward only, which has no causal form
+    if (keep) throw std::runtime_error("attn_fwd: causal attention takes no keep buffer");
+    if (g_attn_wide && S % 128 == 0) attn_fwd_launch<8, 128, true>(qkv, mask, out, lse, g, st);
+    else attn_fwd_launch<4, 64, true>(qkv, mask, out, lse, g, st);
+    return;
+  }
   if (keep && !dtf_attn_keep_words(B, S, H, p))
     throw std::runtime_error("attn_fwd: keep buffer given for a shape that does not use it");
   g.keep = keep;
-  if (g_attn_wide && S % 128 == 0) attn_fwd_launch<8, 128>(qkv, mask, out, lse, g, st);
-  else attn_fwd_launch<4, 64>(qkv, mask, out, lse, g, st);
+  if (g_attn_wide && S % 128 == 0) attn_fwd_launch<8, 128, false>(qkv, mask, out, lse, g, st);
+  else attn_fwd_launch<4, 64, false>(qkv, mask, out, lse, g, st);
 }
 
 // 1 (default): S == 128 runs the fused one-block-per-(b, h) backward
@@ -1614,8 +1678,18 @@ int dtf_attn_bwd_fused(int S) { return g_attn_fused && S == kFusedS; }
 void dtf_attn_bwd(const bf16_t* qkv, const float* mask, const bf16_t* out, const bf16_t* dout,
                   const float* lse, float* delta, bf16_t* dqkv, int B, int S, int H, float scale,
                   float p, uint32_t seed, hipStream_t st, float* colpart,
-                  const uint32_t* keep) {
+                  const uint32_t* keep, int causal) {
   AttnGeom g = attn_geom(B, S, H, scale, p, seed);
+  if (causal) {
+    // always the split kernels, at S == 128 too: the fused backward has no causal form
+    if (colpart || keep)
+      throw std::runtime_error("attn_bwd: causal attention takes no column partials or keep buffer");
+    if (g_attn_wide && S % 128 == 0)
+      attn_bwd_launch<8, 128, true>(qkv, mask, out, dout, lse, delta, dqkv, g, st);
+    else
+      attn_bwd_launch<4, 64, true>(qkv, mask, out, dout, lse, delta, dqkv, g, st);
+    return;
+  }
   if (colpart && !(g_attn_fused && S == kFusedS))
     throw std::runtime_error("attn_bwd: column partials need the fused S == 128 backward");
   if (keep && !dtf_attn_keep_words(B, S, H, p))
@@ -1640,9 +1714,9 @@ void dtf_attn_bwd(const bf16_t* qkv, const float* mask, const bf16_t* out, const
     return;
   }
   if (g_attn_wide && S % 128 == 0)
-    attn_bwd_launch<8, 128>(qkv, mask, out, dout, lse, delta, dqkv, g, st);
+    attn_bwd_launch<8, 128, false>(qkv, mask, out, dout, lse, delta, dqkv, g, st);
   else
-    attn_bwd_launch<4, 64>(qkv, mask, out, dout, lse, delta, dqkv, g, st);
+    attn_bwd_launch<4, 64, false>(qkv, mask, out, dout, lse, delta, dqkv, g, st);
 }
 
 namespace {

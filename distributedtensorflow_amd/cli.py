@@ -21,6 +21,8 @@ Keeps the reference's flags and adds strategy selection:
     python train.py --model resnet50 --num_gpus 8 --eval --eval_steps 20 --eval_every 500
     # moving averages of the variables, evaluated next to the raw weights
     python train.py --model resnet50 --num_gpus 8 --ema_decay 0.9999 --eval
+    # a left-to-right language model on a token set: causal attention, next-token targets
+    python train.py --model bert_base --num_gpus 8 --text_data DIR --causal_lm --eval
 
 The chief prints the reference's ``Worker (i): loss = x.xx (global step: n)`` line every
 ``--log_every`` steps and writes ``Global Step`` / ``Loss`` TensorBoard scalars under
@@ -140,11 +142,23 @@ def build_parser():
                    help="with --text_data: whole-word masking (the pieces of a word are predicted "
                         "together), for training and evaluation; reads DIR/continuation.npy, "
                         "uint8 [vocab_size] with 1 at the ## pieces")
+    p.add_argument("--causal_lm", action="store_true",
+                   help="train a BERT model as a left-to-right language model: causal attention "
+                        "in every layer, every position predicts the next token (pad excluded); "
+                        "rows come from --text_data unmasked, or from the synthetic set; "
+                        "--mlm_prob and --max_predictions are ignored; --eval / --eval_every "
+                        "also report eval_perplexity, exp of the reported (4-place) eval_loss")
     return p
 
 
 def check_data_args(args):
     """The data flags that cannot go together: a SystemExit names the offender."""
+    if args.causal_lm:
+        if not args.model.startswith("bert"):
+            raise SystemExit(f"--causal_lm needs a BERT model, not {args.model}")
+        if args.whole_word_mask:
+            raise SystemExit("--causal_lm masks nothing: it cannot be combined with "
+                             "--whole_word_mask")
     if args.text_data:
         if args.image_data:
             raise SystemExit("--text_data and --image_data cannot be combined")
@@ -355,6 +369,8 @@ def run(args):
     else:
         from .data import SyntheticMLM
         data = SyntheticMLM(batch, args.seq_len, device=device, seed=1234 + rid)
+        if args.causal_lm:
+            _causal_batches(data)
 
     with strategy.scope():
         if num_classes is not None and args.model != "mnist_mlp":
@@ -369,10 +385,11 @@ def run(args):
             model = getattr(dtf.models, args.model)()
         elif args.text_data:
             from .models import bert
-            model = getattr(bert, args.model)(vocab_size=data.masking.vocab_size)
+            model = getattr(bert, args.model)(vocab_size=data.masking.vocab_size,
+                                              causal=args.causal_lm)
         else:
             from .models import bert
-            model = getattr(bert, args.model)()
+            model = getattr(bert, args.model)(causal=args.causal_lm)
         model.train()
         global_step = get_or_create_global_step()
         ema = None
@@ -476,6 +493,8 @@ def run(args):
             result[k] = getattr(args, k)
     if args.whole_word_mask:
         result["whole_word_mask"] = True
+    if args.causal_lm:
+        result["causal_lm"] = True
     steps_done = global_step.value() - (first_step or 0)
     if steps_done > 0 and server is None:
         result["examples_per_sec"] = round(steps_done * batch * nrep * accum / elapsed, 1)
@@ -491,7 +510,12 @@ def run(args):
         for k in ("ema_loss", "ema_top_1", "ema_top_k"):
             if k in ev:
                 result["eval_" + k] = round(ev[k], 4)
-        if args.image_data or args.text_data:
+        if args.causal_lm:
+            # The perplexity is exp of the eval_loss printed next to it, i.e. of the loss rounded
+            # to 4 places, so that the two reported figures agree exactly.  eval_top_1 is the
+            # next-token accuracy and eval_count the number of predicted (non-pad) next tokens.
+            result["eval_perplexity"] = math.exp(result["eval_loss"])
+        if args.image_data or args.text_data or args.causal_lm:
             result["eval_count"] = int(ev["count"])
         elif args.model.startswith("mnist"):
             result["test_accuracy"] = round(ev["top_1"], 4)
@@ -538,10 +562,23 @@ def _image_dataset(args, split, num_classes, batch, device, dtype, shards, shard
                               rand_seed=args.seed + 3000017 * (stream + 1))
 
 
+def _causal_batches(data):
+    """--causal_lm without --text_data: the SyntheticMLM pool's ``input_ids`` / ``input_mask``
+    as next-token batches (``causal_lm_targets``), in place."""
+    from .data import causal_lm_targets
+    for i, b in enumerate(data.batches):
+        labels, weights = causal_lm_targets(b["input_ids"], b["input_mask"])
+        data.batches[i] = {"input_ids": b["input_ids"], "segment_ids": b["segment_ids"],
+                           "input_mask": b["input_mask"], "masked_lm_positions": None,
+                           "masked_lm_ids": labels, "masked_lm_weights": weights}
+    return data
+
+
 def _token_dataset(args, split, batch, device, shards, shard_index):
     """--text_data: the HBM-resident ``split`` of DIR as a DeviceTokenDataset under --mlm_prob /
     --max_predictions (and DIR/meta.json, where present), with DIR/continuation.npy under
-    --whole_word_mask; the batch shrinks to the shard where that is smaller."""
+    --whole_word_mask; the batch shrinks to the shard where that is smaller.  Under --causal_lm
+    the rows come out unmasked with next-token targets."""
     from .data import DeviceTokenDataset, TokenMasking, load_continuation, load_token_arrays
     tokens, masking = load_token_arrays(args.text_data, split, TokenMasking(prob=args.mlm_prob))
     continuation = None
@@ -551,7 +588,11 @@ def _token_dataset(args, split, batch, device, shards, shard_index):
         except (FileNotFoundError, ValueError) as e:
             raise SystemExit(f"--whole_word_mask: {e}")
     S = tokens.shape[1]
-    if S > 512 or args.max_predictions > S:
+    if args.causal_lm:
+        if S > 512:
+            raise SystemExit(f"{args.text_data}: rows of {S} tokens; the sequence length is at "
+                             "most 512")
+    elif S > 512 or args.max_predictions > S:
         raise SystemExit(f"{args.text_data}: rows of {S} tokens; the sequence length is at most "
                          f"512 and at least --max_predictions ({args.max_predictions})")
     if device.type == "cuda" and S % 64:
@@ -564,7 +605,8 @@ def _token_dataset(args, split, batch, device, shards, shard_index):
                               shuffle=split == "train", seed=args.seed + stream,
                               mask_seed=args.seed + 1000003 * (stream + 1),
                               eval_seed=args.seed & 0xFFFFFFFF, num_shards=shards,
-                              shard_index=shard_index, continuation=continuation)
+                              shard_index=shard_index, continuation=continuation,
+                              objective="causal" if args.causal_lm else "mlm")
 
 
 def _make_eval_fn(args, model, opt, strategy, device, dtype, batch, shards, shard_index,
@@ -605,6 +647,8 @@ def _make_eval_fn(args, model, opt, strategy, device, dtype, batch, shards, shar
             from .data import SyntheticMLM
             data = SyntheticMLM(batch, args.seq_len, device=device, seed=4321 + shard_index,
                                 pool=max(1, min(2, args.eval_steps)))
+            if args.causal_lm:
+                _causal_batches(data)
 
         def batches():
             return data.single_pass(args.eval_steps)

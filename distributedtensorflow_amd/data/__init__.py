@@ -7,11 +7,12 @@ from .device import DeviceArrayDataset
 from .images import (DeviceImageDataset, ImageAugment, ImageMix, ImageRandAugment, MixedLabels,
                      mix_plan, randaugment_plan)
 from .synthetic import SyntheticImageNet, SyntheticMLM
-from .tokens import (DeviceTokenDataset, TokenMasking, load_continuation, load_token_arrays,
-                     wordpiece_continuation)
+from .tokens import (DeviceTokenDataset, TokenMasking, causal_lm_targets, load_continuation,
+                     load_token_arrays, wordpiece_continuation)
 
 __all__ = ["images", "mnist", "tokens", "Dataset", "DeviceArrayDataset", "DeviceImageDataset",
            "DeviceTokenDataset", "ImageAugment", "ImageMix", "ImageRandAugment", "Iterator",
            "MixedLabels", "NativeBatchDataset", "SyntheticImageNet", "SyntheticMLM",
-           "TokenMasking", "load_continuation", "load_token_arrays", "mix_plan",
+           "TokenMasking", "causal_lm_targets", "load_continuation", "load_token_arrays",
+           "mix_plan",
            "randaugment_plan", "wordpiece_continuation"]

@@ -136,6 +136,21 @@ def load_continuation(data_dir, masking):
     return check_continuation(np.load(path), masking, path)
 
 
+def causal_lm_targets(input_ids, input_mask):
+    """Next-token targets of a left-to-right language model -> ``(labels, weights)``, int64 and
+    fp32 ``[B, S]``: ``labels[b, j] = input_ids[b, j + 1]`` and ``weights[b, j] =
+    float(input_mask[b, j + 1])`` for ``j < S - 1``; the last position has nothing to predict
+    (label 0, weight 0.0).  A pure function of its arguments."""
+    labels = torch.zeros_like(input_ids, dtype=torch.int64)
+    weights = torch.zeros(input_ids.shape, dtype=torch.float32, device=input_ids.device)
+    labels[:, :-1] = input_ids[:, 1:]
+    weights[:, :-1] = input_mask[:, 1:].to(torch.float32)
+    return labels, weights
+
+
+OBJECTIVES = ("mlm", "causal")
+
+
 class DeviceTokenDataset(DeviceArrayDataset):
     """A :class:`DeviceArrayDataset` of token rows whose batches are masked-LM examples made on
     the device by one kernel; a batch is the dict :class:`SyntheticMLM` yields plus
@@ -154,13 +169,29 @@ class DeviceTokenDataset(DeviceArrayDataset):
 
     ``continuation`` (uint8 or bool [vocab_size], 1 at the ``##`` pieces) turns on whole-word
     masking, for training batches and ``single_pass()`` alike: the table is checked here,
-    uploaded once and handed to every call of the kernel."""
+    uploaded once and handed to every call of the kernel.
+
+    ``objective="causal"`` yields left-to-right language-model batches instead: the gathered
+    rows (read unsigned) as int64 ``input_ids``, ``input_mask = ids != pad_id``, all-zero
+    ``segment_ids``, ``masked_lm_positions = None`` (the model's head then scores every position)
+    and ``masked_lm_ids`` / ``masked_lm_weights`` ``[B, S]`` from :func:`causal_lm_targets`.
+    Nothing is masked: no masking kernel runs, no seed is drawn (``mask_seed``, ``eval_seed``
+    and ``max_predictions`` are unused), ``continuation`` is refused, and ``single_pass()`` is
+    the same batches in order.  A batch is a handful of elementwise launches, not a fused
+    kernel."""
 
     def __init__(self, tokens, batch_size, device, masking=None, max_predictions=20,
                  shuffle=False, seed=0, mask_seed=0, eval_seed=0, num_shards=1, shard_index=0,
-                 drop_remainder=True, chunk_bytes=256 << 20, continuation=None):
+                 drop_remainder=True, chunk_bytes=256 << 20, continuation=None, objective="mlm"):
         device = torch.device(device)
         masking = masking or TokenMasking()
+        if objective not in OBJECTIVES:
+            raise ValueError(f"DeviceTokenDataset: objective {objective!r}, expected one of "
+                             f"{OBJECTIVES}")
+        if objective == "causal" and continuation is not None:
+            raise ValueError("DeviceTokenDataset: continuation (whole-word masking) has no "
+                             "meaning with objective='causal', which masks nothing")
+        self.objective = objective
         if tokens.dtype not in (np.uint16, np.int32) or tokens.ndim != 2:
             raise ValueError("DeviceTokenDataset: tokens must be uint16 or int32 [N, S]")
         if not 0 <= shard_index < num_shards:
@@ -191,6 +222,15 @@ class DeviceTokenDataset(DeviceArrayDataset):
         self._mask_gen.manual_seed(mask_seed)
         self.eval_seed = int(eval_seed)
         from ..ops.reference import _mlm_check, _mlm_continuation_check
+        if objective == "causal":
+            # nothing is masked: max_predictions plays no part, only the storage must hold the ids
+            if self.tokens.dim() != 2 or self.tokens.shape[1] < 1:
+                raise ValueError("DeviceTokenDataset: tokens must be [N, S] with S >= 1")
+            if self.tokens.element_size() == 2 and masking.vocab_size > 65536:
+                raise ValueError(f"DeviceTokenDataset: vocab_size {masking.vocab_size} does not "
+                                 "fit 16-bit token storage")
+            self.continuation = None
+            return
         rule = _mlm_check(self.tokens, torch.zeros(0, dtype=torch.int64, device=device), 0,
                           self.max_predictions, masking)[3]  # validates S, P and the ids now
         self.continuation = None
@@ -210,9 +250,20 @@ class DeviceTokenDataset(DeviceArrayDataset):
             idx = torch.arange(pos, min(pos + bs, self.n), device=self.device)
             yield self._gather(idx, seed=self.eval_seed)
 
+    def _gather_causal(self, idx):
+        store = self.tokens
+        ids = store.index_select(0, idx).long() & ((1 << (8 * store.element_size())) - 1)
+        real = (ids != self.masking.pad_id).long()
+        labels, weights = causal_lm_targets(ids, real)
+        return {"input_ids": ids, "segment_ids": torch.zeros_like(ids), "input_mask": real,
+                "masked_lm_positions": None, "masked_lm_ids": labels,
+                "masked_lm_weights": weights}
+
     def _gather(self, idx, seed=None):
         from .. import ops
-        if seed is None:                                   # a training batch: a fresh seed
+        if self.objective == "causal":
+            return self._gather_causal(idx)
+        if seed is None:                                  # a training batch: a fresh seed
             seed = int(torch.randint(0, 1 << 32, (1,), generator=self._mask_gen,
                                      dtype=torch.int64, device="cpu"))
         return ops.mlm_mask_tokens(self.tokens, idx.contiguous(), seed, self.max_predictions,

@@ -65,6 +65,10 @@ class BertConfig:
     type_vocab_size: int = 2
     initializer_range: float = 0.02
     layer_norm_eps: float = 1e-12
+    # left-to-right attention (query i sees key j iff j <= i) in every layer: the same post-LN
+    # blocks, variables, padded vocabulary and head as a causal language model (GPT-1's block).
+    # Called with masked_lm_positions=None, so the head scores every position.
+    causal: bool = False
 
     @staticmethod
     def base(**kw):
@@ -131,7 +135,8 @@ class BertLayer(nn.Module):
         cfg = self.cfg
         qkv = ops.dense(x, self.qkv_kernel, self.qkv_bias, impl=BERT_GEMM)
         ctx = ops.attention_qkv(qkv, mask, B, S, cfg.num_attention_heads,
-                                cfg.attention_probs_dropout_prob, self.training)
+                                cfg.attention_probs_dropout_prob, self.training,
+                                causal=cfg.causal)
         a = self.attn_out.gemm(ctx)
         # x feeds the QKV dense above and the residual here: its two gradients are summed by
         # that dense's dgrad GEMM (beta = 1), not by a separate add
@@ -250,5 +255,16 @@ def mlm_flops_per_token(cfg: BertConfig, seq_len: int, max_predictions: int) -> 
     return 3.0 * (gemm + attn + head)
 
 
+def causal_lm_flops_per_token(cfg: BertConfig, seq_len: int) -> float:
+    """Training FLOPs per input token of a causal model (fwd + bwd = 3x fwd): the head decodes
+    every position and half the attention products are counted (the visible triangle; the
+    kernels do (n + 1) / (2 n) of them at n = seq_len / 64 tiles, the diagonal tiles whole)."""
+    H, L, I = cfg.hidden_size, cfg.num_hidden_layers, cfg.intermediate_size
+    gemm = 2 * (3 * H * H + H * H + 2 * H * I) * L
+    attn = 2 * 2 * seq_len * H * L / 2
+    head = 2 * (H * H + H * cfg.vocab_size)
+    return 3.0 * (gemm + attn + head)
+
+
 __all__ = ["BertConfig", "BertForPreTraining", "BertLayer", "bert_base", "bert_large",
-           "mlm_flops_per_token"]
+           "causal_lm_flops_per_token", "mlm_flops_per_token"]

@@ -229,10 +229,13 @@ def gelu(x):
     return reference.gelu(x)
 
 
-def attention(q, k, v, mask=None, scale=None):
+def attention(q, k, v, mask=None, scale=None, causal=False):
+    """``causal``: query i sees key j iff j <= i, on top of ``mask``."""
     if _use_native(q):
+        if causal:
+            return _nlp().attention(q, k, v, mask, scale, causal=True)
         return _native().attention(q, k, v, mask, scale)
-    return reference.attention(q, k, v, mask, scale)
+    return reference.attention(q, k, v, mask, scale, causal=causal)
 
 
 def dropout(x, p, training=True):
@@ -289,16 +292,26 @@ def dense_gelu_dense(x, w1, b1, w2):
     return reference.dense(reference.bias_gelu(reference.dense(x, w1), b1), w2)
 
 
-def attention_qkv(qkv, mask, batch, seq_len, heads, p=0.0, training=True, scale=None):
+def attention_qkv(qkv, mask, batch, seq_len, heads, p=0.0, training=True, scale=None,
+                  causal=False):
     """Multi-head self-attention straight from the fused QKV projection output.
 
     ``mask`` is an additive fp32 ``[batch, seq_len]`` key mask and must be FINITE (BERT passes
     -10000 for padding).  The native kernels keep a running row maximum per 64 keys: with
     ``-inf`` over a whole first 64-key chunk the rescale evaluates ``exp2(-inf - -inf)`` and the
-    row becomes NaN."""
+    row becomes NaN.  That holds with ``causal`` too: a left-to-right mask is never passed in as
+    an additive mask, it is this flag.
+
+    ``causal=True``: query i sees key j iff j <= i, on top of ``mask``.  The native kernels skip
+    every 64-key tile above the diagonal instead of masking it, and select the hidden scores of
+    the diagonal tile to ``-inf`` themselves (safe there: key 0 is visible to every query, so the
+    running maximum is finite from the first tile on).  Dropout decisions are those of the
+    non-causal op (index ``(bh * S + q) * S + k``).  The causal backward always runs the split
+    dQ and dK/dV kernels: the returned gradient carries no fused column partials."""
     if _use_native(qkv):
-        return _nlp().attention_qkv(qkv, mask, batch, seq_len, heads, p, training, scale)
-    return reference.attention_qkv(qkv, mask, batch, seq_len, heads, p, training, scale)
+        return _nlp().attention_qkv(qkv, mask, batch, seq_len, heads, p, training, scale, causal)
+    return reference.attention_qkv(qkv, mask, batch, seq_len, heads, p, training, scale,
+                                   causal=causal)
 
 
 def mlm_loss(logits, labels, weights=None, vocab=None):

@@ -241,7 +241,7 @@ class _AttentionQKV(torch.autograd.Function):
     mask: additive fp32 [B, S] key mask (0 keep / -10000 pad) or None.  Returns [B*S, H*64]."""
 
     @staticmethod
-    def forward(ctx, qkv, mask, B, S, heads, p, scale):
+    def forward(ctx, qkv, mask, B, S, heads, p, scale, causal=False):
         if qkv.shape[-1] != 3 * heads * AD:
             raise ValueError(f"qkv last dim {qkv.shape[-1]} != 3*heads*{AD}")
         if S % 64:
@@ -253,11 +253,13 @@ class _AttentionQKV(torch.autograd.Function):
         seed = next_seed() if p > 0 else 0
         # with dropout at S == 128 the forward keeps its keep decisions (1 bit per score) for
         # the fused backward, which then skips re-hashing them
-        nk = _K.attn_keep_words(B, S, heads, float(p))
+        # (causal: split backward only, so no keep bits and no column partials)
+        nk = 0 if causal else _K.attn_keep_words(B, S, heads, float(p))
         keep = torch.empty(nk, device=qkv.device, dtype=torch.int32) if nk else None
         _K.attn_fwd(q.data_ptr(), _p(m), out.data_ptr(), lse.data_ptr(), B, S, heads,
-                    float(scale), float(p), seed, _st(), _p(keep))
+                    float(scale), float(p), seed, _st(), _p(keep), int(causal))
         ctx.keep = keep
+        ctx.causal = bool(causal)
         ctx.save_for_backward(q, m if m is not None else lse, out, lse)
         ctx.cfg = (B, S, heads, float(p), seed, float(scale), m is not None)
         return out
@@ -272,33 +274,35 @@ class _AttentionQKV(torch.autograd.Function):
         # the fused S == 128 backward also leaves per-sequence column sums of dqkv: the QKV
         # projection's bias gradient is then a B-row sum instead of a pass over dqkv
         part = None
-        if _K.attn_bwd_fused(S):
+        if not ctx.causal and _K.attn_bwd_fused(S):
             part = torch.empty(B, 3 * heads * AD, device=q.device, dtype=torch.float32)
         keep, ctx.keep = ctx.keep, None
         if keep is not None and not _K.attn_keep_words(B, S, heads, float(p)):
             keep = None          # knobs changed between forward and backward: re-hash
         _K.attn_bwd(q.data_ptr(), m.data_ptr() if has_mask else 0, out.data_ptr(), do.data_ptr(),
                     lse.data_ptr(), delta.data_ptr(), dqkv.data_ptr(), B, S, heads, scale, p, seed,
-                    _st(), _p(part), _p(keep))
+                    _st(), _p(part), _p(keep), int(ctx.causal))
         if part is not None:
             # valid only for this exact tensor and version (an in-place add would change it)
             dqkv._dtf_colsum_part = (part, B, dqkv._version)
-        return dqkv, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None
 
 
-def attention_qkv(qkv, mask, batch, seq_len, heads, p=0.0, training=True, scale=None):
+def attention_qkv(qkv, mask, batch, seq_len, heads, p=0.0, training=True, scale=None,
+                  causal=False):
     scale = AD ** -0.5 if scale is None else scale
-    return _AttentionQKV.apply(qkv, mask, batch, seq_len, heads, p if training else 0.0, scale)
+    return _AttentionQKV.apply(qkv, mask, batch, seq_len, heads, p if training else 0.0, scale,
+                               bool(causal))
 
 
-def attention(q, k, v, mask=None, scale=None):
+def attention(q, k, v, mask=None, scale=None, causal=False):
     """[B, H, S, 64] q/k/v API (packs into the fused layout; used by generic callers)."""
     B, H, S, D = q.shape
     if D != AD:
         raise ValueError("native attention supports head_dim 64")
     qkv = torch.cat([t.permute(0, 2, 1, 3).reshape(B * S, H * D) for t in (q, k, v)], dim=1)
     m = None if mask is None else mask.reshape(B, S)
-    out = attention_qkv(qkv.to(_BF16), m, B, S, H, 0.0, False, scale)
+    out = attention_qkv(qkv.to(_BF16), m, B, S, H, 0.0, False, scale, causal)
     return out.view(B, S, H, D).permute(0, 2, 1, 3)
 
 

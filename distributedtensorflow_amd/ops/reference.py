@@ -172,13 +172,23 @@ def gelu(x):
     return F.gelu(x.float(), approximate="tanh").to(x.dtype)
 
 
-def attention(q, k, v, mask=None, scale=None):
-    """q,k,v: [B, H, S, D] -> [B, H, S, D].  mask: additive [B,1,1,S] or None."""
+def _causal_select(s):
+    """Scores [..., S, S] with every key above the query's own position selected to -inf."""
+    S = s.shape[-1]
+    vis = torch.ones(S, S, dtype=torch.bool, device=s.device).tril()
+    return torch.where(vis, s, torch.full_like(s, float("-inf")))
+
+
+def attention(q, k, v, mask=None, scale=None, causal=False):
+    """q,k,v: [B, H, S, D] -> [B, H, S, D].  mask: additive [B,1,1,S] or None.  ``causal``:
+    query i sees key j iff j <= i."""
     d = q.shape[-1]
     scale = scale if scale is not None else d ** -0.5
     s = torch.matmul(q.float(), k.float().transpose(-1, -2)) * scale
     if mask is not None:
         s = s + mask.float()
+    if causal:
+        s = _causal_select(s)
     p = torch.softmax(s, dim=-1)
     return torch.matmul(p, v.float()).to(q.dtype)
 
@@ -283,8 +293,11 @@ def bias_gelu(a, bias=None):
     return F.gelu(x, approximate="tanh").to(a.dtype)
 
 
-def attention_qkv(qkv, mask, batch, seq_len, heads, p=0.0, training=True, scale=None, seed=None):
-    """qkv [B*S, 3*H*D] (all q heads | all k heads | all v heads) -> [B*S, H*D]."""
+def attention_qkv(qkv, mask, batch, seq_len, heads, p=0.0, training=True, scale=None, seed=None,
+                  causal=False):
+    """qkv [B*S, 3*H*D] (all q heads | all k heads | all v heads) -> [B*S, H*D].  ``causal``:
+    query i sees key j iff j <= i (a lower-triangular select before the softmax; the dropout
+    indices stay those of the full [B, H, S, S] space)."""
     p = p if training else 0.0
     B, S, Hh = batch, seq_len, heads
     D = qkv.shape[-1] // (3 * Hh)
@@ -294,6 +307,8 @@ def attention_qkv(qkv, mask, batch, seq_len, heads, p=0.0, training=True, scale=
     s = torch.matmul(q, k.transpose(-1, -2)) * scale
     if mask is not None:
         s = s + mask.float().view(B, 1, 1, S)
+    if causal:
+        s = _causal_select(s)
     prob = torch.softmax(s, dim=-1)
     if p > 0:
         seed = _next_seed(p) if seed is None else seed

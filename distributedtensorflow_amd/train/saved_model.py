@@ -586,6 +586,9 @@ def export_bert_saved_model(export_dir, model, seq_len=128, tags=("serve",)):
     """SavedModel of a BERT masked-LM model: inputs ``input_ids`` / ``token_type_ids`` /
     ``input_mask`` (int32 ``[batch, seq_len]``), outputs ``sequence_output`` and the MLM
     ``mlm_logits`` / ``mlm_probabilities`` over every position."""
+    if getattr(model.cfg, "causal", False):
+        raise ValueError("export_bert_saved_model: the exported graph attends in both directions; "
+                         "a causal model (BertConfig.causal=True) cannot be exported")
     _write_variables(export_dir, model)
     bg = _BertGraph(model, seq_len).build()
     _write_saved_model(export_dir, bg.g, bg.var_nodes, tags,
