@@ -890,6 +890,25 @@ PYBIND11_MODULE(_dtf_hip, m) {
   m.def("attn_bwd_fused", &dtf_attn_bwd_fused);
   m.def("attn_set_wide", &dtf_attn_set_wide);
   m.def("attn_set_fused", &dtf_attn_set_fused);
+  m.def("attn_decode_splits", &dtf_attn_decode_splits);
+  m.def("attn_decode_ws_floats", &dtf_attn_decode_ws_floats);
+  m.def("attn_decode", [](uintptr_t qkv_new, uintptr_t pos, uintptr_t k_cache, uintptr_t v_cache,
+                          uintptr_t out, uintptr_t ws, int B, int H, int C, int max_len,
+                          int splits, float scale, uintptr_t st) {
+    dtf_attn_decode(P<const bf16_t>(qkv_new), P<const int>(pos), P<bf16_t>(k_cache),
+                    P<bf16_t>(v_cache), P<bf16_t>(out), P<float>(ws), B, H, C, max_len, splits,
+                    scale, S(st));
+    check_launch("attn_decode");
+  }, py::arg("qkv_new"), py::arg("pos"), py::arg("k_cache"), py::arg("v_cache"), py::arg("out"),
+     py::arg("ws"), py::arg("B"), py::arg("H"), py::arg("C"), py::arg("max_len"),
+     py::arg("splits"), py::arg("scale"), py::arg("st"));
+  m.def("kv_cache_fill", [](uintptr_t qkv, uintptr_t k_cache, uintptr_t v_cache, int B, int S_,
+                            int H, int C, uintptr_t st) {
+    dtf_kv_cache_fill(P<const bf16_t>(qkv), P<bf16_t>(k_cache), P<bf16_t>(v_cache), B, S_, H, C,
+                      S(st));
+    check_launch("kv_cache_fill");
+  }, py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("B"), py::arg("S"),
+     py::arg("H"), py::arg("C"), py::arg("st"));
   m.def("pos_type_grad_ws_floats", &dtf_pos_type_grad_ws_floats);
   m.def("pos_type_grad", [](uintptr_t ds, uintptr_t tt, int B, int S_, int H, int NT,
                             uintptr_t dpos, uintptr_t dtyp, uintptr_t ws, uintptr_t st) {

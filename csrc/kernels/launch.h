@@ -429,6 +429,32 @@ void dtf_mlm_xent(const bf16_t* logits, const int64_t* labels, const float* weig
                   const float* denom, int N, int V, int ld, float* loss_rows, bf16_t* grad,
                   hipStream_t st);
 
+// ---- attn_decode.hip: one new query per sequence against a [B, H, C, 64] key / value cache
+struct AttnDecodeArgs {
+  const bf16_t* qkv_new;   // [B, 3*H*64]
+  const int* pos;          // [B], device: the row the new token takes
+  bf16_t* k_cache;         // [B, H, C, 64]
+  bf16_t* v_cache;
+  bf16_t* out;             // [B, H*64]
+  float* ws;               // [B, H, splits, 66] partials (splits > 1)
+  int B, H, C, splits;
+  float c;                 // scale * log2(e)
+};
+struct KvFillArgs {
+  const bf16_t* qkv;       // [B*S, 3*H*64]
+  bf16_t* k_cache;
+  bf16_t* v_cache;
+  int B, S, H, C;
+  long n;                  // 16-B chunks to copy
+};
+int dtf_attn_decode_splits(int B, int H, int max_len);
+long dtf_attn_decode_ws_floats(int B, int H, int splits);
+void dtf_attn_decode(const bf16_t* qkv_new, const int* pos, bf16_t* k_cache, bf16_t* v_cache,
+                     bf16_t* out, float* ws, int B, int H, int C, int max_len, int splits,
+                     float scale, hipStream_t st);
+void dtf_kv_cache_fill(const bf16_t* qkv, bf16_t* k_cache, bf16_t* v_cache, int B, int S, int H,
+                       int C, hipStream_t st);
+
 // ---- f32.hip
 int dtf_gemm_f32_splits(int M, int N, int K);
 void dtf_gemm_f32(const float* A, const float* B, float* C, const float* bias, int M, int N, int K,

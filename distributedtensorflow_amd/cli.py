@@ -148,11 +148,26 @@ def build_parser():
                         "rows come from --text_data unmasked, or from the synthetic set; "
                         "--mlm_prob and --max_predictions are ignored; --eval / --eval_every "
                         "also report eval_perplexity, exp of the reported (4-place) eval_loss")
+    p.add_argument("--generate", type=int, default=0, metavar="N",
+                   help="with --causal_lm: after training (and evaluation) continue the first "
+                        "min(batch, 4) rows of the validation or synthetic set by N tokens with "
+                        "the KV-cache decoder; adds generated and generate_tokens_per_sec to the "
+                        "result")
+    p.add_argument("--generate_prompt", type=int, default=16, metavar="P",
+                   help="tokens of each row used as the prompt of --generate")
+    p.add_argument("--generate_temperature", type=float, default=0.0,
+                   help="0: greedy; else softmax sampling of logits / T")
+    p.add_argument("--generate_top_k", type=int, default=0,
+                   help="sample among the K largest logits only (0: all)")
     return p
 
 
 def check_data_args(args):
     """The data flags that cannot go together: a SystemExit names the offender."""
+    if args.generate and not args.causal_lm:
+        raise SystemExit("--generate needs --causal_lm")
+    if args.generate < 0 or (args.generate and args.generate_prompt < 1):
+        raise SystemExit("--generate and --generate_prompt must be at least 1")
     if args.causal_lm:
         if not args.model.startswith("bert"):
             raise SystemExit(f"--causal_lm needs a BERT model, not {args.model}")
@@ -519,11 +534,48 @@ def run(args):
             result["eval_count"] = int(ev["count"])
         elif args.model.startswith("mnist"):
             result["test_accuracy"] = round(ev["top_1"], 4)
+    if args.generate and is_chief:
+        result.update(_generate(args, model, device, batch))
     if is_chief:
         print(json.dumps(result), flush=True)
     if server is not None:
         server.shutdown()
     return 0
+
+
+def _generate(args, model, device, batch):
+    """--generate: prompts from the first rows of the validation (--text_data) or synthetic set,
+    continued by ``BertForPreTraining.generate`` -> the two result entries."""
+    import torch
+    if args.text_data:
+        rows = next(iter(_token_dataset(args, "val", batch, device, 1, 0).single_pass()))
+    else:
+        from .data import SyntheticMLM
+        rows = next(iter(SyntheticMLM(batch, args.seq_len, device=device, seed=4321,
+                                      pool=1).single_pass(1)))
+    ids = rows["input_ids"][:min(batch, 4)]
+    P = args.generate_prompt
+    if P > ids.shape[1]:
+        raise SystemExit(f"--generate_prompt {P} exceeds the rows' {ids.shape[1]} tokens")
+    # the prefill runs the causal forward: S % 64 == 0 on the device
+    Sp = -(-P // 64) * 64 if ids.is_cuda else P
+    prompt = torch.zeros(ids.shape[0], Sp, dtype=torch.int64, device=ids.device)
+    prompt[:, :P] = ids[:, :P]
+    gen = torch.Generator(device=ids.device).manual_seed(args.seed & 0xFFFFFFFF)
+    cuda = ids.is_cuda
+    try:
+        if cuda:
+            torch.cuda.synchronize()
+        t0 = time.time()
+        out = model.generate(prompt, torch.full((ids.shape[0],), P), args.generate,
+                             args.generate_temperature, args.generate_top_k, generator=gen)
+        if cuda:
+            torch.cuda.synchronize()
+    except ValueError as e:
+        raise SystemExit(f"--generate: {e}")
+    dt = max(time.time() - t0, 1e-9)
+    return {"generated": out.cpu().tolist(),
+            "generate_tokens_per_sec": round(out.numel() / dt, 1)}
 
 
 def _image_dataset(args, split, num_classes, batch, device, dtype, shards, shard_index):

@@ -6,6 +6,14 @@ from .resnet import ResNet, num_params, resnet50, resnet101, resnet152
 
 __all__ = [
     "BatchNormalization", "Conv2D", "Dense", "Layer", "MaxPooling2D", "NameScope",
-    "collect_variables", "name_scope", "MnistCNN", "MnistMLP", "ResNet", "num_params",
+    "collect_variables", "name_scope", "KVCache", "MnistCNN", "MnistMLP", "ResNet", "num_params",
     "resnet50", "resnet101", "resnet152",
 ]
+
+
+def __getattr__(name):
+    # the BERT module is imported on first use, like bert_base / bert_large (models.bert)
+    if name == "KVCache":
+        from .bert import KVCache
+        return KVCache
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

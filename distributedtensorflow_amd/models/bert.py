@@ -131,12 +131,28 @@ class BertLayer(nn.Module):
         self.out = _Dense(cfg.intermediate_size, H, f"{pre}/output/dense", std)
         self.out_ln = _LayerNorm(H, f"{pre}/output/LayerNorm")
 
-    def forward(self, x, mask, B, S):
+    def forward(self, x, mask, B, S, cache=None):
+        """``cache``: a ``(k, v)`` pair of [B, heads, C, 64] tensors that receives this layer's
+        keys and values of positions 0 .. S-1 (the prefill of incremental decoding)."""
         cfg = self.cfg
         qkv = ops.dense(x, self.qkv_kernel, self.qkv_bias, impl=BERT_GEMM)
+        if cache is not None:
+            ops.kv_cache_fill(qkv, cache[0], cache[1], B, S, cfg.num_attention_heads)
         ctx = ops.attention_qkv(qkv, mask, B, S, cfg.num_attention_heads,
                                 cfg.attention_probs_dropout_prob, self.training,
                                 causal=cfg.causal)
+        return self._after_attention(x, ctx)
+
+    def decode(self, x, k_cache, v_cache, pos, max_len=None):
+        """One new token per sequence (x [B, H]) at positions ``pos`` against this layer's cache,
+        which takes the token's key and value in place."""
+        qkv = ops.dense(x, self.qkv_kernel, self.qkv_bias, impl=BERT_GEMM)
+        ctx = ops.attention_decode(qkv, k_cache, v_cache, pos, self.cfg.num_attention_heads,
+                                   max_len=max_len)
+        return self._after_attention(x, ctx)
+
+    def _after_attention(self, x, ctx):
+        cfg = self.cfg
         a = self.attn_out.gemm(ctx)
         # x feeds the QKV dense above and the residual here: its two gradients are summed by
         # that dense's dgrad GEMM (beta = 1), not by a separate add
@@ -200,8 +216,9 @@ class BertForPreTraining(Layer):
                 else:
                     yield p._dtf_name, p, p._dtf_layout
 
-    def encode(self, input_ids, token_type_ids=None, attention_mask=None):
-        """-> ([B*S, H] final hidden states, additive key mask)."""
+    def encode(self, input_ids, token_type_ids=None, attention_mask=None, cache=None):
+        """-> ([B*S, H] final hidden states, additive key mask).  ``cache``: a :class:`KVCache`
+        that every layer fills with its keys and values."""
         cfg = self.cfg
         B, S = input_ids.shape
         dtype = torch.bfloat16 if input_ids.is_cuda else torch.float32
@@ -212,8 +229,11 @@ class BertForPreTraining(Layer):
         mask = None
         if attention_mask is not None:
             mask = (1.0 - attention_mask.float()) * -10000.0
-        for layer in self.layers:
-            x = layer(x, mask, B, S)
+        for i, layer in enumerate(self.layers):
+            if cache is None:
+                x = layer(x, mask, B, S)
+            else:
+                x = layer(x, mask, B, S, cache=(cache.k[i], cache.v[i]))
         return x, mask
 
     def forward(self, input_ids, token_type_ids=None, attention_mask=None,
@@ -227,15 +247,142 @@ class BertForPreTraining(Layer):
             masked_lm_positions = torch.arange(S, device=x.device).expand(B, S)
         flat = (masked_lm_positions + torch.arange(B, device=x.device).unsqueeze(1) * S).reshape(-1)
         h = x.index_select(0, flat)                                      # [B*P, H] gather
-        h = ops.bias_gelu(self.mlm_transform.gemm(h), self.mlm_transform.bias)
-        h = ops.bias_dropout_add_layer_norm(h, None, None, self.mlm_ln.gamma, self.mlm_ln.beta,
-                                            0.0, self.training, cfg.layer_norm_eps)
-        # tied decoder over the padded vocabulary [B*P, Vp]; the padding logits are exactly 0
-        logits = ops.dense(h, self.word_embeddings, self.mlm_bias, impl=BERT_GEMM)
+        logits = self._head(h)
         V = cfg.vocab_size
         if masked_lm_ids is None:
             return logits if logits.shape[-1] == V else logits[:, :V]
         return ops.mlm_loss(logits, masked_lm_ids, masked_lm_weights, vocab=V)
+
+    def _head(self, h):
+        """Hidden rows [N, H] -> logits over the padded vocabulary [N, Vp] (the padding logits
+        are exactly 0)."""
+        h = ops.bias_gelu(self.mlm_transform.gemm(h), self.mlm_transform.bias)
+        h = ops.bias_dropout_add_layer_norm(h, None, None, self.mlm_ln.gamma, self.mlm_ln.beta,
+                                            0.0, self.training, self.cfg.layer_norm_eps)
+        return ops.dense(h, self.word_embeddings, self.mlm_bias, impl=BERT_GEMM)
+
+    # ------------------------------------------------------------------------- generation
+    def _check_prompts(self, input_ids, prompt_lens):
+        if not self.cfg.causal:
+            raise ValueError("incremental decoding needs a causal model (BertConfig(causal=True))")
+        B, Sp = input_ids.shape
+        lens = torch.as_tensor(prompt_lens).reshape(-1).cpu()
+        if lens.numel() != B or int(lens.min()) < 1 or int(lens.max()) > Sp:
+            raise ValueError(f"prompt_lens must hold {B} lengths in [1, {Sp}]")
+        return lens
+
+    @torch.no_grad()
+    def prefill(self, input_ids, prompt_lens, cache):
+        """The causal forward over the right-padded prompts [B, Sp] (``prompt_lens``: CPU lengths
+        in [1, Sp]): fills every layer of ``cache``, sets ``cache.pos = prompt_lens`` and returns
+        the logits of each row's last real position, [B, vocab_size]."""
+        lens = self._check_prompts(input_ids, prompt_lens)
+        B, Sp = input_ids.shape
+        if B != cache.batch or Sp > cache.capacity:
+            raise ValueError(f"cache is for batch {cache.batch}, capacity {cache.capacity}")
+        dev = input_ids.device
+        lens_d = lens.to(dev)
+        am = (torch.arange(Sp, device=dev).unsqueeze(0) < lens_d.unsqueeze(1)).long()
+        x, _ = self.encode(input_ids, None, am, cache=cache)
+        cache.pos.copy_(lens_d)
+        cache.max_len = int(lens.max())
+        last = torch.arange(B, device=dev) * Sp + lens_d.long() - 1
+        return self._head(x.index_select(0, last))[:, :self.cfg.vocab_size]
+
+    @torch.no_grad()
+    def decode_step(self, ids_new, cache):
+        """One token per sequence (``ids_new`` [B]) at positions ``cache.pos``: every layer runs
+        at B rows with ``ops.attention_decode`` against its cache, ``cache.pos`` advances by one
+        on the device.  -> logits [B, vocab_size].  Nothing here reads the device."""
+        cfg = self.cfg
+        if not cfg.causal:
+            raise ValueError("incremental decoding needs a causal model (BertConfig(causal=True))")
+        dtype = cache.k.dtype
+        # the embedding kernel indexes positions by row % S: form word[id] + pos[p] + type[0] as
+        # it does (tables rounded to the activation dtype, summed in fp32, rounded once)
+        p = cache.pos.long().clamp(max=cfg.max_position_embeddings - 1)
+        s = (self.word_embeddings[ids_new.reshape(-1)].to(dtype).float()
+             + self.position_embeddings[p].to(dtype).float()
+             + self.token_type_embeddings[0].to(dtype).float()).to(dtype)
+        x = ops.bias_dropout_add_layer_norm(s, None, None, self.emb_ln.gamma, self.emb_ln.beta,
+                                            0.0, False, cfg.layer_norm_eps)
+        cache.max_len = min(cache.max_len + 1, cache.capacity)
+        for i, layer in enumerate(self.layers):
+            x = layer.decode(x, cache.k[i], cache.v[i], cache.pos, cache.max_len)
+        cache.pos.add_(1)
+        return self._head(x)[:, :cfg.vocab_size]
+
+    def generate(self, input_ids, prompt_lens, max_new_tokens, temperature=0.0, top_k=0,
+                 eos_id=None, generator=None):
+        """Continue the right-padded prompts [B, Sp] by ``max_new_tokens`` tokens -> int64
+        [B, max_new_tokens].  Greedy at ``temperature == 0``; otherwise softmax sampling of
+        ``logits / temperature`` over the ``top_k`` largest (all when 0) with ``generator``.  A row
+        that has produced ``eos_id`` keeps producing it.  ``prompt_lens`` are CPU lengths: the one
+        host check (capacity) is made from them before the loop, which never reads the device."""
+        lens = self._check_prompts(input_ids, prompt_lens)
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be at least 1")
+        need = int(lens.max()) + max_new_tokens
+        if need > self.cfg.max_position_embeddings:
+            raise ValueError(f"prompt + max_new_tokens = {need} exceeds the capacity "
+                             f"{self.cfg.max_position_embeddings}")
+        dev = input_ids.device
+        cache = KVCache(self.cfg, input_ids.shape[0], need, dev,
+                        torch.bfloat16 if input_ids.is_cuda else torch.float32,
+                        min_rows=input_ids.shape[1])
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                out = torch.empty(input_ids.shape[0], max_new_tokens, dtype=torch.int64,
+                                  device=dev)
+                done = torch.zeros(input_ids.shape[0], dtype=torch.bool, device=dev)
+                logits = self.prefill(input_ids, lens, cache)
+                for t in range(max_new_tokens):
+                    tok = _pick(logits, temperature, top_k, generator)
+                    if eos_id is not None:
+                        tok = torch.where(done, torch.full_like(tok, eos_id), tok)
+                        done = done | (tok == eos_id)
+                    out[:, t] = tok
+                    if t + 1 < max_new_tokens:
+                        logits = self.decode_step(tok, cache)
+        finally:
+            self.train(was_training)
+        return out
+
+
+def _pick(logits, temperature, top_k, generator):
+    """The next token of every row: argmax, or a sample of softmax(logits / temperature) over the
+    ``top_k`` largest logits."""
+    if temperature <= 0:
+        return logits.argmax(-1)
+    x = logits.float() / temperature
+    if top_k > 0:
+        vals, idx = x.topk(min(top_k, x.shape[-1]), dim=-1)
+        choice = torch.multinomial(torch.softmax(vals, -1), 1, generator=generator)
+        return idx.gather(1, choice).squeeze(1)
+    return torch.multinomial(torch.softmax(x, -1), 1, generator=generator).squeeze(1)
+
+
+class KVCache:
+    """The keys and values of every layer for incremental decoding: ``k`` / ``v``
+    [L, B, heads, C, 64] (one (batch, head)'s keys are contiguous 128-B rows, the layout the decode
+    kernel streams) and ``pos`` int32 [B] on the device, the row each sequence's next token takes.
+    ``capacity`` is rounded up to a multiple of 64.  ``max_len`` is the host's upper bound on
+    ``pos + 1``; it only sizes launches."""
+
+    def __init__(self, cfg: BertConfig, batch, capacity, device, dtype=torch.bfloat16,
+                 min_rows=0):
+        # min_rows: storage for a prefill whose padding runs past the capacity
+        C = -(-max(int(capacity), int(min_rows)) // 64) * 64
+        if capacity < 1 or capacity > cfg.max_position_embeddings:
+            raise ValueError(f"capacity {capacity} outside [1, max_position_embeddings = "
+                             f"{cfg.max_position_embeddings}]")
+        shape = (cfg.num_hidden_layers, batch, cfg.num_attention_heads, C, 64)
+        self.k = torch.zeros(shape, device=device, dtype=dtype)
+        self.v = torch.zeros(shape, device=device, dtype=dtype)
+        self.pos = torch.zeros(batch, device=device, dtype=torch.int32)
+        self.batch, self.capacity, self.max_len = batch, C, C
 
 
 def bert_base(**kw) -> BertForPreTraining:
@@ -266,5 +413,5 @@ def causal_lm_flops_per_token(cfg: BertConfig, seq_len: int) -> float:
     return 3.0 * (gemm + attn + head)
 
 
-__all__ = ["BertConfig", "BertForPreTraining", "BertLayer", "bert_base", "bert_large",
+__all__ = ["BertConfig", "BertForPreTraining", "BertLayer", "KVCache", "bert_base", "bert_large",
            "causal_lm_flops_per_token", "mlm_flops_per_token"]

@@ -314,6 +314,31 @@ def attention_qkv(qkv, mask, batch, seq_len, heads, p=0.0, training=True, scale=
                                    causal=causal)
 
 
+def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=None, splits=0):
+    """Incremental decoding: one new query per sequence against a key / value cache.
+
+    ``qkv_new`` [B, 3*heads*64] is the new token's fused projection, ``k_cache`` / ``v_cache`` are
+    [B, heads, C, 64] (C % 64 == 0) and ``pos`` int32 [B] is the row the new token takes.  The new
+    K / V rows are written into the caches IN PLACE at ``pos[b]`` (clamped to the cache) and the
+    query attends keys 0 .. pos[b]: ``softmax(q K^T scale) V`` -> [B, heads*64].  No mask, no
+    dropout; rows past ``pos[b]`` may hold anything and are never used.  Native: ``pos`` is read on
+    the device only; ``max_len`` (an upper bound on pos + 1, default C) and ``splits`` (0 = choose)
+    size the launch.  A no-grad op.  Not fenced: it reads no variable."""
+    if _use_native(qkv_new):
+        return _nlp().attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale, max_len,
+                                       splits)
+    return reference.attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale, max_len,
+                                      splits)
+
+
+def kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads):
+    """Copy the K and V thirds of a prefill's fused QKV matrix [batch*seq_len, 3*heads*64] into
+    rows 0 .. seq_len-1 of the [batch, heads, C, 64] caches, in place.  A no-grad op.  Not fenced: it reads no variable."""
+    if _use_native(qkv):
+        return _nlp().kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads)
+    return reference.kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads)
+
+
 def mlm_loss(logits, labels, weights=None, vocab=None):
     """Weighted masked-LM cross-entropy.  ``vocab``: the class count when the logits rows are
     padded past it (BERT's tied decoder runs on a vocabulary padded to a multiple of 64)."""
@@ -487,5 +512,5 @@ __all__ = [
     "bias_dropout_add_layer_norm", "embedding_layer_norm", "bias_gelu", "bias_gelu_dense",
     "dense_gelu_dense", "attention_qkv", "mlm_loss", "eval_rows", "in_top_k", "augment_images",
     "mlm_mask_tokens", "ema_update", "grad_accumulate", "augment_mix_images",
-    "mixed_softmax_cross_entropy", "augment_rand_images",
+    "mixed_softmax_cross_entropy", "augment_rand_images", "attention_decode", "kv_cache_fill",
 ]

@@ -306,6 +306,46 @@ def attention(q, k, v, mask=None, scale=None, causal=False):
     return out.view(B, S, H, D).permute(0, 2, 1, 3)
 
 
+# ----------------------------------------------------------------------------- decoding
+def _check_decode_tensors(name, *tensors):
+    for t in tensors:
+        if not t.is_cuda or t.dtype != _BF16:
+            raise ValueError(f"native {name} takes bf16 device tensors")
+
+
+def kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads):
+    """csrc/kernels/attn_decode.hip kv_cache_fill_kernel (see ``reference.kv_cache_fill``)."""
+    from . import reference
+    reference.no_grad_op("kv_cache_fill", qkv, k_cache, v_cache)
+    reference.check_fill_args(qkv, k_cache, v_cache, batch, seq_len, heads)
+    _check_decode_tensors("kv_cache_fill", qkv, k_cache, v_cache)
+    q = qkv.detach().contiguous()
+    _K.kv_cache_fill(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), batch, seq_len, heads,
+                     k_cache.shape[2], _st())
+
+
+def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=None, splits=0):
+    """csrc/kernels/attn_decode.hip (see ``reference.attention_decode``).  ``pos`` stays on the
+    device: nothing here reads it, so a generation loop launches its steps without a sync."""
+    from . import reference
+    reference.no_grad_op("attention_decode", qkv_new, k_cache, v_cache)
+    B, C, max_len = reference.check_decode_args(qkv_new, k_cache, v_cache, pos, heads, max_len,
+                                                splits)
+    _check_decode_tensors("attention_decode", qkv_new, k_cache, v_cache)
+    if not pos.is_cuda:
+        raise ValueError("native attention_decode takes pos on the device")
+    scale = AD ** -0.5 if scale is None else scale
+    q = qkv_new.detach().contiguous()
+    splits = splits or _K.attn_decode_splits(B, heads, max_len)
+    nws = _K.attn_decode_ws_floats(B, heads, splits)
+    ws = torch.empty(nws, device=q.device, dtype=torch.float32) if nws else None
+    out = torch.empty(B, heads * AD, device=q.device, dtype=_BF16)
+    _K.attn_decode(q.data_ptr(), pos.contiguous().data_ptr(), k_cache.data_ptr(),
+                   v_cache.data_ptr(), out.data_ptr(), _p(ws), B, heads, C, max_len, splits,
+                   float(scale), _st())
+    return out
+
+
 # ----------------------------------------------------------------------------- MLM loss
 class _MlmLoss(torch.autograd.Function):
     """``vocab``: the class count when the logits rows are padded past it (the tied decoder's

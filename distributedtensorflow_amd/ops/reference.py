@@ -318,6 +318,83 @@ def attention_qkv(qkv, mask, batch, seq_len, heads, p=0.0, training=True, scale=
     return o.permute(0, 2, 1, 3).reshape(B * S, Hh * D).to(qkv.dtype)
 
 
+def check_decode_args(qkv_new, k_cache, v_cache, pos, heads, max_len, splits):
+    """The shape / dtype conditions of ``attention_decode``, shared by both backends ->
+    (B, capacity, max_len)."""
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[3] != 64:
+        raise ValueError("k_cache and v_cache must both be [B, heads, capacity, 64]")
+    B, H, C, D = k_cache.shape
+    if H != heads:
+        raise ValueError(f"caches hold {H} heads, not {heads}")
+    if qkv_new.dim() != 2 or tuple(qkv_new.shape) != (B, 3 * H * D):
+        raise ValueError(f"qkv_new must be [{B}, {3 * H * D}], got {tuple(qkv_new.shape)}")
+    if C < 64 or C % 64:
+        raise ValueError("cache capacity must be a multiple of 64, at least 64")
+    if pos.dtype != torch.int32 or tuple(pos.shape) != (B,):
+        raise ValueError(f"pos must be int32 [{B}]")
+    if not (qkv_new.dtype == k_cache.dtype == v_cache.dtype):
+        raise ValueError("qkv_new and the caches must share one dtype")
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("the caches must be contiguous")
+    max_len = C if max_len is None else int(max_len)
+    if not 1 <= max_len <= C:
+        raise ValueError("max_len must lie in [1, capacity]")
+    if splits < 0 or splits > -(-max_len // 64):
+        raise ValueError(f"splits {splits} exceeds the {-(-max_len // 64)} tiles of max_len")
+    return B, C, max_len
+
+
+def check_fill_args(qkv, k_cache, v_cache, batch, seq_len, heads):
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[3] != 64:
+        raise ValueError("k_cache and v_cache must both be [B, heads, capacity, 64]")
+    B, H, C, D = k_cache.shape
+    if (B, H) != (batch, heads):
+        raise ValueError(f"caches are for batch {B}, {H} heads")
+    if qkv.dim() != 2 or tuple(qkv.shape) != (batch * seq_len, 3 * H * D):
+        raise ValueError(f"qkv must be [{batch * seq_len}, {3 * H * D}], got {tuple(qkv.shape)}")
+    if C < 64 or C % 64 or not 1 <= seq_len <= C:
+        raise ValueError("capacity must be a multiple of 64 and 1 <= seq_len <= capacity")
+    if not (qkv.dtype == k_cache.dtype == v_cache.dtype):
+        raise ValueError("qkv and the caches must share one dtype")
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("the caches must be contiguous")
+
+
+def no_grad_op(name, *tensors):
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError(f"{name} is a no-grad op: call it under torch.no_grad()")
+
+
+def kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads):
+    """The K and V thirds of a prefill qkv [B*S, 3*H*64] into rows 0 .. S-1 of the [B, H, C, 64]
+    caches (in place; rows >= S untouched)."""
+    no_grad_op("kv_cache_fill", qkv, k_cache, v_cache)
+    check_fill_args(qkv, k_cache, v_cache, batch, seq_len, heads)
+    x = qkv.detach().view(batch, seq_len, 3, heads, 64)
+    k_cache[:, :, :seq_len] = x[:, :, 1].permute(0, 2, 1, 3)
+    v_cache[:, :, :seq_len] = x[:, :, 2].permute(0, 2, 1, 3)
+
+
+def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=None, splits=0):
+    """One new query per sequence against the caches: the new K / V rows go to row ``pos[b]``
+    (clamped to the cache), the query attends keys 0 .. pos[b].  fp32 math on the stored values;
+    ``max_len`` and ``splits`` only size the native launch."""
+    no_grad_op("attention_decode", qkv_new, k_cache, v_cache)
+    B, C, _ = check_decode_args(qkv_new, k_cache, v_cache, pos, heads, max_len, splits)
+    scale = 64 ** -0.5 if scale is None else scale
+    x = qkv_new.detach().view(B, 3, heads, 64)
+    p = pos.long().clamp(0, C - 1)
+    rows = torch.arange(B, device=pos.device)
+    k_cache[rows, :, p] = x[:, 1]
+    v_cache[rows, :, p] = x[:, 2]
+    s = torch.einsum("bhd,bhkd->bhk", x[:, 0].float(), k_cache.float()) * scale
+    vis = torch.arange(C, device=pos.device).view(1, 1, C) <= p.view(B, 1, 1)
+    prob = torch.softmax(torch.where(vis, s, torch.full_like(s, float("-inf"))), dim=-1)
+    # select, not multiply: unwritten cache rows may hold anything
+    v = torch.where(vis.unsqueeze(-1), v_cache.float(), torch.zeros((), device=pos.device))
+    return torch.einsum("bhk,bhkd->bhd", prob, v).reshape(B, heads * 64).to(qkv_new.dtype)
+
+
 def mlm_loss(logits, labels, weights=None, vocab=None):
     """sum_i w_i * nll_i / sum_i w_i  (google-research/bert run_pretraining.py).  ``vocab``: the
     class count when the logits rows are padded past it (columns from ``vocab`` on are ignored)."""

@@ -10,6 +10,14 @@ variants in this process in alternation (``--rounds`` rounds of ``--iters`` call
 line per (S, dropout) with the median and the min-max spread of each and their ratio next to the
 share of 64 x 64 tiles a causal kernel visits, (n + 1) / (2 n) at n = S / 64.  The non-causal
 side is what the op runs: at S = 128 the fused backward, with the keep bits under dropout.
+
+``--decode`` times the incremental-decoding kernel (csrc/kernels/attn_decode.hip) instead: one
+query per sequence against a cache of ``len`` keys for B in {1, 8, 64} and len in {128, 512, 2048},
+with the launcher's own ``splits`` and with ``splits = 1``, both arms in this process in
+alternation; every call takes the next of a ring of caches (512 MB in all, at most 64), so that
+the larger shapes stream from HBM rather than from a cache that one call has just filled.  One
+JSON line per shape: median time, spread, the bytes the algorithm must move (K and V once,
+``2 * len * 128 * B * H``, plus the fp32 partials written and read back) and bytes / time.
 """
 import argparse
 import json
@@ -86,18 +94,61 @@ def causal_main(a):
             print(json.dumps(rec), flush=True)
 
 
+def decode_main(a):
+    H, dev = a.heads, "cuda"
+    st = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    for B in (1, 8, 64):
+        for n in (128, 512, 2048):
+            kv_bytes = 2 * n * 128 * B * H
+            ring = max(2, min(64, (512 << 20) // kv_bytes))
+            g = torch.Generator(device=dev).manual_seed(n + B)
+            kc = (torch.randn(ring, B, H, n, 64, device=dev, generator=g) * 0.5).to(torch.bfloat16)
+            vc = torch.randn(ring, B, H, n, 64, device=dev, generator=g).to(torch.bfloat16)
+            new = (torch.randn(B, 3 * H * 64, device=dev, generator=g) * 0.5).to(torch.bfloat16)
+            pos = torch.full((B,), n - 1, device=dev, dtype=torch.int32)
+            out = torch.empty(B, H * 64, device=dev, dtype=torch.bfloat16)
+            auto = _K.attn_decode_splits(B, H, n)
+            ws = torch.empty(max(1, _K.attn_decode_ws_floats(B, H, auto)), device=dev)
+            turn = [0]
+
+            def call(splits):
+                i = turn[0] = (turn[0] + 1) % ring
+                _K.attn_decode(new.data_ptr(), pos.data_ptr(), kc[i].data_ptr(), vc[i].data_ptr(),
+                               out.data_ptr(), ws.data_ptr(), B, H, n, n, splits, 0.125, st())
+
+            arms = {"auto": auto, "one": 1}
+            t = {k: [] for k in arms}
+            for _ in range(a.rounds):
+                for k, sp in arms.items():
+                    t[k].append(timeit(lambda: call(sp), a.iters))
+            rec = {"probe": "attn_decode", "B": B, "H": H, "len": n, "ring": ring,
+                   "rounds": a.rounds, "iters": a.iters, "splits_auto": auto}
+            for k, sp in arms.items():
+                moved = kv_bytes + (2 * 4 * B * H * sp * 66 if sp > 1 else 0)
+                rec[f"{k}_us"] = round(med(t[k]) * 1e3, 2)
+                rec[f"{k}_spread_us"] = [round(min(t[k]) * 1e3, 2), round(max(t[k]) * 1e3, 2)]
+                rec[f"{k}_bytes"] = moved
+                rec[f"{k}_GBps"] = round(moved / (med(t[k]) * 1e-3) / 1e9, 1)
+            print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--decode", action="store_true",
+                    help="time the incremental-decoding kernel (see above)")
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--seq", type=int, default=128)
     ap.add_argument("--heads", type=int, default=12)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--causal", action="store_true",
                     help="time the causal kernels against the non-causal ones (see above)")
-    ap.add_argument("--rounds", type=int, default=5, help="--causal: alternation rounds")
+    ap.add_argument("--rounds", type=int, default=5, help="--causal / --decode: alternation rounds")
     a = ap.parse_args()
     if a.causal:
         return causal_main(a)
+    if a.decode:
+        return decode_main(a)
     B, S, H, D = a.batch, a.seq, a.heads, 64
     dev = "cuda"
     g = torch.Generator(device=dev).manual_seed(0)

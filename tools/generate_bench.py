@@ -1,0 +1,82 @@
+"""Generation with the KV cache against the only alternative without it: re-running the padded
+causal forward over the whole prefix for every token and taking its last row.
+
+    python tools/generate_bench.py [--batch 8] [--prompt 64] [--new 128] [--rounds 3]
+
+BERT-base, causal, greedy, random weights.  Both arms run in this process in alternation; one JSON
+line with the median seconds and tokens per second of each, and the route the M = batch GEMMs of a
+decode step take (``_dense_gemm_native``: the persistent MFMA GEMM, else ``F.linear``).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from distributedtensorflow_amd.models import bert  # noqa: E402
+from distributedtensorflow_amd.ops import native  # noqa: E402
+
+
+def recompute(model, prompt, plen, n_new):
+    """Greedy decoding at the parent's means: the causal forward over the prefix, padded to a
+    multiple of 64, once per token."""
+    B = prompt.shape[0]
+    seq = torch.zeros(B, plen + n_new, dtype=torch.int64, device=prompt.device)
+    seq[:, :plen] = prompt[:, :plen]
+    with torch.no_grad():
+        for t in range(n_new):
+            n = plen + t
+            S = -(-n // 64) * 64
+            ids = torch.zeros(B, S, dtype=torch.int64, device=prompt.device)
+            ids[:, :n] = seq[:, :n]
+            seq[:, n] = model(ids).view(B, S, -1)[:, n - 1].argmax(-1)
+    return seq[:, plen:]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=8)
+    ap.add_argument("--prompt", type=int, default=64)
+    ap.add_argument("--new", type=int, default=128)
+    ap.add_argument("--rounds", type=int, default=3)
+    a = ap.parse_args()
+    torch.manual_seed(0)
+    model = bert.bert_base(causal=True).cuda().eval()
+    B, P = a.batch, a.prompt
+    Sp = -(-P // 64) * 64
+    prompt = torch.zeros(B, Sp, dtype=torch.int64, device="cuda")
+    prompt[:, :P] = torch.randint(1, 30522, (B, P), device="cuda")
+    lens = torch.full((B,), P)
+    arms = {"kv_cache": lambda: model.generate(prompt, lens, a.new),
+            "recompute": lambda: recompute(model, prompt, P, a.new)}
+    times = {k: [] for k in arms}
+    outs = {}
+    for r in range(a.rounds + 1):                     # round 0 warms both arms up
+        for k, fn in arms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            outs[k] = fn()
+            torch.cuda.synchronize()
+            if r:
+                times[k].append(time.perf_counter() - t0)
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    cfg = model.cfg
+    Hd, I = cfg.hidden_size, cfg.intermediate_size
+    rec = {"probe": "generate", "model": "bert_base", "B": B, "prompt": P, "new": a.new,
+           "rounds": a.rounds,
+           "same_tokens": float((outs["kv_cache"] == outs["recompute"]).float().mean()),
+           "decode_gemm_native": {f"{n}x{k}": bool(native._dense_gemm_native(B, n, k))
+                                  for n, k in ((3 * Hd, Hd), (Hd, Hd), (I, Hd), (Hd, I))}}
+    for k in arms:
+        rec[f"{k}_s"] = round(med(times[k]), 4)
+        rec[f"{k}_spread_s"] = [round(min(times[k]), 4), round(max(times[k]), 4)]
+        rec[f"{k}_tokens_per_sec"] = round(B * a.new / med(times[k]), 1)
+    rec["speedup"] = round(med(times["recompute"]) / med(times["kv_cache"]), 2)
+    print(json.dumps(rec), flush=True)
+
+
+if __name__ == "__main__":
+    main()
