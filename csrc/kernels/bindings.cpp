@@ -909,6 +909,16 @@ PYBIND11_MODULE(_dtf_hip, m) {
     check_launch("kv_cache_fill");
   }, py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("B"), py::arg("S"),
      py::arg("H"), py::arg("C"), py::arg("st"));
+  m.def("sample_max_keys", &dtf_sample_max_keys, py::arg("large"));
+  m.def("sample_tokens", [](uintptr_t logits, uintptr_t counter, uintptr_t tokens,
+                            uintptr_t logprob, int B, int V, int ld, uint32_t seed,
+                            float temperature, int top_k, float top_p, uintptr_t st) {
+    dtf_sample_tokens(P<const bf16_t>(logits), P<const int>(counter), P<int64_t>(tokens),
+                      P<float>(logprob), B, V, ld, seed, temperature, top_k, top_p, S(st));
+    check_launch("sample_tokens");
+  }, py::arg("logits"), py::arg("counter"), py::arg("tokens"), py::arg("logprob"), py::arg("B"),
+     py::arg("V"), py::arg("ld"), py::arg("seed"), py::arg("temperature"), py::arg("top_k"),
+     py::arg("top_p"), py::arg("st"));
   m.def("pos_type_grad_ws_floats", &dtf_pos_type_grad_ws_floats);
   m.def("pos_type_grad", [](uintptr_t ds, uintptr_t tt, int B, int S_, int H, int NT,
                             uintptr_t dpos, uintptr_t dtyp, uintptr_t ws, uintptr_t st) {

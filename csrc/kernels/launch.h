@@ -455,6 +455,24 @@ void dtf_attn_decode(const bf16_t* qkv_new, const int* pos, bf16_t* k_cache, bf1
 void dtf_kv_cache_fill(const bf16_t* qkv, bf16_t* k_cache, bf16_t* v_cache, int B, int S, int H,
                        int C, hipStream_t st);
 
+// ---- sample.hip: top-k / top-p filtering and the draw of one token per logits row, one kernel
+struct SampleArgs {
+  const bf16_t* logits;    // [B, ld], columns >= V are padding
+  const int* counter;      // [B], device: the draw's counter (a KV cache's pos)
+  int64_t* tokens;         // [B]
+  float* logprob;          // [B]
+  int V, ld;
+  uint32_t seed;
+  int top_k;               // 0 or >= V: no top-k filter
+  float top_p;             // >= 1: no top-p filter
+  float c;                 // log2(e) / temperature (log2(e) when greedy)
+  int greedy;
+};
+int dtf_sample_max_keys(bool large);
+void dtf_sample_tokens(const bf16_t* logits, const int* counter, int64_t* tokens, float* logprob,
+                       int B, int V, int ld, uint32_t seed, float temperature, int top_k,
+                       float top_p, hipStream_t st);
+
 // ---- f32.hip
 int dtf_gemm_f32_splits(int M, int N, int K);
 void dtf_gemm_f32(const float* A, const float* B, float* C, const float* bias, int M, int N, int K,

@@ -159,6 +159,12 @@ def build_parser():
                    help="0: greedy; else softmax sampling of logits / T")
     p.add_argument("--generate_top_k", type=int, default=0,
                    help="sample among the K largest logits only (0: all)")
+    p.add_argument("--generate_top_p", type=float, default=1.0,
+                   help="nucleus sampling: the smallest set of the largest logits with this share "
+                        "of the mass; needs --generate_seed")
+    p.add_argument("--generate_seed", type=int, default=None,
+                   help="pick every token with the fused on-device sampler, reproducible from "
+                        "this seed (default: torch's generator seeded with --seed)")
     return p
 
 
@@ -563,12 +569,17 @@ def _generate(args, model, device, batch):
     prompt[:, :P] = ids[:, :P]
     gen = torch.Generator(device=ids.device).manual_seed(args.seed & 0xFFFFFFFF)
     cuda = ids.is_cuda
+    kw = {"generator": gen}
+    if args.generate_seed is not None:
+        kw = {"seed": args.generate_seed}
+    if args.generate_top_p != 1.0:
+        kw["top_p"] = args.generate_top_p
     try:
         if cuda:
             torch.cuda.synchronize()
         t0 = time.time()
         out = model.generate(prompt, torch.full((ids.shape[0],), P), args.generate,
-                             args.generate_temperature, args.generate_top_k, generator=gen)
+                             args.generate_temperature, args.generate_top_k, **kw)
         if cuda:
             torch.cuda.synchronize()
     except ValueError as e:

@@ -272,7 +272,7 @@ class BertForPreTraining(Layer):
         return lens
 
     @torch.no_grad()
-    def prefill(self, input_ids, prompt_lens, cache):
+    def prefill(self, input_ids, prompt_lens, cache, _padded=False):
         """The causal forward over the right-padded prompts [B, Sp] (``prompt_lens``: CPU lengths
         in [1, Sp]): fills every layer of ``cache``, sets ``cache.pos = prompt_lens`` and returns
         the logits of each row's last real position, [B, vocab_size]."""
@@ -287,10 +287,11 @@ class BertForPreTraining(Layer):
         cache.pos.copy_(lens_d)
         cache.max_len = int(lens.max())
         last = torch.arange(B, device=dev) * Sp + lens_d.long() - 1
-        return self._head(x.index_select(0, last))[:, :self.cfg.vocab_size]
+        logits = self._head(x.index_select(0, last))
+        return logits if _padded else logits[:, :self.cfg.vocab_size]
 
     @torch.no_grad()
-    def decode_step(self, ids_new, cache):
+    def decode_step(self, ids_new, cache, _padded=False):
         """One token per sequence (``ids_new`` [B]) at positions ``cache.pos``: every layer runs
         at B rows with ``ops.attention_decode`` against its cache, ``cache.pos`` advances by one
         on the device.  -> logits [B, vocab_size].  Nothing here reads the device."""
@@ -310,16 +311,25 @@ class BertForPreTraining(Layer):
         for i, layer in enumerate(self.layers):
             x = layer.decode(x, cache.k[i], cache.v[i], cache.pos, cache.max_len)
         cache.pos.add_(1)
-        return self._head(x)[:, :cfg.vocab_size]
+        logits = self._head(x)
+        return logits if _padded else logits[:, :cfg.vocab_size]
 
     def generate(self, input_ids, prompt_lens, max_new_tokens, temperature=0.0, top_k=0,
-                 eos_id=None, generator=None):
+                 eos_id=None, generator=None, top_p=1.0, seed=None, return_logprobs=False):
         """Continue the right-padded prompts [B, Sp] by ``max_new_tokens`` tokens -> int64
         [B, max_new_tokens].  Greedy at ``temperature == 0``; otherwise softmax sampling of
         ``logits / temperature`` over the ``top_k`` largest (all when 0) with ``generator``.  A row
         that has produced ``eos_id`` keeps producing it.  ``prompt_lens`` are CPU lengths: the one
-        host check (capacity) is made from them before the loop, which never reads the device."""
+        host check (capacity) is made from them before the loop, which never reads the device.
+
+        With an int ``seed`` every pick is one ``ops.sample_tokens`` call on the padded logits
+        (greedy included), counted by ``cache.pos``: the tokens are a function of the seed,
+        ``top_p`` (nucleus) filtering is available and ``return_logprobs=True`` also returns the
+        log-probability of every picked token, fp32 [B, max_new_tokens] (of the sampled token, also
+        where ``eos_id`` replaced it).  ``generator`` is not used then."""
         lens = self._check_prompts(input_ids, prompt_lens)
+        if seed is None and (top_p != 1.0 or return_logprobs):
+            raise ValueError("top_p and return_logprobs need the seeded path: pass seed=")
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be at least 1")
         need = int(lens.max()) + max_new_tokens
@@ -337,18 +347,24 @@ class BertForPreTraining(Layer):
                 out = torch.empty(input_ids.shape[0], max_new_tokens, dtype=torch.int64,
                                   device=dev)
                 done = torch.zeros(input_ids.shape[0], dtype=torch.bool, device=dev)
-                logits = self.prefill(input_ids, lens, cache)
+                fused = seed is not None
+                lps = torch.empty(out.shape, dtype=torch.float32, device=dev) if fused else None
+                logits = self.prefill(input_ids, lens, cache, _padded=fused)
                 for t in range(max_new_tokens):
-                    tok = _pick(logits, temperature, top_k, generator)
+                    if fused:
+                        tok, lps[:, t] = ops.sample_tokens(logits, seed, cache.pos, temperature,
+                                                           top_k, top_p, self.cfg.vocab_size)
+                    else:
+                        tok = _pick(logits, temperature, top_k, generator)
                     if eos_id is not None:
                         tok = torch.where(done, torch.full_like(tok, eos_id), tok)
                         done = done | (tok == eos_id)
                     out[:, t] = tok
                     if t + 1 < max_new_tokens:
-                        logits = self.decode_step(tok, cache)
+                        logits = self.decode_step(tok, cache, _padded=fused)
         finally:
             self.train(was_training)
-        return out
+        return (out, lps) if return_logprobs else out
 
 
 def _pick(logits, temperature, top_k, generator):

@@ -339,6 +339,20 @@ def kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads):
     return reference.kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads)
 
 
+def sample_tokens(logits, seed, counter, temperature=1.0, top_k=0, top_p=1.0, vocab=None):
+    """The next token of every logits row, filtered by top-k and top-p and drawn in one kernel.
+
+    ``logits`` [B, ld] (columns >= ``vocab`` are padding, never candidates), ``counter`` int32 [B]
+    on the logits' device (for example ``KVCache.pos``), ``seed`` an int in [0, 2^31).  The draw
+    is a pure function of (seed, counter[b], b) (``reference.sample_uniform``), so nothing reads
+    the device.  ``temperature == 0`` is greedy.  -> (tokens int64 [B], logprob fp32 [B]): the
+    log-probability of the token in the filtered, renormalised distribution (greedy: the plain
+    log-softmax).  The exact rule is ``reference.sample_details``.  A no-grad op.  Not fenced: it reads no variable."""
+    if _use_native(logits):
+        return _nlp().sample_tokens(logits, seed, counter, temperature, top_k, top_p, vocab)
+    return reference.sample_tokens(logits, seed, counter, temperature, top_k, top_p, vocab)
+
+
 def mlm_loss(logits, labels, weights=None, vocab=None):
     """Weighted masked-LM cross-entropy.  ``vocab``: the class count when the logits rows are
     padded past it (BERT's tied decoder runs on a vocabulary padded to a multiple of 64)."""
@@ -513,4 +527,5 @@ __all__ = [
     "dense_gelu_dense", "attention_qkv", "mlm_loss", "eval_rows", "in_top_k", "augment_images",
     "mlm_mask_tokens", "ema_update", "grad_accumulate", "augment_mix_images",
     "mixed_softmax_cross_entropy", "augment_rand_images", "attention_decode", "kv_cache_fill",
+    "sample_tokens",
 ]

@@ -346,6 +346,27 @@ def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=
     return out
 
 
+def sample_tokens(logits, seed, counter, temperature=1.0, top_k=0, top_p=1.0, vocab=None):
+    """csrc/kernels/sample.hip (see ``reference.sample_details``): one launch, nothing read from
+    the device."""
+    from . import reference
+    reference.no_grad_op("sample_tokens", logits)
+    B, V = reference.check_sample_args(logits, seed, counter, temperature, top_k, top_p, vocab)
+    if not logits.is_cuda or logits.dtype != _BF16:
+        raise ValueError("native sample_tokens takes bf16 device logits")
+    if logits.shape[1] % 8:
+        raise ValueError("native sample_tokens takes rows of a multiple of 8 columns")
+    if -(-V // 8) * 8 > _K.sample_max_keys(True):
+        raise ValueError(f"vocab {V} exceeds the kernel's {_K.sample_max_keys(True)} keys")
+    x = logits.detach().contiguous()
+    tokens = torch.empty(B, device=x.device, dtype=torch.int64)
+    logprob = torch.empty(B, device=x.device, dtype=torch.float32)
+    _K.sample_tokens(x.data_ptr(), counter.contiguous().data_ptr(), tokens.data_ptr(),
+                     logprob.data_ptr(), B, V, x.shape[1], int(seed), float(temperature),
+                     int(top_k), float(top_p), _st())
+    return tokens, logprob
+
+
 # ----------------------------------------------------------------------------- MLM loss
 class _MlmLoss(torch.autograd.Function):
     """``vocab``: the class count when the logits rows are padded past it (the tied decoder's

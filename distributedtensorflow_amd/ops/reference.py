@@ -227,6 +227,15 @@ def keep_mask(seed, idx, p):
     return h >= drop_threshold(p)
 
 
+def sample_uniform(seed, counter):
+    """The draw of ``sample_tokens``: row b of the int32 ``counter`` [B] gets
+    ``u = (fmix32(fmix32(b * 0x9E3779B1 + seed) + counter[b]) >> 8) * 2^-24`` (uint32 math), fp64."""
+    b = torch.arange(counter.numel(), device=counter.device, dtype=torch.int64)
+    h = _fmix32((b * 0x9E3779B1 + int(seed)) & _M32)
+    h = _fmix32((h + (counter.to(torch.int64) & _M32)) & _M32)
+    return (h >> 8).double() * 2.0 ** -24
+
+
 def _drop(x, p, seed, idx):
     if p <= 0:
         return x
@@ -393,6 +402,99 @@ def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=
     # select, not multiply: unwritten cache rows may hold anything
     v = torch.where(vis.unsqueeze(-1), v_cache.float(), torch.zeros((), device=pos.device))
     return torch.einsum("bhk,bhkd->bhd", prob, v).reshape(B, heads * 64).to(qkv_new.dtype)
+
+
+def check_sample_args(logits, seed, counter, temperature, top_k, top_p, vocab):
+    """The argument conditions of ``sample_tokens``, shared by both backends -> (B, vocab)."""
+    if logits.dim() != 2:
+        raise ValueError("logits must be [B, ld]")
+    B, ld = logits.shape
+    V = ld if vocab is None else int(vocab)
+    if not 0 < V <= ld:
+        raise ValueError(f"vocab {V} outside (0, {ld}]")
+    if not 0.0 < top_p <= 1.0:
+        raise ValueError(f"top_p {top_p} outside (0, 1]")
+    if top_k < 0:
+        raise ValueError(f"top_k {top_k} is negative")
+    if temperature < 0:
+        raise ValueError(f"temperature {temperature} is negative")
+    if not 0 <= int(seed) < 2 ** 31:
+        raise ValueError(f"seed {seed} outside [0, 2^31)")
+    if (not torch.is_tensor(counter) or counter.dtype != torch.int32
+            or tuple(counter.shape) != (B,) or counter.device != logits.device):
+        raise ValueError(f"counter must be int32 [{B}] on the logits' device")
+    return B, V
+
+
+def sample_details(logits, seed, counter, temperature=1.0, top_k=0, top_p=1.0, vocab=None,
+                   math=torch.float32):
+    """``sample_tokens`` with its intermediate quantities, in ``math`` precision on the logits
+    rounded to bf16 (the values the device stores) -> dict: ``tokens`` [B], ``logprob`` [B],
+    ``keep`` [B, V] (the final candidate set) and, when not greedy, ``keep_k`` [B, V] (what top-k
+    kept) and per row ``Z`` (final mass),
+    ``target`` (u Z), ``cdf_lo`` / ``cdf_hi`` (the running mass before / at the token), ``need``
+    (top_p times the mass top-k kept), ``s_at`` / ``s_above`` (the upper mass at the top-p
+    threshold key and at the next key above it; ``s_above`` is 0 at the largest key).
+
+    The rule: 16-bit keys of the bf16 bits (negatives flipped, others with the sign bit set) carry
+    the order; top-k keeps ``key >= k-th largest key``; top-p then keeps ``key >= t``, t the largest
+    key whose upper mass ``sum{m : key >= t}`` reaches ``fp32(top_p)`` times the kept mass, with
+    ``m = exp(z - zmax)``, ``z = x / temperature``; the token is the lowest kept index whose running
+    mass in index order exceeds ``u Z``; ``logprob = z_tok - zmax - log Z``.  ``temperature == 0``:
+    the lowest index of the largest key, its log-softmax over all classes at temperature 1."""
+    B, V = check_sample_args(logits, seed, counter, temperature, top_k, top_p, vocab)
+    xb = logits.detach()[:, :V].to(torch.bfloat16).contiguous()
+    bits = xb.view(torch.int16).to(torch.int64) & 0xFFFF
+    key = torch.where(bits >= 0x8000, ~bits & 0xFFFF, bits | 0x8000)
+    x = xb.to(math)
+    idx = torch.arange(V, device=x.device)
+    if temperature == 0:
+        top = key == key.max(1, keepdim=True).values
+        tok = torch.where(top, idx, V).min(1).values
+        lp = torch.log_softmax(x, 1).gather(1, tok.unsqueeze(1)).squeeze(1)
+        return {"tokens": tok, "logprob": lp, "keep": torch.ones_like(top)}
+    z = x / temperature
+    zmax = z.max(1, keepdim=True).values
+    m = torch.exp(z - zmax)
+    u = sample_uniform(seed, counter).to(math)
+    p32 = float(torch.tensor(top_p, dtype=torch.float32))
+    out = {k: [] for k in ("tokens", "logprob", "keep", "keep_k", "Z", "target", "cdf_lo", "cdf_hi", "need",
+                           "s_at", "s_above")}
+    for b in range(B):
+        k, mb = key[b], m[b]
+        keep = torch.ones(V, dtype=torch.bool, device=x.device)
+        if 0 < top_k < V:
+            keep = k >= torch.topk(k, top_k).values[-1]
+        need = p32 * (mb * keep).sum()
+        out["keep_k"].append(keep)
+        s_at, s_above = need / p32, torch.zeros((), dtype=math, device=x.device)
+        if top_p < 1.0:
+            uk, inv = torch.unique(k[keep], return_inverse=True)
+            mass = torch.zeros(uk.numel(), dtype=math, device=x.device).index_add_(0, inv, mb[keep])
+            upper = mass.flip(0).cumsum(0).flip(0)
+            j = int(torch.nonzero(upper >= need).max())
+            keep = keep & (k >= uk[j])
+            s_at = upper[j]
+            if j + 1 < uk.numel():
+                s_above = upper[j + 1]
+        mk = mb * keep
+        cum = mk.cumsum(0)
+        Z = cum[-1]
+        hit = keep & (cum > u[b] * Z)
+        tok = torch.where(hit, idx, V).min() if bool(hit.any()) else idx[keep].max()
+        for name, v in (("tokens", tok), ("logprob", z[b, tok] - zmax[b, 0] - torch.log(Z)),
+                        ("keep", keep), ("Z", Z), ("target", u[b] * Z), ("cdf_hi", cum[tok]),
+                        ("cdf_lo", cum[tok] - mk[tok]), ("need", need), ("s_at", s_at),
+                        ("s_above", s_above)):
+            out[name].append(v)
+    return {name: torch.stack(v) for name, v in out.items()}
+
+
+def sample_tokens(logits, seed, counter, temperature=1.0, top_k=0, top_p=1.0, vocab=None):
+    """One token per logits row -> (tokens int64 [B], logprob fp32 [B]); see ``sample_details``."""
+    no_grad_op("sample_tokens", logits)
+    d = sample_details(logits, seed, counter, temperature, top_k, top_p, vocab)
+    return d["tokens"], d["logprob"].float()
 
 
 def mlm_loss(logits, labels, weights=None, vocab=None):

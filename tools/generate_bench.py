@@ -6,6 +6,15 @@ causal forward over the whole prefix for every token and taking its last row.
 BERT-base, causal, greedy, random weights.  Both arms run in this process in alternation; one JSON
 line with the median seconds and tokens per second of each, and the route the M = batch GEMMs of a
 decode step take (``_dense_gemm_native``: the persistent MFMA GEMM, else ``F.linear``).
+
+    python tools/generate_bench.py --sample [--rounds 3] [--new 128]
+
+``--sample`` times the pick of the next token instead.  Per call: the fused ``ops.sample_tokens``
+(csrc/kernels/sample.hip) on the padded [B, 30528] bf16 logits against ``_pick`` on their
+``[:, :30522]`` slice copy (what ``generate`` without a seed runs per token), B = 8 and 64, the arms
+alternating in one process, device events around 20 calls each, medians of 15 such windows.  End to
+end: tokens per second of ``generate(seed=...)`` against ``generate(generator=...)`` at
+temperature 0.8, top_k 50.  One JSON line per measurement.
 """
 import argparse
 import json
@@ -16,6 +25,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from distributedtensorflow_amd import ops  # noqa: E402
 from distributedtensorflow_amd.models import bert  # noqa: E402
 from distributedtensorflow_amd.ops import native  # noqa: E402
 
@@ -36,13 +46,74 @@ def recompute(model, prompt, plen, n_new):
     return seq[:, plen:]
 
 
+def _med(v):
+    return sorted(v)[len(v) // 2]
+
+
+def sample_bench(a):
+    V, ld, calls, windows = 30522, 30528, 20, 15
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    for B in (8, 64):
+        logits = torch.zeros(B, ld, device="cuda")
+        logits[:, :V] = 3.0 * torch.randn(B, V, device="cuda", generator=gen)
+        logits = logits.bfloat16()
+        pos = torch.arange(B, device="cuda", dtype=torch.int32)
+        for T, k, p in ((0.0, 0, 1.0), (0.8, 0, 1.0), (0.8, 50, 1.0), (0.8, 50, 0.9),
+                        (0.8, 0, 0.9)):
+            arms = {"fused": lambda: ops.sample_tokens(logits, 7, pos, T, k, p, V)}
+            if p == 1.0:                                   # _pick has no top_p
+                arms["pick"] = lambda: bert._pick(logits[:, :V], T, k, gen)
+            us = {n: [] for n in arms}
+            for w in range(windows + 1):                   # window 0 warms both arms up
+                for n, fn in arms.items():
+                    e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+                    e0.record()
+                    for _ in range(calls):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if w:
+                        us[n].append(e0.elapsed_time(e1) * 1e3 / calls)
+            rec = {"probe": "sample_pick", "B": B, "V": V, "temperature": T, "top_k": k, "top_p": p}
+            for n in arms:
+                rec[f"{n}_us"] = round(_med(us[n]), 2)
+                rec[f"{n}_spread_us"] = [round(min(us[n]), 2), round(max(us[n]), 2)]
+            print(json.dumps(rec), flush=True)
+    torch.manual_seed(0)
+    model = bert.bert_base(causal=True).cuda().eval()
+    B, P = 8, 64
+    prompt = torch.randint(1, V, (B, P), device="cuda")
+    lens = torch.full((B,), P)
+    arms = {"seeded": lambda: model.generate(prompt, lens, a.new, 0.8, 50, seed=7),
+            "generator": lambda: model.generate(prompt, lens, a.new, 0.8, 50, generator=gen)}
+    times = {n: [] for n in arms}
+    for r in range(a.rounds + 1):
+        for n, fn in arms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if r:
+                times[n].append(time.perf_counter() - t0)
+    rec = {"probe": "generate_sampled", "model": "bert_base", "B": B, "prompt": P, "new": a.new,
+           "temperature": 0.8, "top_k": 50, "rounds": a.rounds}
+    for n in arms:
+        rec[f"{n}_s"] = round(_med(times[n]), 4)
+        rec[f"{n}_spread_s"] = [round(min(times[n]), 4), round(max(times[n]), 4)]
+        rec[f"{n}_tokens_per_sec"] = round(B * a.new / _med(times[n]), 1)
+    print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--prompt", type=int, default=64)
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--sample", action="store_true")
     a = ap.parse_args()
+    if a.sample:
+        return sample_bench(a)
     torch.manual_seed(0)
     model = bert.bert_base(causal=True).cuda().eval()
     B, P = a.batch, a.prompt
