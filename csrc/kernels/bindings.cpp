@@ -909,6 +909,18 @@ PYBIND11_MODULE(_dtf_hip, m) {
     check_launch("kv_cache_fill");
   }, py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("B"), py::arg("S"),
      py::arg("H"), py::arg("C"), py::arg("st"));
+  m.def("attn_append_splits", &dtf_attn_append_splits);
+  m.def("attn_append_ws_floats", &dtf_attn_append_ws_floats);
+  m.def("attn_append", [](uintptr_t qkv_new, uintptr_t pos, uintptr_t n_new, uintptr_t k_cache,
+                          uintptr_t v_cache, uintptr_t out, uintptr_t ws, int B, int T, int H,
+                          int C, int max_len, int splits, float scale, uintptr_t st) {
+    dtf_attn_append(P<const bf16_t>(qkv_new), P<const int>(pos), P<const int>(n_new),
+                    P<bf16_t>(k_cache), P<bf16_t>(v_cache), P<bf16_t>(out), P<float>(ws), B, T, H,
+                    C, max_len, splits, scale, S(st));
+    check_launch("attn_append");
+  }, py::arg("qkv_new"), py::arg("pos"), py::arg("n_new"), py::arg("k_cache"), py::arg("v_cache"),
+     py::arg("out"), py::arg("ws"), py::arg("B"), py::arg("T"), py::arg("H"), py::arg("C"),
+     py::arg("max_len"), py::arg("splits"), py::arg("scale"), py::arg("st"));
   m.def("sample_max_keys", &dtf_sample_max_keys, py::arg("large"));
   m.def("sample_tokens", [](uintptr_t logits, uintptr_t counter, uintptr_t tokens,
                             uintptr_t logprob, int B, int V, int ld, uint32_t seed,

@@ -455,6 +455,24 @@ void dtf_attn_decode(const bf16_t* qkv_new, const int* pos, bf16_t* k_cache, bf1
 void dtf_kv_cache_fill(const bf16_t* qkv, bf16_t* k_cache, bf16_t* v_cache, int B, int S, int H,
                        int C, hipStream_t st);
 
+// ---- attn_append.hip: T new tokens per sequence against the [B, H, C, 64] caches
+struct AttnAppendArgs {
+  const bf16_t* qkv_new;   // [B*T, 3*H*64]
+  const int* pos;          // [B], device: the cache row new token 0 takes
+  const int* n_new;        // [B], device: new tokens of the row (null: T everywhere)
+  bf16_t* k_cache;         // [B, H, C, 64]
+  bf16_t* v_cache;
+  bf16_t* out;             // [B*T, H*64]
+  float* ws;               // [B, H, T, splits, 68] partials (splits > 1)
+  int B, T, H, C, splits;
+  float c;                 // scale * log2(e)
+};
+int dtf_attn_append_splits(int B, int H, int T, int max_len);
+long dtf_attn_append_ws_floats(int B, int H, int T, int splits);
+void dtf_attn_append(const bf16_t* qkv_new, const int* pos, const int* n_new, bf16_t* k_cache,
+                     bf16_t* v_cache, bf16_t* out, float* ws, int B, int T, int H, int C,
+                     int max_len, int splits, float scale, hipStream_t st);
+
 // ---- sample.hip: top-k / top-p filtering and the draw of one token per logits row, one kernel
 struct SampleArgs {
   const bf16_t* logits;    // [B, ld], columns >= V are padding

@@ -162,6 +162,9 @@ def build_parser():
     p.add_argument("--generate_top_p", type=float, default=1.0,
                    help="nucleus sampling: the smallest set of the largest logits with this share "
                         "of the mass; needs --generate_seed")
+    p.add_argument("--generate_prefill_chunk", type=int, default=None, metavar="T",
+                   help="feed the prompt of --generate through the KV cache T tokens at a time "
+                        "(append attention) instead of one causal forward")
     p.add_argument("--generate_seed", type=int, default=None,
                    help="pick every token with the fused on-device sampler, reproducible from "
                         "this seed (default: torch's generator seeded with --seed)")
@@ -574,6 +577,8 @@ def _generate(args, model, device, batch):
         kw = {"seed": args.generate_seed}
     if args.generate_top_p != 1.0:
         kw["top_p"] = args.generate_top_p
+    if args.generate_prefill_chunk is not None:
+        kw["prefill_chunk"] = args.generate_prefill_chunk
     try:
         if cuda:
             torch.cuda.synchronize()

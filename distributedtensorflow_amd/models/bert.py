@@ -151,6 +151,15 @@ class BertLayer(nn.Module):
                                    max_len=max_len)
         return self._after_attention(x, ctx)
 
+    def extend(self, x, k_cache, v_cache, pos, n_new, T, max_len=None):
+        """T new tokens per sequence (x [B*T, H]), the first ``n_new[b]`` of them real, at
+        positions ``pos[b] ..`` against this layer's cache, which takes their keys and values in
+        place (``ops.attention_append``)."""
+        qkv = ops.dense(x, self.qkv_kernel, self.qkv_bias, impl=BERT_GEMM)
+        ctx = ops.attention_append(qkv, k_cache, v_cache, pos, self.cfg.num_attention_heads,
+                                   n_new=n_new, max_len=max_len)
+        return self._after_attention(x, ctx)
+
     def _after_attention(self, x, ctx):
         cfg = self.cfg
         a = self.attn_out.gemm(ctx)
@@ -272,14 +281,30 @@ class BertForPreTraining(Layer):
         return lens
 
     @torch.no_grad()
-    def prefill(self, input_ids, prompt_lens, cache, _padded=False):
+    def prefill(self, input_ids, prompt_lens, cache, _padded=False, chunk=None):
         """The causal forward over the right-padded prompts [B, Sp] (``prompt_lens``: CPU lengths
         in [1, Sp]): fills every layer of ``cache``, sets ``cache.pos = prompt_lens`` and returns
-        the logits of each row's last real position, [B, vocab_size]."""
+        the logits of each row's last real position, [B, vocab_size].
+
+        ``chunk=T``: the prompt goes through :meth:`extend` in ``ceil(Sp / T)`` pieces from an
+        empty cache instead, piece c with ``n_new = clamp(prompt_lens - c T, 0, T)``: activation
+        memory is that of T tokens per row and Sp needs no padding to a multiple of 64."""
         lens = self._check_prompts(input_ids, prompt_lens)
         B, Sp = input_ids.shape
         if B != cache.batch or Sp > cache.capacity:
             raise ValueError(f"cache is for batch {cache.batch}, capacity {cache.capacity}")
+        if chunk is not None:
+            T = int(chunk)
+            if T < 1:
+                raise ValueError("chunk must be at least 1")
+            cache.reset()
+            piece_of = ((lens - 1) // T).to(input_ids.device).view(B, 1)
+            logits = None
+            for c in range(-(-Sp // T)):
+                part = self.extend(input_ids[:, c * T:(c + 1) * T].contiguous(), cache,
+                                   (lens - c * T).clamp(0, min(T, Sp - c * T)), _padded=_padded)
+                logits = part if logits is None else torch.where(piece_of == c, part, logits)
+            return logits
         dev = input_ids.device
         lens_d = lens.to(dev)
         am = (torch.arange(Sp, device=dev).unsqueeze(0) < lens_d.unsqueeze(1)).long()
@@ -314,8 +339,53 @@ class BertForPreTraining(Layer):
         logits = self._head(x)
         return logits if _padded else logits[:, :cfg.vocab_size]
 
+    @torch.no_grad()
+    def extend(self, ids_new, cache, n_new=None, all_logits=False, _padded=False):
+        """T new tokens per sequence (``ids_new`` [B, T], the first ``n_new[b]`` of row b real;
+        ``n_new``: CPU lengths in [0, T], default T everywhere) at positions ``cache.pos[b] ..``:
+        every layer runs at B*T rows with ``ops.attention_append`` against its cache and
+        ``cache.pos`` advances by ``n_new`` on the device.  -> the logits of each row's last new
+        token [B, vocab_size], or of all T positions [B, T, vocab_size] with ``all_logits``.
+
+        A row with ``n_new == 0`` and, with ``all_logits``, the positions at or past ``n_new[b]``
+        return logits that callers must not use.  The capacity is checked on the host against
+        ``cache.max_len``, the host's bound on ``cache.pos`` (``cache.reset()`` and ``prefill``
+        set it); nothing here reads the device."""
+        cfg = self.cfg
+        if not cfg.causal:
+            raise ValueError("incremental decoding needs a causal model (BertConfig(causal=True))")
+        B, T = ids_new.shape
+        n = torch.full((B,), T) if n_new is None else torch.as_tensor(n_new).reshape(-1).cpu()
+        if B != cache.batch or n.numel() != B or int(n.min()) < 0 or int(n.max()) > T:
+            raise ValueError(f"n_new must hold {cache.batch} lengths in [0, {T}]")
+        if cache.max_len + int(n.max()) > cache.capacity:
+            raise ValueError(f"{cache.max_len} cached + {int(n.max())} new tokens exceed the "
+                             f"capacity {cache.capacity}")
+        dev, dtype = ids_new.device, cache.k.dtype
+        n_d = n.to(dev, torch.int32)
+        # word[id] + pos[p] + type[0] as decode_step forms it, p = cache.pos[b] + i
+        p = (cache.pos.long().view(B, 1) + torch.arange(T, device=dev).view(1, T)).reshape(-1)
+        p = p.clamp(max=cfg.max_position_embeddings - 1)
+        s = (self.word_embeddings[ids_new.reshape(-1)].to(dtype).float()
+             + self.position_embeddings[p].to(dtype).float()
+             + self.token_type_embeddings[0].to(dtype).float()).to(dtype)
+        x = ops.bias_dropout_add_layer_norm(s, None, None, self.emb_ln.gamma, self.emb_ln.beta,
+                                            0.0, False, cfg.layer_norm_eps)
+        launch_len = max(T, min(cache.max_len + T, cache.capacity))
+        for i, layer in enumerate(self.layers):
+            x = layer.extend(x, cache.k[i], cache.v[i], cache.pos, n_d, T, launch_len)
+        cache.pos.add_(n_d)
+        cache.max_len = min(cache.max_len + int(n.max()), cache.capacity)
+        if not all_logits:
+            last = torch.arange(B, device=dev) * T + (n_d.long() - 1).clamp(min=0)
+            x = x.index_select(0, last)
+        logits = self._head(x)
+        logits = logits if _padded else logits[:, :cfg.vocab_size]
+        return logits.view(B, T, -1) if all_logits else logits
+
     def generate(self, input_ids, prompt_lens, max_new_tokens, temperature=0.0, top_k=0,
-                 eos_id=None, generator=None, top_p=1.0, seed=None, return_logprobs=False):
+                 eos_id=None, generator=None, top_p=1.0, seed=None, return_logprobs=False,
+                 prefill_chunk=None):
         """Continue the right-padded prompts [B, Sp] by ``max_new_tokens`` tokens -> int64
         [B, max_new_tokens].  Greedy at ``temperature == 0``; otherwise softmax sampling of
         ``logits / temperature`` over the ``top_k`` largest (all when 0) with ``generator``.  A row
@@ -326,7 +396,9 @@ class BertForPreTraining(Layer):
         (greedy included), counted by ``cache.pos``: the tokens are a function of the seed,
         ``top_p`` (nucleus) filtering is available and ``return_logprobs=True`` also returns the
         log-probability of every picked token, fp32 [B, max_new_tokens] (of the sampled token, also
-        where ``eos_id`` replaced it).  ``generator`` is not used then."""
+        where ``eos_id`` replaced it).  ``generator`` is not used then.
+
+        ``prefill_chunk=T`` feeds the prompt through ``prefill(chunk=T)``, T tokens at a time."""
         lens = self._check_prompts(input_ids, prompt_lens)
         if seed is None and (top_p != 1.0 or return_logprobs):
             raise ValueError("top_p and return_logprobs need the seeded path: pass seed=")
@@ -349,7 +421,11 @@ class BertForPreTraining(Layer):
                 done = torch.zeros(input_ids.shape[0], dtype=torch.bool, device=dev)
                 fused = seed is not None
                 lps = torch.empty(out.shape, dtype=torch.float32, device=dev) if fused else None
-                logits = self.prefill(input_ids, lens, cache, _padded=fused)
+                if prefill_chunk is None:
+                    logits = self.prefill(input_ids, lens, cache, _padded=fused)
+                else:
+                    logits = self.prefill(input_ids, lens, cache, _padded=fused,
+                                          chunk=prefill_chunk)
                 for t in range(max_new_tokens):
                     if fused:
                         tok, lps[:, t] = ops.sample_tokens(logits, seed, cache.pos, temperature,
@@ -399,6 +475,12 @@ class KVCache:
         self.v = torch.zeros(shape, device=device, dtype=dtype)
         self.pos = torch.zeros(batch, device=device, dtype=torch.int32)
         self.batch, self.capacity, self.max_len = batch, C, C
+
+    def reset(self):
+        """An empty cache: ``pos = 0`` on the device and ``max_len = 0`` (the stored keys and
+        values stay; nothing reads rows at or past ``pos``)."""
+        self.pos.zero_()
+        self.max_len = 0
 
 
 def bert_base(**kw) -> BertForPreTraining:

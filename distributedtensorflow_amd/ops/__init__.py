@@ -331,6 +331,27 @@ def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=
                                       splits)
 
 
+def attention_append(qkv_new, k_cache, v_cache, pos, heads, n_new=None, scale=None, max_len=None,
+                     splits=0):
+    """Append attention: T new tokens per sequence against a key / value cache -- chunked
+    prefill, extending a conversation, scoring drafted tokens.
+
+    ``qkv_new`` [B*T, 3*heads*64] holds the fused projections of T new tokens per row, the caches
+    are [B, heads, C, 64] (C % 64 == 0), ``pos`` int32 [B] is the cache row new token 0 takes and
+    ``n_new`` int32 [B] (default: T everywhere) how many of the T tokens are real.  Per row, with
+    ``p0 = clamp(pos, 0, C)`` and ``n = clamp(n_new, 0, min(T, C - p0))``: cache rows p0 .. p0+n-1
+    take the new K / V IN PLACE, query i < n attends keys 0 .. p0+i (causal among the new tokens),
+    output rows i >= n are exactly zero -> [B*T, heads*64].  ``pos`` is NOT advanced.  Cache rows
+    at or past p0+n may hold anything and are never used.  Native: ``pos`` and ``n_new`` are read
+    on the device only; ``max_len`` (an upper bound on pos + T, default C) and ``splits``
+    (0 = choose) size the launch.  A no-grad op.  Not fenced: it reads no variable."""
+    if _use_native(qkv_new):
+        return _nlp().attention_append(qkv_new, k_cache, v_cache, pos, heads, n_new, scale,
+                                       max_len, splits)
+    return reference.attention_append(qkv_new, k_cache, v_cache, pos, heads, n_new, scale,
+                                      max_len, splits)
+
+
 def kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads):
     """Copy the K and V thirds of a prefill's fused QKV matrix [batch*seq_len, 3*heads*64] into
     rows 0 .. seq_len-1 of the [batch, heads, C, 64] caches, in place.  A no-grad op.  Not fenced: it reads no variable."""
@@ -527,5 +548,5 @@ __all__ = [
     "dense_gelu_dense", "attention_qkv", "mlm_loss", "eval_rows", "in_top_k", "augment_images",
     "mlm_mask_tokens", "ema_update", "grad_accumulate", "augment_mix_images",
     "mixed_softmax_cross_entropy", "augment_rand_images", "attention_decode", "kv_cache_fill",
-    "sample_tokens",
+    "sample_tokens", "attention_append",
 ]

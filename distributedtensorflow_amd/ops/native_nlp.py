@@ -346,6 +346,28 @@ def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=
     return out
 
 
+def attention_append(qkv_new, k_cache, v_cache, pos, heads, n_new=None, scale=None, max_len=None,
+                     splits=0):
+    """csrc/kernels/attn_append.hip (see ``reference.attention_append``).  ``pos`` and ``n_new``
+    stay on the device: nothing here reads them."""
+    from . import reference
+    reference.no_grad_op("attention_append", qkv_new, k_cache, v_cache)
+    B, T, C, max_len = reference.check_append_args(qkv_new, k_cache, v_cache, pos, heads, n_new,
+                                                   max_len, splits)
+    _check_decode_tensors("attention_append", qkv_new, k_cache, v_cache)
+    scale = AD ** -0.5 if scale is None else scale
+    q = qkv_new.detach().contiguous()
+    splits = splits or _K.attn_append_splits(B, heads, T, max_len)
+    nws = _K.attn_append_ws_floats(B, heads, T, splits)
+    ws = torch.empty(nws, device=q.device, dtype=torch.float32) if nws else None
+    out = torch.empty(B * T, heads * AD, device=q.device, dtype=_BF16)
+    n_new = None if n_new is None else n_new.contiguous()
+    _K.attn_append(q.data_ptr(), pos.contiguous().data_ptr(), _p(n_new), k_cache.data_ptr(),
+                   v_cache.data_ptr(), out.data_ptr(), _p(ws), B, T, heads, C, max_len, splits,
+                   float(scale), _st())
+    return out
+
+
 def sample_tokens(logits, seed, counter, temperature=1.0, top_k=0, top_p=1.0, vocab=None):
     """csrc/kernels/sample.hip (see ``reference.sample_details``): one launch, nothing read from
     the device."""

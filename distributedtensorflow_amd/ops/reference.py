@@ -404,6 +404,70 @@ def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=
     return torch.einsum("bhk,bhkd->bhd", prob, v).reshape(B, heads * 64).to(qkv_new.dtype)
 
 
+def check_append_args(qkv_new, k_cache, v_cache, pos, heads, n_new, max_len, splits):
+    """The shape / dtype conditions of ``attention_append``, shared by both backends ->
+    (B, T, capacity, max_len)."""
+    if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[3] != 64:
+        raise ValueError("k_cache and v_cache must both be [B, heads, capacity, 64]")
+    B, H, C, D = k_cache.shape
+    if H != heads:
+        raise ValueError(f"caches hold {H} heads, not {heads}")
+    if (qkv_new.dim() != 2 or qkv_new.shape[1] != 3 * H * D or qkv_new.shape[0] < B
+            or qkv_new.shape[0] % B):
+        raise ValueError(f"qkv_new must be [{B} * T, {3 * H * D}], got {tuple(qkv_new.shape)}")
+    T = qkv_new.shape[0] // B
+    if C < 64 or C % 64:
+        raise ValueError("cache capacity must be a multiple of 64, at least 64")
+    for name, t in (("pos", pos), ("n_new", n_new)):
+        if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (B,)
+                              or t.device != qkv_new.device):
+            raise ValueError(f"{name} must be int32 [{B}] on qkv_new's device")
+    if not (qkv_new.dtype == k_cache.dtype == v_cache.dtype):
+        raise ValueError("qkv_new and the caches must share one dtype")
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise ValueError("the caches must be contiguous")
+    max_len = C if max_len is None else int(max_len)
+    if not T <= max_len <= C:
+        raise ValueError(f"max_len must lie in [T = {T}, capacity = {C}]")
+    if splits < 0 or splits > -(-max_len // 64):
+        raise ValueError(f"splits {splits} exceeds the {-(-max_len // 64)} tiles of max_len")
+    return B, T, C, max_len
+
+
+def attention_append(qkv_new, k_cache, v_cache, pos, heads, n_new=None, scale=None, max_len=None,
+                     splits=0):
+    """T new tokens per sequence against the caches.  Per row b, with p0 = clamp(pos[b], 0, C) and
+    n = clamp(n_new[b] (default T), 0, min(T, C - p0)): the K / V of new tokens 0 .. n-1 go to
+    cache rows p0 .. p0+n-1, query i < n attends keys 0 .. p0+i, output rows i >= n are zero.
+    fp32 math on the stored values; ``max_len`` and ``splits`` only size the native launch."""
+    no_grad_op("attention_append", qkv_new, k_cache, v_cache)
+    B, T, C, _ = check_append_args(qkv_new, k_cache, v_cache, pos, heads, n_new, max_len, splits)
+    scale = 64 ** -0.5 if scale is None else scale
+    dev = qkv_new.device
+    x = qkv_new.detach().view(B, T, 3, heads, 64)
+    p0 = pos.long().clamp(0, C)
+    n = (torch.full_like(p0, T) if n_new is None else n_new.long()).clamp(min=0)
+    n = torch.minimum(n, (C - p0).clamp(max=T))
+    i = torch.arange(T, device=dev)
+    live = i.view(1, T) < n.view(B, 1)                                   # [B, T]
+    b_idx, t_idx = live.nonzero(as_tuple=True)
+    rows = p0[b_idx] + t_idx
+    k_cache[b_idx, :, rows] = x[b_idx, t_idx, 1]
+    v_cache[b_idx, :, rows] = x[b_idx, t_idx, 2]
+    s = torch.einsum("bthd,bhkd->bhtk", x[:, :, 0].float(), k_cache.float()) * scale
+    last = (p0.view(B, 1) + i.view(1, T)).view(B, 1, T, 1)
+    vis = (torch.arange(C, device=dev).view(1, 1, 1, C) <= last) & live.view(B, 1, T, 1)
+    # select, not multiply: hidden scores and unwritten cache rows may hold anything
+    s = torch.where(vis, s, torch.full_like(s, float("-inf")))
+    e = torch.where(vis, torch.exp(s - s.amax(-1, keepdim=True).clamp_min(-3e38)),
+                    torch.zeros_like(s))
+    prob = e / e.sum(-1, keepdim=True).clamp_min(1e-30)                  # a dead row: all zeros
+    keys = (torch.arange(C, device=dev).view(1, C) < (p0 + n).view(B, 1)).view(B, 1, C, 1)
+    v = torch.where(keys, v_cache.float(), torch.zeros((), device=dev))
+    out = torch.einsum("bhtk,bhkd->bthd", prob, v)
+    return out.reshape(B * T, heads * 64).to(qkv_new.dtype)
+
+
 def check_sample_args(logits, seed, counter, temperature, top_k, top_p, vocab):
     """The argument conditions of ``sample_tokens``, shared by both backends -> (B, vocab)."""
     if logits.dim() != 2:

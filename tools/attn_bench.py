@@ -18,6 +18,13 @@ alternation; every call takes the next of a ring of caches (512 MB in all, at mo
 the larger shapes stream from HBM rather than from a cache that one call has just filled.  One
 JSON line per shape: median time, spread, the bytes the algorithm must move (K and V once,
 ``2 * len * 128 * B * H``, plus the fp32 partials written and read back) and bytes / time.
+
+``--append`` times the append-attention kernels (csrc/kernels/attn_append.hip): T in {8, 16, 64,
+128} new tokens that bring a cache to ``len`` keys, same B, len and cache ring.  Arms, alternating
+in this process: ``attention_append`` with the launcher's ``splits``; T successive
+``attention_decode`` calls; the causal forward over all ``len`` tokens (what a caller without the
+kernel recomputes); and at B = 1 explicit ``splits`` 1 / 2 / 4 / 8, the evidence for the split
+threshold.  One JSON line per shape with the median and spread of each arm in microseconds.
 """
 import argparse
 import json
@@ -133,10 +140,73 @@ def decode_main(a):
             print(json.dumps(rec), flush=True)
 
 
+def append_main(a):
+    H, dev = a.heads, "cuda"
+    st = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    for B in (1, 8, 64):
+        for n in (128, 512, 2048):
+            kv_bytes = 2 * n * 128 * B * H
+            ring = max(2, min(64, (512 << 20) // kv_bytes))
+            g = torch.Generator(device=dev).manual_seed(n + B)
+            kc = (torch.randn(ring, B, H, n, 64, device=dev, generator=g) * 0.5).to(torch.bfloat16)
+            vc = torch.randn(ring, B, H, n, 64, device=dev, generator=g).to(torch.bfloat16)
+            qkv = (torch.randn(B * n, 3 * H * 64, device=dev, generator=g) * 0.5).to(torch.bfloat16)
+            lse = torch.empty(B * H * n, device=dev)
+            for T in (8, 16, 64, 128):
+                new = qkv.view(B, n, -1)[:, n - T:]
+                steps = new.transpose(0, 1).contiguous()            # [T, B, 3*H*64]
+                new = new.reshape(B * T, -1).contiguous()
+                pos = torch.full((B,), n - T, device=dev, dtype=torch.int32)
+                pos_t = [pos + i for i in range(T)]
+                out = torch.empty(B * n, H * 64, device=dev, dtype=torch.bfloat16)
+                auto = _K.attn_append_splits(B, H, T, n)
+                dsp = _K.attn_decode_splits(B, H, n)
+                ws = torch.empty(max(1, _K.attn_append_ws_floats(B, H, T, max(auto, 8)),
+                                     _K.attn_decode_ws_floats(B, H, dsp)), device=dev)
+                turn = [0]
+
+                def append(splits):
+                    i = turn[0] = (turn[0] + 1) % ring
+                    _K.attn_append(new.data_ptr(), pos.data_ptr(), 0, kc[i].data_ptr(),
+                                   vc[i].data_ptr(), out.data_ptr(), ws.data_ptr(), B, T, H, n, n,
+                                   splits, 0.125, st())
+
+                def decode():
+                    i = turn[0] = (turn[0] + 1) % ring
+                    for t in range(T):
+                        _K.attn_decode(steps[t].data_ptr(), pos_t[t].data_ptr(), kc[i].data_ptr(),
+                                       vc[i].data_ptr(), out.data_ptr(), ws.data_ptr(), B, H, n, n,
+                                       dsp, 0.125, st())
+
+                def forward():                                       # n % 64 == 0: it fits
+                    _K.attn_fwd(qkv.data_ptr(), 0, out.data_ptr(), lse.data_ptr(), B, n, H, 0.125,
+                                0.0, 1234, st(), 0, 1)
+
+                arms = {"append": lambda: append(auto), "decode_x_T": decode,
+                        "causal_forward": forward}
+                # the split threshold's evidence: explicit splits at the launch-bound batch
+                for sp in ((1, 2, 4, 8) if B == 1 else (1,)):
+                    if sp != auto and sp <= n // 64:
+                        arms[f"append_splits{sp}"] = lambda sp=sp: append(sp)
+                t = {k: [] for k in arms}
+                for _ in range(a.rounds):
+                    for k, fn in arms.items():
+                        t[k].append(timeit(fn, a.iters))
+                rec = {"probe": "attn_append", "B": B, "H": H, "T": T, "len": n, "ring": ring,
+                       "rounds": a.rounds, "iters": a.iters, "splits_auto": auto}
+                for k in arms:
+                    rec[f"{k}_us"] = round(med(t[k]) * 1e3, 2)
+                    rec[f"{k}_spread_us"] = [round(min(t[k]) * 1e3, 2), round(max(t[k]) * 1e3, 2)]
+                print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--decode", action="store_true",
                     help="time the incremental-decoding kernel (see above)")
+    ap.add_argument("--append", action="store_true",
+                    help="time the append-attention kernel against its alternatives (see above)")
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--seq", type=int, default=128)
     ap.add_argument("--heads", type=int, default=12)
@@ -149,6 +219,8 @@ def main():
         return causal_main(a)
     if a.decode:
         return decode_main(a)
+    if a.append:
+        return append_main(a)
     B, S, H, D = a.batch, a.seq, a.heads, 64
     dev = "cuda"
     g = torch.Generator(device=dev).manual_seed(0)

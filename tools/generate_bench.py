@@ -15,6 +15,12 @@ decode step take (``_dense_gemm_native``: the persistent MFMA GEMM, else ``F.lin
 alternating in one process, device events around 20 calls each, medians of 15 such windows.  End to
 end: tokens per second of ``generate(seed=...)`` against ``generate(generator=...)`` at
 temperature 0.8, top_k 50.  One JSON line per measurement.
+
+    python tools/generate_bench.py --prefill_chunk 64 [--batch 8] [--rounds 3]
+
+``--prefill_chunk T`` times the prefill of a 512-token prompt in one causal forward against
+``prefill(chunk=T)`` (append attention, T tokens at a time), alternating in one process, with the
+peak of ``torch.cuda.max_memory_allocated`` of each.
 """
 import argparse
 import json
@@ -104,8 +110,44 @@ def sample_bench(a):
     print(json.dumps(rec), flush=True)
 
 
+def prefill_bench(a):
+    """One-shot against chunked prefill of a 512-token prompt: median time and the peak of
+    ``torch.cuda.max_memory_allocated`` above what is allocated before the call."""
+    torch.manual_seed(0)
+    model = bert.bert_base(causal=True).cuda().eval()
+    B, P, T = a.batch, 512, a.prefill_chunk
+    prompt = torch.randint(1, 30522, (B, P), device="cuda")
+    lens = torch.full((B,), P)
+    cache = bert.KVCache(model.cfg, B, P, "cuda")
+    arms = {"one_shot": lambda: model.prefill(prompt, lens, cache),
+            "chunked": lambda: model.prefill(prompt, lens, cache, chunk=T)}
+    times, peak, outs = {k: [] for k in arms}, {}, {}
+    for r in range(a.rounds + 1):                     # round 0 warms both arms up
+        for k, fn in arms.items():
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            t0 = time.perf_counter()
+            outs[k] = fn()
+            torch.cuda.synchronize()
+            if r:
+                times[k].append(time.perf_counter() - t0)
+                peak[k] = torch.cuda.max_memory_allocated() - base
+    rec = {"probe": "prefill_chunk", "model": "bert_base", "B": B, "prompt": P, "chunk": T,
+           "rounds": a.rounds,
+           "same_argmax": float((outs["one_shot"].argmax(-1) == outs["chunked"].argmax(-1))
+                                .float().mean())}
+    for k in arms:
+        rec[f"{k}_ms"] = round(_med(times[k]) * 1e3, 3)
+        rec[f"{k}_spread_ms"] = [round(min(times[k]) * 1e3, 3), round(max(times[k]) * 1e3, 3)]
+        rec[f"{k}_peak_MB"] = round(peak[k] / 2 ** 20, 1)
+    print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--prefill_chunk", type=int, default=0, metavar="T",
+                    help="time prefill(chunk=T) against the one-shot prefill of 512 tokens")
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--prompt", type=int, default=64)
     ap.add_argument("--new", type=int, default=128)
@@ -114,6 +156,8 @@ def main():
     a = ap.parse_args()
     if a.sample:
         return sample_bench(a)
+    if a.prefill_chunk:
+        return prefill_bench(a)
     torch.manual_seed(0)
     model = bert.bert_base(causal=True).cuda().eval()
     B, P = a.batch, a.prompt
