@@ -45,9 +45,15 @@
 //     SELECTED to -inf (copes with NaN in K), but P V is an MFMA and 0 x NaN is NaN, so K and V rows
 //     >= p0 + n are zero-filled on the way into LDS (they are never loaded).
 //   * Query lanes >= T load nothing (zeros) and store nothing.
+//   * The FP8 cache (dtf_attn_append_f8; format and helpers in kv_f8.h) is the template parameter
+//     F8 of the same kernel.  Its copy quantises (kv_cache_append_f8_kernel); its staging loads 16
+//     bytes and the row's scale and writes their 16 exactly dequantised bf16 into the same LDS
+//     tile (half the global traffic, half the staging steps).  From LDS on nothing differs, so it
+//     computes the bf16 kernel's function of the dequantised cache.
 #include <stdexcept>
 #include <string>
 
+#include "kv_f8.h"
 #include "launch.h"
 
 namespace {
@@ -119,7 +125,38 @@ __global__ void __launch_bounds__(256) kv_cache_append_kernel(const AttnAppendAr
   *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
 }
 
-template <int QT>
+// The same copy into an FP8 cache (kv_f8.h): one thread per 16 output bytes (32 B of bf16 in), the
+// row maximum over the 4 lanes of a row by shuffles, then the scale, then the bytes.  A row's 4
+// lanes share t and b, so they leave together; rows outside p0 .. p0 + n - 1 and their scales are
+// not touched.
+__global__ void __launch_bounds__(256) kv_cache_append_f8_kernel(const AttnAppendArgs g, long total) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int sub = (int)(idx & 3);
+  long r = idx >> 2;
+  const int h = (int)(r % g.H);
+  r /= g.H;
+  const int t = (int)(r % g.T);
+  r /= g.T;
+  const int b = (int)(r % g.B);
+  const int which = (int)(r / g.B);                       // 0: K, 1: V
+  int p0, n;
+  row_extent(g, b, p0, n);
+  if (t >= n) return;
+  const long HD = (long)g.H * kHd;
+  const bf16_t* src = g.qkv_new + ((long)b * g.T + t) * 3 * HD + (1 + which) * HD + h * kHd + sub * 16;
+  const uint4 lo = *reinterpret_cast<const uint4*>(src);
+  const uint4 hi = *reinterpret_cast<const uint4*>(src + 8);
+  const int e = kv_f8_exponent(kv_f8_group4_max(max(kv_f8_absmax8(lo), kv_f8_absmax8(hi))));
+  const long row = ((long)b * g.H + h) * g.C + p0 + t;
+  uint8_t* dst = reinterpret_cast<uint8_t*>(which ? g.v_cache : g.k_cache) + row * kHd + sub * 16;
+  *reinterpret_cast<uint4*>(dst) = kv_f8_quantize16(lo, hi, kv_f8_pow2(-e));
+  if (sub == 0) (which ? g.v_scale : g.k_scale)[row] = kv_f8_pow2(e);
+}
+
+// F8: the caches are e4m3 bytes with one scale per row (kv_f8.h); only the staging differs -- a
+// thread's 16 bytes are dequantised, exactly, to the 16 bf16 the bf16 cache would hold.
+template <int QT, bool F8>
 __global__ void __launch_bounds__(64 * kWaves) attn_append_kernel(const AttnAppendArgs g) {
   constexpr int KS = kWaves / QT;                         // 64-key sub-tiles per staged chunk
   constexpr int CH = kTile * KS;                          // keys per staged chunk
@@ -165,15 +202,36 @@ __global__ void __launch_bounds__(64 * kWaves) attn_append_kernel(const AttnAppe
 
   for (int tc = t0; tc < t1; tc += KS) {
     __syncthreads();
-    // CH rows x 128 B of K and of V: 16 B per thread and step, 8 whole rows per wave instruction
+    if constexpr (F8) {
+      // CH rows x 64 B of K and of V: 16 B (16 values) per thread and step, 16 whole rows per wave
+      // instruction, and the row's scale (the 4 lanes of a row read the same word)
+      const long bh = (long)b * g.H + h;
 #pragma unroll
-    for (int i = 0; i < 2 * CH * 8 / (64 * kWaves); ++i) {
-      const int v = tid + 64 * kWaves * i;
-      const int sel = v / (CH * 8), row = (v >> 3) % CH, cc = (v & 7) * 8;
-      const int key = tc * kTile + row;
-      uint4 x = make_uint4(0, 0, 0, 0);
-      if (key < kend) x = *reinterpret_cast<const uint4*>((sel ? vc : kc) + (long)key * kHd + cc);
-      *reinterpret_cast<uint4*>((sel ? Vs : Ks) + row * kLd + cc) = x;
+      for (int i = 0; i < 2 * CH * 4 / (64 * kWaves); ++i) {
+        const int v = tid + 64 * kWaves * i;
+        const int sel = v / (CH * 4), row = (v >> 2) % CH, cc = (v & 3) * 16;
+        const int key = tc * kTile + row;
+        uint4 lo = make_uint4(0, 0, 0, 0), hi = lo;
+        if (key < kend) {
+          const uint8_t* c8 = reinterpret_cast<const uint8_t*>(sel ? g.v_cache : g.k_cache);
+          const uint4 x = *reinterpret_cast<const uint4*>(c8 + (bh * g.C + key) * kHd + cc);
+          kv_f8_dequantize16(x, (sel ? g.v_scale : g.k_scale)[bh * g.C + key], lo, hi);
+        }
+        bf16_t* d = (sel ? Vs : Ks) + row * kLd + cc;
+        *reinterpret_cast<uint4*>(d) = lo;
+        *reinterpret_cast<uint4*>(d + 8) = hi;
+      }
+    } else {
+      // CH rows x 128 B of K and of V: 16 B per thread and step, 8 whole rows per wave instruction
+#pragma unroll
+      for (int i = 0; i < 2 * CH * 8 / (64 * kWaves); ++i) {
+        const int v = tid + 64 * kWaves * i;
+        const int sel = v / (CH * 8), row = (v >> 3) % CH, cc = (v & 7) * 8;
+        const int key = tc * kTile + row;
+        uint4 x = make_uint4(0, 0, 0, 0);
+        if (key < kend) x = *reinterpret_cast<const uint4*>((sel ? vc : kc) + (long)key * kHd + cc);
+        *reinterpret_cast<uint4*>((sel ? Vs : Ks) + row * kLd + cc) = x;
+      }
     }
     __syncthreads();
     const int tile = tc + ks;
@@ -323,19 +381,19 @@ constexpr int kSmallT = 16;          // up to here: one query tile, four key sub
 int tiles_of(int len) { return (len + kTile - 1) / kTile; }
 int query_blocks(int T) { return T <= kSmallT ? 1 : (T + 63) / 64; }
 
-template <int QT>
+template <int QT, bool F8>
 void launch_append(const AttnAppendArgs& g, int nqb, hipStream_t st) {
   constexpr int kLds = 2 * kTile * (kWaves / QT) * kLd * (int)sizeof(bf16_t);
   if constexpr (kLds > 64 * 1024) {
     static bool once = false;
     if (!once) {
-      HIP_CHECK(hipFuncSetAttribute((const void*)attn_append_kernel<QT>,
+      HIP_CHECK(hipFuncSetAttribute((const void*)attn_append_kernel<QT, F8>,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
       once = true;
     }
   }
-  hipLaunchKernelGGL(attn_append_kernel<QT>, dim3(g.splits * nqb, g.H, g.B), dim3(64 * kWaves),
-                     kLds, st, g);
+  hipLaunchKernelGGL((attn_append_kernel<QT, F8>), dim3(g.splits * nqb, g.H, g.B),
+                     dim3(64 * kWaves), kLds, st, g);
 }
 
 }  // namespace
@@ -361,37 +419,65 @@ long dtf_attn_append_ws_floats(int B, int H, int T, int splits) {
   return splits > 1 ? (long)B * H * T * splits * kWsRow : 0;
 }
 
-void dtf_attn_append(const bf16_t* qkv_new, const int* pos, const int* n_new, bf16_t* k_cache,
-                     bf16_t* v_cache, bf16_t* out, float* ws, int B, int T, int H, int C,
-                     int max_len, int splits, float scale, hipStream_t st) {
-  if (!qkv_new || !pos || !k_cache || !v_cache || !out)
-    throw std::runtime_error("attn_append: null pointer");
+namespace {
+
+// F8: k_cache / v_cache point at e4m3 bytes and the scales are set
+template <bool F8>
+void append_any(const char* name, const bf16_t* qkv_new, const int* pos, const int* n_new,
+                void* k_cache, void* v_cache, float* k_scale, float* v_scale, bf16_t* out,
+                float* ws, int B, int T, int H, int C, int max_len, int splits, float scale,
+                hipStream_t st) {
+  const std::string nm(name);
+  if (!qkv_new || !pos || !k_cache || !v_cache || !out || (F8 && (!k_scale || !v_scale)))
+    throw std::runtime_error(nm + ": null pointer");
   if (B < 1 || H < 1 || B > 65535 || H > 65535)
-    throw std::runtime_error("attn_append: 1 <= B, H <= 65535");
+    throw std::runtime_error(nm + ": 1 <= B, H <= 65535");
   if (C < kTile || C % kTile)
-    throw std::runtime_error("attn_append: cache capacity must be a multiple of 64, at least 64");
-  if (T < 1) throw std::runtime_error("attn_append: at least one new token per row (T >= 1)");
+    throw std::runtime_error(nm + ": cache capacity must be a multiple of 64, at least 64");
+  if (T < 1) throw std::runtime_error(nm + ": at least one new token per row (T >= 1)");
   if (max_len < T || max_len > C)
-    throw std::runtime_error("attn_append: T <= max_len <= capacity");
+    throw std::runtime_error(nm + ": T <= max_len <= capacity");
   if (splits == 0) splits = dtf_attn_append_splits(B, H, T, max_len);
   if (splits < 1 || splits > tiles_of(max_len))
-    throw std::runtime_error("attn_append: splits " + std::to_string(splits) + " exceeds the " +
+    throw std::runtime_error(nm + ": splits " + std::to_string(splits) + " exceeds the " +
                              std::to_string(tiles_of(max_len)) + " tiles of max_len");
-  if (splits > 1 && !ws) throw std::runtime_error("attn_append: splits > 1 needs the workspace");
-  const AttnAppendArgs g{qkv_new, pos, n_new, k_cache, v_cache, out, ws, B, T, H, C, splits,
-                         scale * 1.4426950408889634f};
-  const long chunks = 2L * B * T * H * 8;
-  if (chunks >= 2147483647L * 256) throw std::runtime_error("attn_append: tensor too large");
-  hipLaunchKernelGGL(kv_cache_append_kernel, dim3(dtf_cdiv(chunks, 256)), dim3(256), 0, st, g,
-                     chunks);
+  if (splits > 1 && !ws) throw std::runtime_error(nm + ": splits > 1 needs the workspace");
+  const AttnAppendArgs g{qkv_new, pos, n_new, static_cast<bf16_t*>(k_cache),
+                         static_cast<bf16_t*>(v_cache), out, ws, B, T, H, C, splits,
+                         scale * 1.4426950408889634f, k_scale, v_scale};
+  const long chunks = 2L * B * T * H * (F8 ? 4 : 8);
+  if (chunks >= 2147483647L * 256) throw std::runtime_error(nm + ": tensor too large");
+  if constexpr (F8)
+    hipLaunchKernelGGL(kv_cache_append_f8_kernel, dim3(dtf_cdiv(chunks, 256)), dim3(256), 0, st,
+                       g, chunks);
+  else
+    hipLaunchKernelGGL(kv_cache_append_kernel, dim3(dtf_cdiv(chunks, 256)), dim3(256), 0, st, g,
+                       chunks);
   const int nqb = query_blocks(T);
   if (T <= kSmallT)
-    launch_append<1>(g, nqb, st);
+    launch_append<1, F8>(g, nqb, st);
   else
-    launch_append<4>(g, nqb, st);
+    launch_append<4, F8>(g, nqb, st);
   if (splits > 1) {
     const long rows = (long)B * H * T * 16;
     hipLaunchKernelGGL(attn_append_combine_kernel, dim3(dtf_cdiv(rows, 256)), dim3(256), 0, st, g,
                        rows);
   }
+}
+
+}  // namespace
+
+void dtf_attn_append(const bf16_t* qkv_new, const int* pos, const int* n_new, bf16_t* k_cache,
+                     bf16_t* v_cache, bf16_t* out, float* ws, int B, int T, int H, int C,
+                     int max_len, int splits, float scale, hipStream_t st) {
+  append_any<false>("attn_append", qkv_new, pos, n_new, k_cache, v_cache, nullptr, nullptr, out,
+                    ws, B, T, H, C, max_len, splits, scale, st);
+}
+
+void dtf_attn_append_f8(const bf16_t* qkv_new, const int* pos, const int* n_new, uint8_t* k_cache,
+                        uint8_t* v_cache, float* k_scale, float* v_scale, bf16_t* out, float* ws,
+                        int B, int T, int H, int C, int max_len, int splits, float scale,
+                        hipStream_t st) {
+  append_any<true>("attn_append_f8", qkv_new, pos, n_new, k_cache, v_cache, k_scale, v_scale, out,
+                   ws, B, T, H, C, max_len, splits, scale, st);
 }

@@ -44,15 +44,18 @@
 #include <stdexcept>
 #include <string>
 
+#include "attn_decode_merge.h"
 #include "launch.h"
 
 namespace {
 
+using decode_merge::kNegInf;
+using decode_merge::kWaves;
+using decode_merge::kWsRow;
+using decode_merge::merge_weight;
+
 constexpr int kHd = 64;          // head dim
 constexpr int kTile = 64;        // keys per tile
-constexpr int kWaves = 4;        // waves per block
-constexpr int kWsRow = 66;       // acc[64], m, l
-constexpr float kNegInf = -__builtin_inff();
 
 DTF_DEV float group8_sum(float v) {            // over the 8 lanes that share a row
   v += __shfl_xor(v, 1, 64);
@@ -71,11 +74,6 @@ DTF_DEV float groups_max(float v) {
   v = fmaxf(v, __shfl_xor(v, 16, 64));
   v = fmaxf(v, __shfl_xor(v, 32, 64));
   return v;
-}
-// weight of a partial with maximum m in a merge whose maximum is M: an empty partial (m = -inf)
-// weighs exactly 0, also when M is -inf
-DTF_DEV float merge_weight(float m, float M) {
-  return m == kNegInf ? 0.f : __builtin_amdgcn_exp2f(m - M);
 }
 
 // One 64-key tile of one wave's online softmax.  LAST: the tile that holds row pos -- rows past
@@ -178,32 +176,7 @@ __global__ void __launch_bounds__(64 * kWaves) attn_decode_kernel(const AttnDeco
   if (threadIdx.x >= 8) return;
 
   // threads 0 .. 7: head dims 8 sub .. + 7 of the 4 waves, in wave order
-  float M = kNegInf;
-#pragma unroll
-  for (int i = 0; i < kWaves; ++i) M = fmaxf(M, sm[i][64]);
-  float L = 0.f, A[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) A[e] = 0.f;
-#pragma unroll
-  for (int i = 0; i < kWaves; ++i) {
-    const float f = merge_weight(sm[i][64], M);
-    L = __builtin_fmaf(sm[i][65], f, L);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) A[e] = __builtin_fmaf(sm[i][sub * 8 + e], f, A[e]);
-  }
-  const long bh = (long)b * g.H + h;
-  if (g.splits == 1) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) A[e] /= L;
-    *reinterpret_cast<uint4*>(g.out + bh * kHd + sub * 8) = pack8(A);
-    return;
-  }
-  // 264-B partial rows: 8-B aligned
-  float* ws = g.ws + (bh * g.splits + split) * kWsRow;
-#pragma unroll
-  for (int e = 0; e < 8; e += 2)
-    *reinterpret_cast<float2*>(ws + sub * 8 + e) = make_float2(A[e], A[e + 1]);
-  if (sub == 0) *reinterpret_cast<float2*>(ws + 64) = make_float2(M, L);
+  decode_merge::merge_waves(sm, sub, g.out, g.ws, g.splits, split, (long)b * g.H + h);
 }
 
 // 8 threads per (b, h): the partials of its splits merged in split order.  The last split always
@@ -282,6 +255,13 @@ long dtf_attn_decode_ws_floats(int B, int H, int splits) {
   return splits > 1 ? (long)B * H * splits * kWsRow : 0;
 }
 
+// the combine launch alone (reads g.ws, g.splits, g.B, g.H; writes g.out): attn_f8.hip's decode
+// kernel leaves the same workspace rows
+void dtf_attn_decode_combine(const AttnDecodeArgs& g, hipStream_t st) {
+  hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(dtf_cdiv((long)g.B * g.H * 8, 256)),
+                     dim3(256), 0, st, g);
+}
+
 void dtf_attn_decode(const bf16_t* qkv_new, const int* pos, bf16_t* k_cache, bf16_t* v_cache,
                      bf16_t* out, float* ws, int B, int H, int C, int max_len, int splits,
                      float scale, hipStream_t st) {
@@ -300,9 +280,7 @@ void dtf_attn_decode(const bf16_t* qkv_new, const int* pos, bf16_t* k_cache, bf1
   const AttnDecodeArgs g{qkv_new, pos, k_cache, v_cache, out, ws, B, H, C, splits,
                          scale * 1.4426950408889634f};
   hipLaunchKernelGGL(attn_decode_kernel, dim3(splits, H, B), dim3(64 * kWaves), 0, st, g);
-  if (splits > 1)
-    hipLaunchKernelGGL(attn_decode_combine_kernel, dim3(dtf_cdiv((long)B * H * 8, 256)), dim3(256),
-                       0, st, g);
+  if (splits > 1) dtf_attn_decode_combine(g, st);
 }
 
 void dtf_kv_cache_fill(const bf16_t* qkv, bf16_t* k_cache, bf16_t* v_cache, int B, int S, int H,

@@ -921,6 +921,39 @@ PYBIND11_MODULE(_dtf_hip, m) {
   }, py::arg("qkv_new"), py::arg("pos"), py::arg("n_new"), py::arg("k_cache"), py::arg("v_cache"),
      py::arg("out"), py::arg("ws"), py::arg("B"), py::arg("T"), py::arg("H"), py::arg("C"),
      py::arg("max_len"), py::arg("splits"), py::arg("scale"), py::arg("st"));
+  m.def("attn_decode_f8", [](uintptr_t qkv_new, uintptr_t pos, uintptr_t k_cache,
+                             uintptr_t v_cache, uintptr_t k_scale, uintptr_t v_scale,
+                             uintptr_t out, uintptr_t ws, int B, int H, int C, int max_len,
+                             int splits, float scale, uintptr_t st) {
+    dtf_attn_decode_f8(P<const bf16_t>(qkv_new), P<const int>(pos), P<uint8_t>(k_cache),
+                       P<uint8_t>(v_cache), P<float>(k_scale), P<float>(v_scale), P<bf16_t>(out),
+                       P<float>(ws), B, H, C, max_len, splits, scale, S(st));
+    check_launch("attn_decode_f8");
+  }, py::arg("qkv_new"), py::arg("pos"), py::arg("k_cache"), py::arg("v_cache"),
+     py::arg("k_scale"), py::arg("v_scale"), py::arg("out"), py::arg("ws"), py::arg("B"),
+     py::arg("H"), py::arg("C"), py::arg("max_len"), py::arg("splits"), py::arg("scale"),
+     py::arg("st"));
+  m.def("kv_cache_fill_f8", [](uintptr_t qkv, uintptr_t k_cache, uintptr_t v_cache,
+                               uintptr_t k_scale, uintptr_t v_scale, int B, int S_, int H, int C,
+                               uintptr_t st) {
+    dtf_kv_cache_fill_f8(P<const bf16_t>(qkv), P<uint8_t>(k_cache), P<uint8_t>(v_cache),
+                         P<float>(k_scale), P<float>(v_scale), B, S_, H, C, S(st));
+    check_launch("kv_cache_fill_f8");
+  }, py::arg("qkv"), py::arg("k_cache"), py::arg("v_cache"), py::arg("k_scale"),
+     py::arg("v_scale"), py::arg("B"), py::arg("S"), py::arg("H"), py::arg("C"), py::arg("st"));
+  m.def("attn_append_f8", [](uintptr_t qkv_new, uintptr_t pos, uintptr_t n_new, uintptr_t k_cache,
+                             uintptr_t v_cache, uintptr_t k_scale, uintptr_t v_scale,
+                             uintptr_t out, uintptr_t ws, int B, int T, int H, int C, int max_len,
+                             int splits, float scale, uintptr_t st) {
+    dtf_attn_append_f8(P<const bf16_t>(qkv_new), P<const int>(pos), P<const int>(n_new),
+                       P<uint8_t>(k_cache), P<uint8_t>(v_cache), P<float>(k_scale),
+                       P<float>(v_scale), P<bf16_t>(out), P<float>(ws), B, T, H, C, max_len,
+                       splits, scale, S(st));
+    check_launch("attn_append_f8");
+  }, py::arg("qkv_new"), py::arg("pos"), py::arg("n_new"), py::arg("k_cache"), py::arg("v_cache"),
+     py::arg("k_scale"), py::arg("v_scale"), py::arg("out"), py::arg("ws"), py::arg("B"),
+     py::arg("T"), py::arg("H"), py::arg("C"), py::arg("max_len"), py::arg("splits"),
+     py::arg("scale"), py::arg("st"));
   m.def("sample_max_keys", &dtf_sample_max_keys, py::arg("large"));
   m.def("sample_tokens", [](uintptr_t logits, uintptr_t counter, uintptr_t tokens,
                             uintptr_t logprob, int B, int V, int ld, uint32_t seed,

@@ -454,6 +454,37 @@ void dtf_attn_decode(const bf16_t* qkv_new, const int* pos, bf16_t* k_cache, bf1
                      float scale, hipStream_t st);
 void dtf_kv_cache_fill(const bf16_t* qkv, bf16_t* k_cache, bf16_t* v_cache, int B, int S, int H,
                        int C, hipStream_t st);
+// the combine launch alone (reads g.ws, g.splits, g.B, g.H, writes g.out)
+void dtf_attn_decode_combine(const AttnDecodeArgs& g, hipStream_t st);
+
+// ---- attn_f8.hip: the same against an FP8 cache -- e4m3 bytes [B, H, C, 64] and one fp32
+// power-of-two scale per row, [B, H, C] (kv_f8.h)
+struct AttnDecodeF8Args {
+  const bf16_t* qkv_new;   // [B, 3*H*64]
+  const int* pos;          // [B], device
+  uint8_t* k_cache;        // [B, H, C, 64] e4m3
+  uint8_t* v_cache;
+  float* k_scale;          // [B, H, C]
+  float* v_scale;
+  bf16_t* out;             // [B, H*64]
+  float* ws;               // [B, H, splits, 66] partials (splits > 1), the rows of attn_decode.hip
+  int B, H, C, splits;
+  float c;                 // scale * log2(e)
+};
+struct KvFillF8Args {
+  const bf16_t* qkv;       // [B*S, 3*H*64]
+  uint8_t* k_cache;
+  uint8_t* v_cache;
+  float* k_scale;
+  float* v_scale;
+  int B, S, H, C;
+  long n;                  // 16-B chunks to write
+};
+void dtf_attn_decode_f8(const bf16_t* qkv_new, const int* pos, uint8_t* k_cache, uint8_t* v_cache,
+                        float* k_scale, float* v_scale, bf16_t* out, float* ws, int B, int H,
+                        int C, int max_len, int splits, float scale, hipStream_t st);
+void dtf_kv_cache_fill_f8(const bf16_t* qkv, uint8_t* k_cache, uint8_t* v_cache, float* k_scale,
+                          float* v_scale, int B, int S, int H, int C, hipStream_t st);
 
 // ---- attn_append.hip: T new tokens per sequence against the [B, H, C, 64] caches
 struct AttnAppendArgs {
@@ -466,12 +497,20 @@ struct AttnAppendArgs {
   float* ws;               // [B, H, T, splits, 68] partials (splits > 1)
   int B, T, H, C, splits;
   float c;                 // scale * log2(e)
+  // the FP8 cache (dtf_attn_append_f8; null otherwise): k_cache / v_cache then point at e4m3
+  // bytes [B, H, C, 64] and these at the rows' fp32 scales [B, H, C]
+  float* k_scale;
+  float* v_scale;
 };
 int dtf_attn_append_splits(int B, int H, int T, int max_len);
 long dtf_attn_append_ws_floats(int B, int H, int T, int splits);
 void dtf_attn_append(const bf16_t* qkv_new, const int* pos, const int* n_new, bf16_t* k_cache,
                      bf16_t* v_cache, bf16_t* out, float* ws, int B, int T, int H, int C,
                      int max_len, int splits, float scale, hipStream_t st);
+void dtf_attn_append_f8(const bf16_t* qkv_new, const int* pos, const int* n_new, uint8_t* k_cache,
+                        uint8_t* v_cache, float* k_scale, float* v_scale, bf16_t* out, float* ws,
+                        int B, int T, int H, int C, int max_len, int splits, float scale,
+                        hipStream_t st);
 
 // ---- sample.hip: top-k / top-p filtering and the draw of one token per logits row, one kernel
 struct SampleArgs {

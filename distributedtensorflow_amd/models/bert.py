@@ -133,31 +133,35 @@ class BertLayer(nn.Module):
 
     def forward(self, x, mask, B, S, cache=None):
         """``cache``: a ``(k, v)`` pair of [B, heads, C, 64] tensors that receives this layer's
-        keys and values of positions 0 .. S-1 (the prefill of incremental decoding)."""
+        keys and values of positions 0 .. S-1 (the prefill of incremental decoding); an FP8
+        cache's ``(k, v, k_scale, v_scale)``."""
         cfg = self.cfg
         qkv = ops.dense(x, self.qkv_kernel, self.qkv_bias, impl=BERT_GEMM)
         if cache is not None:
-            ops.kv_cache_fill(qkv, cache[0], cache[1], B, S, cfg.num_attention_heads)
+            ops.kv_cache_fill(qkv, cache[0], cache[1], B, S, cfg.num_attention_heads, *cache[2:])
         ctx = ops.attention_qkv(qkv, mask, B, S, cfg.num_attention_heads,
                                 cfg.attention_probs_dropout_prob, self.training,
                                 causal=cfg.causal)
         return self._after_attention(x, ctx)
 
-    def decode(self, x, k_cache, v_cache, pos, max_len=None):
+    def decode(self, x, k_cache, v_cache, pos, max_len=None, k_scale=None, v_scale=None):
         """One new token per sequence (x [B, H]) at positions ``pos`` against this layer's cache,
-        which takes the token's key and value in place."""
+        which takes the token's key and value in place (``k_scale`` / ``v_scale``: an FP8 cache's
+        row scales)."""
         qkv = ops.dense(x, self.qkv_kernel, self.qkv_bias, impl=BERT_GEMM)
         ctx = ops.attention_decode(qkv, k_cache, v_cache, pos, self.cfg.num_attention_heads,
-                                   max_len=max_len)
+                                   max_len=max_len, k_scale=k_scale, v_scale=v_scale)
         return self._after_attention(x, ctx)
 
-    def extend(self, x, k_cache, v_cache, pos, n_new, T, max_len=None):
+    def extend(self, x, k_cache, v_cache, pos, n_new, T, max_len=None, k_scale=None,
+               v_scale=None):
         """T new tokens per sequence (x [B*T, H]), the first ``n_new[b]`` of them real, at
         positions ``pos[b] ..`` against this layer's cache, which takes their keys and values in
         place (``ops.attention_append``)."""
         qkv = ops.dense(x, self.qkv_kernel, self.qkv_bias, impl=BERT_GEMM)
         ctx = ops.attention_append(qkv, k_cache, v_cache, pos, self.cfg.num_attention_heads,
-                                   n_new=n_new, max_len=max_len)
+                                   n_new=n_new, max_len=max_len, k_scale=k_scale,
+                                   v_scale=v_scale)
         return self._after_attention(x, ctx)
 
     def _after_attention(self, x, ctx):
@@ -242,7 +246,7 @@ class BertForPreTraining(Layer):
             if cache is None:
                 x = layer(x, mask, B, S)
             else:
-                x = layer(x, mask, B, S, cache=(cache.k[i], cache.v[i]))
+                x = layer(x, mask, B, S, cache=cache.layer(i))
         return x, mask
 
     def forward(self, input_ids, token_type_ids=None, attention_mask=None,
@@ -323,7 +327,7 @@ class BertForPreTraining(Layer):
         cfg = self.cfg
         if not cfg.causal:
             raise ValueError("incremental decoding needs a causal model (BertConfig(causal=True))")
-        dtype = cache.k.dtype
+        dtype = cache.act_dtype
         # the embedding kernel indexes positions by row % S: form word[id] + pos[p] + type[0] as
         # it does (tables rounded to the activation dtype, summed in fp32, rounded once)
         p = cache.pos.long().clamp(max=cfg.max_position_embeddings - 1)
@@ -334,7 +338,8 @@ class BertForPreTraining(Layer):
                                             0.0, False, cfg.layer_norm_eps)
         cache.max_len = min(cache.max_len + 1, cache.capacity)
         for i, layer in enumerate(self.layers):
-            x = layer.decode(x, cache.k[i], cache.v[i], cache.pos, cache.max_len)
+            x = layer.decode(x, cache.k[i], cache.v[i], cache.pos, cache.max_len,
+                             *cache.layer(i)[2:])
         cache.pos.add_(1)
         logits = self._head(x)
         return logits if _padded else logits[:, :cfg.vocab_size]
@@ -361,7 +366,7 @@ class BertForPreTraining(Layer):
         if cache.max_len + int(n.max()) > cache.capacity:
             raise ValueError(f"{cache.max_len} cached + {int(n.max())} new tokens exceed the "
                              f"capacity {cache.capacity}")
-        dev, dtype = ids_new.device, cache.k.dtype
+        dev, dtype = ids_new.device, cache.act_dtype
         n_d = n.to(dev, torch.int32)
         # word[id] + pos[p] + type[0] as decode_step forms it, p = cache.pos[b] + i
         p = (cache.pos.long().view(B, 1) + torch.arange(T, device=dev).view(1, T)).reshape(-1)
@@ -373,7 +378,8 @@ class BertForPreTraining(Layer):
                                             0.0, False, cfg.layer_norm_eps)
         launch_len = max(T, min(cache.max_len + T, cache.capacity))
         for i, layer in enumerate(self.layers):
-            x = layer.extend(x, cache.k[i], cache.v[i], cache.pos, n_d, T, launch_len)
+            x = layer.extend(x, cache.k[i], cache.v[i], cache.pos, n_d, T, launch_len,
+                             *cache.layer(i)[2:])
         cache.pos.add_(n_d)
         cache.max_len = min(cache.max_len + int(n.max()), cache.capacity)
         if not all_logits:
@@ -385,7 +391,7 @@ class BertForPreTraining(Layer):
 
     def generate(self, input_ids, prompt_lens, max_new_tokens, temperature=0.0, top_k=0,
                  eos_id=None, generator=None, top_p=1.0, seed=None, return_logprobs=False,
-                 prefill_chunk=None):
+                 prefill_chunk=None, kv_dtype=None):
         """Continue the right-padded prompts [B, Sp] by ``max_new_tokens`` tokens -> int64
         [B, max_new_tokens].  Greedy at ``temperature == 0``; otherwise softmax sampling of
         ``logits / temperature`` over the ``top_k`` largest (all when 0) with ``generator``.  A row
@@ -398,7 +404,8 @@ class BertForPreTraining(Layer):
         log-probability of every picked token, fp32 [B, max_new_tokens] (of the sampled token, also
         where ``eos_id`` replaced it).  ``generator`` is not used then.
 
-        ``prefill_chunk=T`` feeds the prompt through ``prefill(chunk=T)``, T tokens at a time."""
+        ``prefill_chunk=T`` feeds the prompt through ``prefill(chunk=T)``, T tokens at a time.
+        ``kv_dtype="fp8"`` keeps the keys and values in an FP8 cache (:class:`KVCache`)."""
         lens = self._check_prompts(input_ids, prompt_lens)
         if seed is None and (top_p != 1.0 or return_logprobs):
             raise ValueError("top_p and return_logprobs need the seeded path: pass seed=")
@@ -411,7 +418,7 @@ class BertForPreTraining(Layer):
         dev = input_ids.device
         cache = KVCache(self.cfg, input_ids.shape[0], need, dev,
                         torch.bfloat16 if input_ids.is_cuda else torch.float32,
-                        min_rows=input_ids.shape[1])
+                        min_rows=input_ids.shape[1], kv_dtype=kv_dtype)
         was_training = self.training
         self.eval()
         try:
@@ -461,20 +468,42 @@ class KVCache:
     [L, B, heads, C, 64] (one (batch, head)'s keys are contiguous 128-B rows, the layout the decode
     kernel streams) and ``pos`` int32 [B] on the device, the row each sequence's next token takes.
     ``capacity`` is rounded up to a multiple of 64.  ``max_len`` is the host's upper bound on
-    ``pos + 1``; it only sizes launches."""
+    ``pos + 1``; it only sizes launches.
+
+    ``kv_dtype`` (default ``dtype``): ``torch.float8_e4m3fn`` or ``"fp8"`` stores ``k`` / ``v`` as
+    e4m3 bytes, 64-B rows, with ``k_scale`` / ``v_scale`` fp32 [L, B, heads, C], one power-of-two
+    scale per row (``ops.reference.kv_quantize_rows``): 68 bytes per cached row instead of 128.
+    ``act_dtype`` is ``dtype``, what the model computes in."""
 
     def __init__(self, cfg: BertConfig, batch, capacity, device, dtype=torch.bfloat16,
-                 min_rows=0):
+                 min_rows=0, kv_dtype=None):
         # min_rows: storage for a prefill whose padding runs past the capacity
         C = -(-max(int(capacity), int(min_rows)) // 64) * 64
         if capacity < 1 or capacity > cfg.max_position_embeddings:
             raise ValueError(f"capacity {capacity} outside [1, max_position_embeddings = "
                              f"{cfg.max_position_embeddings}]")
         shape = (cfg.num_hidden_layers, batch, cfg.num_attention_heads, C, 64)
-        self.k = torch.zeros(shape, device=device, dtype=dtype)
-        self.v = torch.zeros(shape, device=device, dtype=dtype)
+        if kv_dtype in (None, "bf16") or kv_dtype == dtype:
+            kv_dtype = dtype
+        elif kv_dtype == "fp8":
+            kv_dtype = torch.float8_e4m3fn
+        if kv_dtype not in (dtype, torch.float8_e4m3fn):
+            raise ValueError(f"kv_dtype {kv_dtype} is neither the activation dtype nor fp8")
+        self.act_dtype = dtype
+        self.k = torch.zeros(shape, device=device, dtype=kv_dtype)
+        self.v = torch.zeros(shape, device=device, dtype=kv_dtype)
+        self.k_scale = self.v_scale = None
+        if kv_dtype == torch.float8_e4m3fn:
+            self.k_scale = torch.zeros(shape[:4], device=device, dtype=torch.float32)
+            self.v_scale = torch.zeros(shape[:4], device=device, dtype=torch.float32)
         self.pos = torch.zeros(batch, device=device, dtype=torch.int32)
         self.batch, self.capacity, self.max_len = batch, C, C
+
+    def layer(self, i):
+        """Layer i's ``(k, v)``, an FP8 cache's ``(k, v, k_scale, v_scale)``."""
+        if self.k_scale is None:
+            return self.k[i], self.v[i]
+        return self.k[i], self.v[i], self.k_scale[i], self.v_scale[i]
 
     def reset(self):
         """An empty cache: ``pos = 0`` on the device and ``max_len = 0`` (the stored keys and

@@ -314,7 +314,8 @@ def attention_qkv(qkv, mask, batch, seq_len, heads, p=0.0, training=True, scale=
                                    causal=causal)
 
 
-def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=None, splits=0):
+def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=None, splits=0,
+                     k_scale=None, v_scale=None):
     """Incremental decoding: one new query per sequence against a key / value cache.
 
     ``qkv_new`` [B, 3*heads*64] is the new token's fused projection, ``k_cache`` / ``v_cache`` are
@@ -323,16 +324,20 @@ def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=
     query attends keys 0 .. pos[b]: ``softmax(q K^T scale) V`` -> [B, heads*64].  No mask, no
     dropout; rows past ``pos[b]`` may hold anything and are never used.  Native: ``pos`` is read on
     the device only; ``max_len`` (an upper bound on pos + 1, default C) and ``splits`` (0 = choose)
-    size the launch.  A no-grad op.  Not fenced: it reads no variable."""
+    size the launch.  A no-grad op.  Not fenced: it reads no variable.
+
+    FP8 cache: with ``float8_e4m3fn`` caches ``k_scale`` / ``v_scale`` fp32 [B, heads, C] hold one
+    power-of-two scale per 64-byte row (the rule: ``reference.kv_quantize_rows``).  The new rows
+    are quantised on the way in and the result is exactly this op on the dequantised caches."""
     if _use_native(qkv_new):
         return _nlp().attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale, max_len,
-                                       splits)
+                                       splits, k_scale, v_scale)
     return reference.attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale, max_len,
-                                      splits)
+                                      splits, k_scale, v_scale)
 
 
 def attention_append(qkv_new, k_cache, v_cache, pos, heads, n_new=None, scale=None, max_len=None,
-                     splits=0):
+                     splits=0, k_scale=None, v_scale=None):
     """Append attention: T new tokens per sequence against a key / value cache -- chunked
     prefill, extending a conversation, scoring drafted tokens.
 
@@ -344,20 +349,23 @@ def attention_append(qkv_new, k_cache, v_cache, pos, heads, n_new=None, scale=No
     output rows i >= n are exactly zero -> [B*T, heads*64].  ``pos`` is NOT advanced.  Cache rows
     at or past p0+n may hold anything and are never used.  Native: ``pos`` and ``n_new`` are read
     on the device only; ``max_len`` (an upper bound on pos + T, default C) and ``splits``
-    (0 = choose) size the launch.  A no-grad op.  Not fenced: it reads no variable."""
+    (0 = choose) size the launch.  A no-grad op.  Not fenced: it reads no variable.
+    ``k_scale`` / ``v_scale``: the FP8 cache, as :func:`attention_decode`."""
     if _use_native(qkv_new):
         return _nlp().attention_append(qkv_new, k_cache, v_cache, pos, heads, n_new, scale,
-                                       max_len, splits)
+                                       max_len, splits, k_scale, v_scale)
     return reference.attention_append(qkv_new, k_cache, v_cache, pos, heads, n_new, scale,
-                                      max_len, splits)
+                                      max_len, splits, k_scale, v_scale)
 
 
-def kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads):
+def kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads, k_scale=None, v_scale=None):
     """Copy the K and V thirds of a prefill's fused QKV matrix [batch*seq_len, 3*heads*64] into
-    rows 0 .. seq_len-1 of the [batch, heads, C, 64] caches, in place.  A no-grad op.  Not fenced: it reads no variable."""
+    rows 0 .. seq_len-1 of the [batch, heads, C, 64] caches, in place.  A no-grad op.  Not fenced: it reads no variable.
+    ``k_scale`` / ``v_scale``: the FP8 cache, as :func:`attention_decode` (the rows are quantised)."""
     if _use_native(qkv):
-        return _nlp().kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads)
-    return reference.kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads)
+        return _nlp().kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads, k_scale,
+                                    v_scale)
+    return reference.kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads, k_scale, v_scale)
 
 
 def sample_tokens(logits, seed, counter, temperature=1.0, top_k=0, top_p=1.0, vocab=None):

@@ -307,31 +307,44 @@ def attention(q, k, v, mask=None, scale=None, causal=False):
 
 
 # ----------------------------------------------------------------------------- decoding
-def _check_decode_tensors(name, *tensors):
-    for t in tensors:
-        if not t.is_cuda or t.dtype != _BF16:
-            raise ValueError(f"native {name} takes bf16 device tensors")
+def _check_decode_tensors(name, qkv, k_cache, v_cache, f8=False):
+    """``f8``: the caches are float8_e4m3fn (``reference.check_kv_dtypes`` has checked the rest)."""
+    for t, dtype in ((qkv, _BF16), (k_cache, torch.float8_e4m3fn if f8 else _BF16),
+                     (v_cache, torch.float8_e4m3fn if f8 else _BF16)):
+        if not t.is_cuda or t.dtype != dtype:
+            raise ValueError(f"native {name} takes bf16 device tensors (and bf16 or float8_e4m3fn "
+                             "caches)")
 
 
-def kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads):
-    """csrc/kernels/attn_decode.hip kv_cache_fill_kernel (see ``reference.kv_cache_fill``)."""
+def kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads, k_scale=None, v_scale=None):
+    """csrc/kernels/attn_decode.hip kv_cache_fill_kernel, or attn_f8.hip's quantising one for an
+    FP8 cache (see ``reference.kv_cache_fill``)."""
     from . import reference
     reference.no_grad_op("kv_cache_fill", qkv, k_cache, v_cache)
-    reference.check_fill_args(qkv, k_cache, v_cache, batch, seq_len, heads)
-    _check_decode_tensors("kv_cache_fill", qkv, k_cache, v_cache)
+    reference.check_fill_args(qkv, k_cache, v_cache, batch, seq_len, heads, k_scale, v_scale)
+    f8 = k_scale is not None
+    _check_decode_tensors("kv_cache_fill", qkv, k_cache, v_cache, f8)
     q = qkv.detach().contiguous()
+    if f8:
+        _K.kv_cache_fill_f8(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                            k_scale.data_ptr(), v_scale.data_ptr(), batch, seq_len, heads,
+                            k_cache.shape[2], _st())
+        return
     _K.kv_cache_fill(q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), batch, seq_len, heads,
                      k_cache.shape[2], _st())
 
 
-def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=None, splits=0):
-    """csrc/kernels/attn_decode.hip (see ``reference.attention_decode``).  ``pos`` stays on the
-    device: nothing here reads it, so a generation loop launches its steps without a sync."""
+def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=None, splits=0,
+                     k_scale=None, v_scale=None):
+    """csrc/kernels/attn_decode.hip, or attn_f8.hip for an FP8 cache (see
+    ``reference.attention_decode``).  ``pos`` stays on the device: nothing here reads it, so a
+    generation loop launches its steps without a sync."""
     from . import reference
     reference.no_grad_op("attention_decode", qkv_new, k_cache, v_cache)
     B, C, max_len = reference.check_decode_args(qkv_new, k_cache, v_cache, pos, heads, max_len,
-                                                splits)
-    _check_decode_tensors("attention_decode", qkv_new, k_cache, v_cache)
+                                                splits, k_scale, v_scale)
+    f8 = k_scale is not None
+    _check_decode_tensors("attention_decode", qkv_new, k_cache, v_cache, f8)
     if not pos.is_cuda:
         raise ValueError("native attention_decode takes pos on the device")
     scale = AD ** -0.5 if scale is None else scale
@@ -340,6 +353,12 @@ def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=
     nws = _K.attn_decode_ws_floats(B, heads, splits)
     ws = torch.empty(nws, device=q.device, dtype=torch.float32) if nws else None
     out = torch.empty(B, heads * AD, device=q.device, dtype=_BF16)
+    if f8:
+        _K.attn_decode_f8(q.data_ptr(), pos.contiguous().data_ptr(), k_cache.data_ptr(),
+                          v_cache.data_ptr(), k_scale.data_ptr(), v_scale.data_ptr(),
+                          out.data_ptr(), _p(ws), B, heads, C, max_len, splits, float(scale),
+                          _st())
+        return out
     _K.attn_decode(q.data_ptr(), pos.contiguous().data_ptr(), k_cache.data_ptr(),
                    v_cache.data_ptr(), out.data_ptr(), _p(ws), B, heads, C, max_len, splits,
                    float(scale), _st())
@@ -347,14 +366,16 @@ def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=
 
 
 def attention_append(qkv_new, k_cache, v_cache, pos, heads, n_new=None, scale=None, max_len=None,
-                     splits=0):
-    """csrc/kernels/attn_append.hip (see ``reference.attention_append``).  ``pos`` and ``n_new``
-    stay on the device: nothing here reads them."""
+                     splits=0, k_scale=None, v_scale=None):
+    """csrc/kernels/attn_append.hip, its F8 instances for an FP8 cache (see
+    ``reference.attention_append``).  ``pos`` and ``n_new`` stay on the device: nothing here
+    reads them."""
     from . import reference
     reference.no_grad_op("attention_append", qkv_new, k_cache, v_cache)
     B, T, C, max_len = reference.check_append_args(qkv_new, k_cache, v_cache, pos, heads, n_new,
-                                                   max_len, splits)
-    _check_decode_tensors("attention_append", qkv_new, k_cache, v_cache)
+                                                   max_len, splits, k_scale, v_scale)
+    f8 = k_scale is not None
+    _check_decode_tensors("attention_append", qkv_new, k_cache, v_cache, f8)
     scale = AD ** -0.5 if scale is None else scale
     q = qkv_new.detach().contiguous()
     splits = splits or _K.attn_append_splits(B, heads, T, max_len)
@@ -362,6 +383,12 @@ def attention_append(qkv_new, k_cache, v_cache, pos, heads, n_new=None, scale=No
     ws = torch.empty(nws, device=q.device, dtype=torch.float32) if nws else None
     out = torch.empty(B * T, heads * AD, device=q.device, dtype=_BF16)
     n_new = None if n_new is None else n_new.contiguous()
+    if f8:
+        _K.attn_append_f8(q.data_ptr(), pos.contiguous().data_ptr(), _p(n_new),
+                          k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(),
+                          v_scale.data_ptr(), out.data_ptr(), _p(ws), B, T, heads, C, max_len,
+                          splits, float(scale), _st())
+        return out
     _K.attn_append(q.data_ptr(), pos.contiguous().data_ptr(), _p(n_new), k_cache.data_ptr(),
                    v_cache.data_ptr(), out.data_ptr(), _p(ws), B, T, heads, C, max_len, splits,
                    float(scale), _st())

@@ -327,7 +327,73 @@ def attention_qkv(qkv, mask, batch, seq_len, heads, p=0.0, training=True, scale=
     return o.permute(0, 2, 1, 3).reshape(B * S, Hh * D).to(qkv.dtype)
 
 
-def check_decode_args(qkv_new, k_cache, v_cache, pos, heads, max_len, splits):
+F8 = torch.float8_e4m3fn
+
+
+def kv_quantize_rows(x):
+    """THE rule of the FP8 key / value cache (the kernels of csrc/kernels/kv_f8.h reproduce it bit
+    for bit): rows ``x`` [..., 64] of finite values -> (e4m3 bytes [..., 64], fp32 scales [...]).
+
+    With ``a = max |x_i| = f 2^k``, f in [0.5, 1): ``e = k - 9`` if ``f <= 0.875`` (448 =
+    0.875 * 2^9, the largest e4m3 value) else ``k - 8``, clamped to [-100, 120]; ``a == 0`` gives
+    ``e = 0``.  The scale is ``2^e`` and byte i is ``x_i 2^-e`` rounded to nearest even: by
+    construction ``|x_i 2^-e| <= 448``, nothing saturates."""
+    xf = x.detach().float()
+    a = xf.abs().amax(-1)
+    f, k = torch.frexp(a)
+    e = torch.where(f <= 0.875, k - 9, k - 8)
+    e = torch.where(a == 0, torch.zeros_like(e), e).clamp(-100, 120)
+    one = torch.ones_like(a)
+    return (xf * torch.ldexp(one, -e).unsqueeze(-1)).to(F8), torch.ldexp(one, e)
+
+
+def kv_dequantize(q, scale, dtype=torch.float32):
+    """``float(byte) * scale``: exact in fp32 (a power of two times 4 significant bits) and, with
+    the clamp on the exponent, a normal bf16."""
+    return (q.float() * scale.unsqueeze(-1)).to(dtype)
+
+
+def check_kv_dtypes(name, qkv, k_cache, v_cache, k_scale, v_scale):
+    """The one rule for the cache's data type, shared by the three cache ops and both backends ->
+    True for an FP8 cache.  ``float8_e4m3fn`` caches need both fp32 [B, heads, C] scales; any
+    other cache shares ``qkv``'s dtype and takes none."""
+    if k_cache.dtype != v_cache.dtype:
+        raise ValueError("k_cache and v_cache must share one dtype")
+    if k_cache.dtype != F8:
+        if k_scale is not None or v_scale is not None:
+            raise ValueError("k_scale / v_scale go with float8_e4m3fn caches only")
+        if qkv.dtype != k_cache.dtype:
+            raise ValueError(f"{name} and the caches must share one dtype")
+        return False
+    if k_scale is None or v_scale is None:
+        raise ValueError("float8_e4m3fn caches need k_scale and v_scale")
+    for t in (k_scale, v_scale):
+        if (t.dtype != torch.float32 or t.shape != k_cache.shape[:3] or not t.is_contiguous()
+                or t.device != k_cache.device):
+            raise ValueError(f"k_scale / v_scale must be contiguous fp32 "
+                             f"{list(k_cache.shape[:3])} on the caches' device")
+    return True
+
+
+def _f8_call(qkv, k_cache, v_cache, k_scale, v_scale, run):
+    """An FP8-cache op of the reference: ``run(qkv', k, v)`` is the bf16-cache op on the
+    DEQUANTISED caches, fed the new rows as the cache will hold them (quantised and dequantised),
+    and -> the cache rows it wrote as a bool [B, C].  Those rows' bytes and scales go back into
+    the FP8 caches; nothing else is touched."""
+    B, H, C, D = k_cache.shape
+    x = qkv.detach().reshape(B, -1, 3, H, D)
+    packed = [kv_quantize_rows(x[:, :, i]) for i in (1, 2)]           # bytes / scale [B, T, H(, D)]
+    x = torch.stack([x[:, :, 0]] + [kv_dequantize(q, s, qkv.dtype) for q, s in packed], 2)
+    k, v = (kv_dequantize(c, s, qkv.dtype) for c, s in ((k_cache, k_scale), (v_cache, v_scale)))
+    out, b_idx, rows, t_idx = run(x.reshape(qkv.shape), k, v)
+    for (q, s), cache, scale in zip(packed, (k_cache, v_cache), (k_scale, v_scale)):
+        cache.view(torch.uint8)[b_idx, :, rows] = q.view(torch.uint8)[b_idx, t_idx]
+        scale[b_idx, :, rows] = s[b_idx, t_idx]
+    return out
+
+
+def check_decode_args(qkv_new, k_cache, v_cache, pos, heads, max_len, splits, k_scale=None,
+                      v_scale=None):
     """The shape / dtype conditions of ``attention_decode``, shared by both backends ->
     (B, capacity, max_len)."""
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[3] != 64:
@@ -341,8 +407,7 @@ def check_decode_args(qkv_new, k_cache, v_cache, pos, heads, max_len, splits):
         raise ValueError("cache capacity must be a multiple of 64, at least 64")
     if pos.dtype != torch.int32 or tuple(pos.shape) != (B,):
         raise ValueError(f"pos must be int32 [{B}]")
-    if not (qkv_new.dtype == k_cache.dtype == v_cache.dtype):
-        raise ValueError("qkv_new and the caches must share one dtype")
+    check_kv_dtypes("qkv_new", qkv_new, k_cache, v_cache, k_scale, v_scale)
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
         raise ValueError("the caches must be contiguous")
     max_len = C if max_len is None else int(max_len)
@@ -353,7 +418,7 @@ def check_decode_args(qkv_new, k_cache, v_cache, pos, heads, max_len, splits):
     return B, C, max_len
 
 
-def check_fill_args(qkv, k_cache, v_cache, batch, seq_len, heads):
+def check_fill_args(qkv, k_cache, v_cache, batch, seq_len, heads, k_scale=None, v_scale=None):
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[3] != 64:
         raise ValueError("k_cache and v_cache must both be [B, heads, capacity, 64]")
     B, H, C, D = k_cache.shape
@@ -363,8 +428,7 @@ def check_fill_args(qkv, k_cache, v_cache, batch, seq_len, heads):
         raise ValueError(f"qkv must be [{batch * seq_len}, {3 * H * D}], got {tuple(qkv.shape)}")
     if C < 64 or C % 64 or not 1 <= seq_len <= C:
         raise ValueError("capacity must be a multiple of 64 and 1 <= seq_len <= capacity")
-    if not (qkv.dtype == k_cache.dtype == v_cache.dtype):
-        raise ValueError("qkv and the caches must share one dtype")
+    check_kv_dtypes("qkv", qkv, k_cache, v_cache, k_scale, v_scale)
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
         raise ValueError("the caches must be contiguous")
 
@@ -374,23 +438,38 @@ def no_grad_op(name, *tensors):
         raise RuntimeError(f"{name} is a no-grad op: call it under torch.no_grad()")
 
 
-def kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads):
+def kv_cache_fill(qkv, k_cache, v_cache, batch, seq_len, heads, k_scale=None, v_scale=None):
     """The K and V thirds of a prefill qkv [B*S, 3*H*64] into rows 0 .. S-1 of the [B, H, C, 64]
-    caches (in place; rows >= S untouched)."""
+    caches (in place; rows >= S untouched).  FP8 caches take ``kv_quantize_rows`` of them."""
     no_grad_op("kv_cache_fill", qkv, k_cache, v_cache)
-    check_fill_args(qkv, k_cache, v_cache, batch, seq_len, heads)
+    check_fill_args(qkv, k_cache, v_cache, batch, seq_len, heads, k_scale, v_scale)
     x = qkv.detach().view(batch, seq_len, 3, heads, 64)
+    if k_cache.dtype == F8:
+        for i, cache, scale in ((1, k_cache, k_scale), (2, v_cache, v_scale)):
+            q, s = kv_quantize_rows(x[:, :, i].permute(0, 2, 1, 3))
+            cache.view(torch.uint8)[:, :, :seq_len] = q.view(torch.uint8)
+            scale[:, :, :seq_len] = s
+        return
     k_cache[:, :, :seq_len] = x[:, :, 1].permute(0, 2, 1, 3)
     v_cache[:, :, :seq_len] = x[:, :, 2].permute(0, 2, 1, 3)
 
 
-def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=None, splits=0):
+def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=None, splits=0,
+                     k_scale=None, v_scale=None):
     """One new query per sequence against the caches: the new K / V rows go to row ``pos[b]``
     (clamped to the cache), the query attends keys 0 .. pos[b].  fp32 math on the stored values;
-    ``max_len`` and ``splits`` only size the native launch."""
+    ``max_len`` and ``splits`` only size the native launch.  With FP8 caches the new rows are
+    quantised (``kv_quantize_rows``) and this is the same attention on the dequantised caches."""
     no_grad_op("attention_decode", qkv_new, k_cache, v_cache)
-    B, C, _ = check_decode_args(qkv_new, k_cache, v_cache, pos, heads, max_len, splits)
+    B, C, _ = check_decode_args(qkv_new, k_cache, v_cache, pos, heads, max_len, splits, k_scale,
+                                v_scale)
     scale = 64 ** -0.5 if scale is None else scale
+    if k_cache.dtype == F8:
+        def run(x, k, v):
+            b = torch.arange(B, device=pos.device)
+            return (attention_decode(x, k, v, pos, heads, scale), b, pos.long().clamp(0, C - 1),
+                    torch.zeros_like(b))
+        return _f8_call(qkv_new, k_cache, v_cache, k_scale, v_scale, run)
     x = qkv_new.detach().view(B, 3, heads, 64)
     p = pos.long().clamp(0, C - 1)
     rows = torch.arange(B, device=pos.device)
@@ -404,7 +483,8 @@ def attention_decode(qkv_new, k_cache, v_cache, pos, heads, scale=None, max_len=
     return torch.einsum("bhk,bhkd->bhd", prob, v).reshape(B, heads * 64).to(qkv_new.dtype)
 
 
-def check_append_args(qkv_new, k_cache, v_cache, pos, heads, n_new, max_len, splits):
+def check_append_args(qkv_new, k_cache, v_cache, pos, heads, n_new, max_len, splits,
+                      k_scale=None, v_scale=None):
     """The shape / dtype conditions of ``attention_append``, shared by both backends ->
     (B, T, capacity, max_len)."""
     if k_cache.dim() != 4 or k_cache.shape != v_cache.shape or k_cache.shape[3] != 64:
@@ -422,8 +502,7 @@ def check_append_args(qkv_new, k_cache, v_cache, pos, heads, n_new, max_len, spl
         if t is not None and (t.dtype != torch.int32 or tuple(t.shape) != (B,)
                               or t.device != qkv_new.device):
             raise ValueError(f"{name} must be int32 [{B}] on qkv_new's device")
-    if not (qkv_new.dtype == k_cache.dtype == v_cache.dtype):
-        raise ValueError("qkv_new and the caches must share one dtype")
+    check_kv_dtypes("qkv_new", qkv_new, k_cache, v_cache, k_scale, v_scale)
     if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
         raise ValueError("the caches must be contiguous")
     max_len = C if max_len is None else int(max_len)
@@ -435,15 +514,28 @@ def check_append_args(qkv_new, k_cache, v_cache, pos, heads, n_new, max_len, spl
 
 
 def attention_append(qkv_new, k_cache, v_cache, pos, heads, n_new=None, scale=None, max_len=None,
-                     splits=0):
+                     splits=0, k_scale=None, v_scale=None):
     """T new tokens per sequence against the caches.  Per row b, with p0 = clamp(pos[b], 0, C) and
     n = clamp(n_new[b] (default T), 0, min(T, C - p0)): the K / V of new tokens 0 .. n-1 go to
     cache rows p0 .. p0+n-1, query i < n attends keys 0 .. p0+i, output rows i >= n are zero.
-    fp32 math on the stored values; ``max_len`` and ``splits`` only size the native launch."""
+    fp32 math on the stored values; ``max_len`` and ``splits`` only size the native launch.  With
+    FP8 caches the new rows are quantised (``kv_quantize_rows``) and this is the same attention on
+    the dequantised caches."""
     no_grad_op("attention_append", qkv_new, k_cache, v_cache)
-    B, T, C, _ = check_append_args(qkv_new, k_cache, v_cache, pos, heads, n_new, max_len, splits)
+    B, T, C, _ = check_append_args(qkv_new, k_cache, v_cache, pos, heads, n_new, max_len, splits,
+                                   k_scale, v_scale)
     scale = 64 ** -0.5 if scale is None else scale
     dev = qkv_new.device
+    if k_cache.dtype == F8:
+        def run(x, k, v):
+            p0 = pos.long().clamp(0, C)
+            n = (torch.full_like(p0, T) if n_new is None else n_new.long()).clamp(min=0)
+            n = torch.minimum(n, (C - p0).clamp(max=T))
+            b_idx, t_idx = (torch.arange(T, device=dev).view(1, T) < n.view(B, 1)).nonzero(
+                as_tuple=True)
+            return (attention_append(x, k, v, pos, heads, n_new, scale), b_idx,
+                    p0[b_idx] + t_idx, t_idx)
+        return _f8_call(qkv_new, k_cache, v_cache, k_scale, v_scale, run)
     x = qkv_new.detach().view(B, T, 3, heads, 64)
     p0 = pos.long().clamp(0, C)
     n = (torch.full_like(p0, T) if n_new is None else n_new.long()).clamp(min=0)

@@ -101,6 +101,14 @@ def causal_main(a):
             print(json.dumps(rec), flush=True)
 
 
+def _f8_ring(kc, vc):
+    """The bf16 cache ring as FP8 caches -> (k bytes, k scales, v bytes, v scales)."""
+    from distributedtensorflow_amd.ops import reference
+    k8, ks = reference.kv_quantize_rows(kc)
+    v8, vs = reference.kv_quantize_rows(vc)
+    return k8.contiguous(), ks.contiguous(), v8.contiguous(), vs.contiguous()
+
+
 def decode_main(a):
     H, dev = a.heads, "cuda"
     st = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
@@ -124,6 +132,31 @@ def decode_main(a):
                 _K.attn_decode(new.data_ptr(), pos.data_ptr(), kc[i].data_ptr(), vc[i].data_ptr(),
                                out.data_ptr(), ws.data_ptr(), B, H, n, n, splits, 0.125, st())
 
+            if a.kv_dtype == "fp8":
+                # the same ring as an FP8 cache (68 bytes a row), alternating with the bf16 one
+                k8, ks, v8, vs = _f8_ring(kc, vc)
+
+                def call8(splits):
+                    i = turn[0] = (turn[0] + 1) % ring
+                    _K.attn_decode_f8(new.data_ptr(), pos.data_ptr(), k8[i].data_ptr(),
+                                      v8[i].data_ptr(), ks[i].data_ptr(), vs[i].data_ptr(),
+                                      out.data_ptr(), ws.data_ptr(), B, H, n, n, splits, 0.125,
+                                      st())
+
+                t = {"bf16": [], "fp8": []}
+                for _ in range(a.rounds):
+                    t["bf16"].append(timeit(lambda: call(auto), a.iters))
+                    t["fp8"].append(timeit(lambda: call8(auto), a.iters))
+                rec = {"probe": "attn_decode_f8", "B": B, "H": H, "len": n, "ring": ring,
+                       "rounds": a.rounds, "iters": a.iters, "splits_auto": auto}
+                for k, row in (("bf16", 128), ("fp8", 68)):
+                    moved = 2 * n * row * B * H + (2 * 4 * B * H * auto * 66 if auto > 1 else 0)
+                    rec[f"{k}_us"] = round(med(t[k]) * 1e3, 2)
+                    rec[f"{k}_spread_us"] = [round(min(t[k]) * 1e3, 2), round(max(t[k]) * 1e3, 2)]
+                    rec[f"{k}_GBps"] = round(moved / (med(t[k]) * 1e-3) / 1e9, 1)
+                rec["speedup"] = round(med(t["bf16"]) / med(t["fp8"]), 3)
+                print(json.dumps(rec), flush=True)
+                continue
             arms = {"auto": auto, "one": 1}
             t = {k: [] for k in arms}
             for _ in range(a.rounds):
@@ -153,6 +186,7 @@ def append_main(a):
             vc = torch.randn(ring, B, H, n, 64, device=dev, generator=g).to(torch.bfloat16)
             qkv = (torch.randn(B * n, 3 * H * 64, device=dev, generator=g) * 0.5).to(torch.bfloat16)
             lse = torch.empty(B * H * n, device=dev)
+            f8 = _f8_ring(kc, vc) if a.kv_dtype == "fp8" else None
             for T in (8, 16, 64, 128):
                 new = qkv.view(B, n, -1)[:, n - T:]
                 steps = new.transpose(0, 1).contiguous()            # [T, B, 3*H*64]
@@ -185,8 +219,17 @@ def append_main(a):
 
                 arms = {"append": lambda: append(auto), "decode_x_T": decode,
                         "causal_forward": forward}
+                if a.kv_dtype == "fp8":                              # fp8 against bf16 only
+                    def append8():
+                        i = turn[0] = (turn[0] + 1) % ring
+                        _K.attn_append_f8(new.data_ptr(), pos.data_ptr(), 0, f8[0][i].data_ptr(),
+                                          f8[2][i].data_ptr(), f8[1][i].data_ptr(),
+                                          f8[3][i].data_ptr(), out.data_ptr(), ws.data_ptr(), B, T,
+                                          H, n, n, auto, 0.125, st())
+                    arms = {"append": arms["append"], "append_fp8": append8}
                 # the split threshold's evidence: explicit splits at the launch-bound batch
-                for sp in ((1, 2, 4, 8) if B == 1 else (1,)):
+                explicit = () if f8 is not None else (1, 2, 4, 8) if B == 1 else (1,)
+                for sp in explicit:
                     if sp != auto and sp <= n // 64:
                         arms[f"append_splits{sp}"] = lambda sp=sp: append(sp)
                 t = {k: [] for k in arms}
@@ -207,6 +250,9 @@ def main():
                     help="time the incremental-decoding kernel (see above)")
     ap.add_argument("--append", action="store_true",
                     help="time the append-attention kernel against its alternatives (see above)")
+    ap.add_argument("--kv_dtype", choices=["bf16", "fp8"], default="bf16",
+                    help="--decode / --append: fp8 times the FP8-cache kernels against the bf16 "
+                         "ones on the same ring, arms alternating")
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--seq", type=int, default=128)
     ap.add_argument("--heads", type=int, default=12)

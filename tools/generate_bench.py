@@ -153,6 +153,9 @@ def main():
     ap.add_argument("--new", type=int, default=128)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--sample", action="store_true")
+    ap.add_argument("--kv_dtype", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: generate(kv_dtype='fp8') against the bf16 cache instead of the "
+                         "recompute arm; same_tokens is then the share of greedy tokens that agree")
     a = ap.parse_args()
     if a.sample:
         return sample_bench(a)
@@ -167,6 +170,8 @@ def main():
     lens = torch.full((B,), P)
     arms = {"kv_cache": lambda: model.generate(prompt, lens, a.new),
             "recompute": lambda: recompute(model, prompt, P, a.new)}
+    if a.kv_dtype == "fp8":
+        arms["recompute"] = lambda: model.generate(prompt, lens, a.new, kv_dtype="fp8")
     times = {k: [] for k in arms}
     outs = {}
     for r in range(a.rounds + 1):                     # round 0 warms both arms up
@@ -180,8 +185,11 @@ def main():
     med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
     cfg = model.cfg
     Hd, I = cfg.hidden_size, cfg.intermediate_size
+    if a.kv_dtype == "fp8":                           # the second arm is the FP8 cache
+        arms = {"kv_cache": None, "kv_cache_fp8": None}
+        times["kv_cache_fp8"], outs["kv_cache_fp8"] = times.pop("recompute"), outs["recompute"]
     rec = {"probe": "generate", "model": "bert_base", "B": B, "prompt": P, "new": a.new,
-           "rounds": a.rounds,
+           "rounds": a.rounds, "kv_dtype": a.kv_dtype,
            "same_tokens": float((outs["kv_cache"] == outs["recompute"]).float().mean()),
            "decode_gemm_native": {f"{n}x{k}": bool(native._dense_gemm_native(B, n, k))
                                   for n, k in ((3 * Hd, Hd), (Hd, Hd), (I, Hd), (Hd, I))}}
@@ -189,7 +197,10 @@ def main():
         rec[f"{k}_s"] = round(med(times[k]), 4)
         rec[f"{k}_spread_s"] = [round(min(times[k]), 4), round(max(times[k]), 4)]
         rec[f"{k}_tokens_per_sec"] = round(B * a.new / med(times[k]), 1)
-    rec["speedup"] = round(med(times["recompute"]) / med(times["kv_cache"]), 2)
+    if a.kv_dtype == "fp8":                           # of the FP8 cache over the bf16 one
+        rec["speedup"] = round(med(times["kv_cache"]) / med(times["kv_cache_fp8"]), 2)
+    else:
+        rec["speedup"] = round(med(times["recompute"]) / med(times["kv_cache"]), 2)
     print(json.dumps(rec), flush=True)
 
 
