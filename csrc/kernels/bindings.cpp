@@ -954,6 +954,15 @@ PYBIND11_MODULE(_dtf_hip, m) {
      py::arg("k_scale"), py::arg("v_scale"), py::arg("out"), py::arg("ws"), py::arg("B"),
      py::arg("T"), py::arg("H"), py::arg("C"), py::arg("max_len"), py::arg("splits"),
      py::arg("scale"), py::arg("st"));
+  m.def("dense_skinny_splits", &dtf_dense_skinny_splits, py::arg("M"), py::arg("N"), py::arg("K"));
+  m.def("dense_skinny", [](uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t y, uintptr_t ws,
+                           int M, int N, int K, int ldx, int epi, int splits, uintptr_t st) {
+    dtf_dense_skinny(P<const bf16_t>(x), P<const bf16_t>(w), P<const float>(bias), P<bf16_t>(y),
+                     P<float>(ws), M, N, K, ldx, epi, splits, S(st));
+    check_launch("dense_skinny");
+  }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("y"), py::arg("ws"), py::arg("M"),
+     py::arg("N"), py::arg("K"), py::arg("ldx"), py::arg("epi"), py::arg("splits"),
+     py::arg("st"));
   m.def("sample_max_keys", &dtf_sample_max_keys, py::arg("large"));
   m.def("sample_tokens", [](uintptr_t logits, uintptr_t counter, uintptr_t tokens,
                             uintptr_t logprob, int B, int V, int ld, uint32_t seed,

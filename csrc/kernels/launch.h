@@ -512,6 +512,20 @@ void dtf_attn_append_f8(const bf16_t* qkv_new, const int* pos, const int* n_new,
                         int B, int T, int H, int C, int max_len, int splits, float scale,
                         hipStream_t st);
 
+// ---- dense_skinny.hip: y[M, N] = epi(x[M, K] @ W[N, K]^T + b[N]) for 1 <= M <= 64 (decode steps)
+struct DenseSkinnyArgs {
+  const bf16_t* x;         // [M, K], row stride ldx
+  const bf16_t* w;         // [N, K] contiguous
+  const float* bias;       // [N] (epi != 0)
+  bf16_t* y;               // [M, N] contiguous
+  float* ws;               // [splits, M, N] partials (splits > 1)
+  int M, N, K, ldx, splits;
+  int epi;                 // 0 none, 1 bias, 2 bias + GELU
+};
+int dtf_dense_skinny_splits(int M, int N, int K);
+void dtf_dense_skinny(const bf16_t* x, const bf16_t* w, const float* bias, bf16_t* y, float* ws,
+                      int M, int N, int K, int ldx, int epi, int splits, hipStream_t st);
+
 // ---- sample.hip: top-k / top-p filtering and the draw of one token per logits row, one kernel
 struct SampleArgs {
   const bf16_t* logits;    // [B, ld], columns >= V are padding

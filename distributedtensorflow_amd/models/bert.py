@@ -49,6 +49,26 @@ def padded_vocab(v: int) -> int:
 # FFN: bias + GELU + second GEMM as one op whose data gradient carries the GELU derivative in our
 # GEMM's epilogue (A/B knob)
 FUSE_GELU_DGRAD = os.environ.get("DTF_BERT_FUSE_GELU_DGRAD", "1") == "1"
+# the skinny-M weight-streaming kernel (ops.dense(impl="skinny")) serves up to this many rows; a
+# decode or extend call with more keeps the default GEMMs even under gemm="skinny"
+SKINNY_MAX_ROWS = 64
+# ... and a GEMM wider than SKINNY_WIDE outputs only up to this many rows.  Measured
+# (tools/dense_bench.py, profiles/SKINNY.md): the 30528 x 768 vocabulary GEMM takes 21.1 us
+# against 22.2 at 32 rows, but 22.0 against 21.7 at 33, 26.0 against 20.9 at 48 and 31.3 against
+# 21.5 at 64 (every further row tile re-reads x from L2 for each of the 1908 column tiles); the
+# layer GEMMs, up to 3072 wide, win at all of 1 to 64 rows.  Widths in between: not measured.
+SKINNY_MAX_ROWS_WIDE = 32
+SKINNY_WIDE = 3072
+
+
+def _skinny(gemm, rows, width=0):
+    """The ``impl`` for a GEMM with ``width`` outputs in a decode / extend call over ``rows`` rows:
+    "skinny" when asked for and the rows fit, else None (today's path).  Decided on the host from
+    the shapes."""
+    if gemm not in (None, "default", "skinny"):
+        raise ValueError(f"gemm must be None, 'default' or 'skinny', got {gemm!r}")
+    most = SKINNY_MAX_ROWS_WIDE if width > SKINNY_WIDE else SKINNY_MAX_ROWS
+    return "skinny" if gemm == "skinny" and rows <= most else None
 
 
 @dataclasses.dataclass
@@ -99,8 +119,8 @@ class _Dense(nn.Module):
         self.kernel = _param((n_out, n_in), f"{name}/kernel", std, "OI")
         self.bias = _param((n_out,), f"{name}/bias", fill=0.0)
 
-    def gemm(self, x):
-        return ops.dense(x, self.kernel, None, impl=BERT_GEMM)
+    def gemm(self, x, impl=None):
+        return ops.dense(x, self.kernel, None, impl=impl or BERT_GEMM)
 
 
 class _LayerNorm(nn.Module):
@@ -144,36 +164,44 @@ class BertLayer(nn.Module):
                                 causal=cfg.causal)
         return self._after_attention(x, ctx)
 
-    def decode(self, x, k_cache, v_cache, pos, max_len=None, k_scale=None, v_scale=None):
+    def decode(self, x, k_cache, v_cache, pos, max_len=None, k_scale=None, v_scale=None,
+               gemm=None):
         """One new token per sequence (x [B, H]) at positions ``pos`` against this layer's cache,
         which takes the token's key and value in place (``k_scale`` / ``v_scale``: an FP8 cache's
-        row scales)."""
-        qkv = ops.dense(x, self.qkv_kernel, self.qkv_bias, impl=BERT_GEMM)
+        row scales).  ``gemm="skinny"``: the QKV and output projections and the FFN run on the
+        weight-streaming kernel when B <= 64."""
+        impl = _skinny(gemm, x.shape[0])
+        qkv = ops.dense(x, self.qkv_kernel, self.qkv_bias, impl=impl or BERT_GEMM)
         ctx = ops.attention_decode(qkv, k_cache, v_cache, pos, self.cfg.num_attention_heads,
                                    max_len=max_len, k_scale=k_scale, v_scale=v_scale)
-        return self._after_attention(x, ctx)
+        return self._after_attention(x, ctx, impl)
 
     def extend(self, x, k_cache, v_cache, pos, n_new, T, max_len=None, k_scale=None,
-               v_scale=None):
+               v_scale=None, gemm=None):
         """T new tokens per sequence (x [B*T, H]), the first ``n_new[b]`` of them real, at
         positions ``pos[b] ..`` against this layer's cache, which takes their keys and values in
-        place (``ops.attention_append``)."""
-        qkv = ops.dense(x, self.qkv_kernel, self.qkv_bias, impl=BERT_GEMM)
+        place (``ops.attention_append``).  ``gemm="skinny"``: as :meth:`decode`, when B*T <= 64."""
+        impl = _skinny(gemm, x.shape[0])
+        qkv = ops.dense(x, self.qkv_kernel, self.qkv_bias, impl=impl or BERT_GEMM)
         ctx = ops.attention_append(qkv, k_cache, v_cache, pos, self.cfg.num_attention_heads,
                                    n_new=n_new, max_len=max_len, k_scale=k_scale,
                                    v_scale=v_scale)
-        return self._after_attention(x, ctx)
+        return self._after_attention(x, ctx, impl)
 
-    def _after_attention(self, x, ctx):
+    def _after_attention(self, x, ctx, impl=None):
         cfg = self.cfg
-        a = self.attn_out.gemm(ctx)
+        a = self.attn_out.gemm(ctx, impl)
         # x feeds the QKV dense above and the residual here: its two gradients are summed by
         # that dense's dgrad GEMM (beta = 1), not by a separate add
         x = ops.bias_dropout_add_layer_norm(a, self.attn_out.bias, x, self.attn_ln.gamma,
                                             self.attn_ln.beta, cfg.hidden_dropout_prob,
                                             self.training, cfg.layer_norm_eps,
                                             residual_to_dense=True)
-        if FUSE_GELU_DGRAD and BERT_GEMM == "library":
+        if impl == "skinny":
+            # a decode step's FFN: two launches of the skinny-M kernel, bias + GELU in the first
+            o = ops.dense_gelu_dense(x, self.inter.kernel, self.inter.bias, self.out.kernel,
+                                     impl=impl)
+        elif FUSE_GELU_DGRAD and BERT_GEMM == "library":
             # the whole FFN as one op: the first GEMM applies bias + GELU in its epilogue (our
             # MFMA GEMM); the backward forms d(pre-activation) in one GEMM pass with the GELU
             # derivative in the epilogue (ops.native.dense_gelu_dense / _BiasGeluDense)
@@ -266,13 +294,17 @@ class BertForPreTraining(Layer):
             return logits if logits.shape[-1] == V else logits[:, :V]
         return ops.mlm_loss(logits, masked_lm_ids, masked_lm_weights, vocab=V)
 
-    def _head(self, h):
+    def _head(self, h, gemm=None):
         """Hidden rows [N, H] -> logits over the padded vocabulary [N, Vp] (the padding logits
-        are exactly 0)."""
-        h = ops.bias_gelu(self.mlm_transform.gemm(h), self.mlm_transform.bias)
+        are exactly 0).  ``gemm="skinny"``: the transform and vocabulary GEMMs on the
+        weight-streaming kernel when N <= 64 (the vocabulary GEMM: N <= 32, see
+        SKINNY_MAX_ROWS_WIDE)."""
+        impl = _skinny(gemm, h.shape[0])
+        h = ops.bias_gelu(self.mlm_transform.gemm(h, impl), self.mlm_transform.bias)
         h = ops.bias_dropout_add_layer_norm(h, None, None, self.mlm_ln.gamma, self.mlm_ln.beta,
                                             0.0, self.training, self.cfg.layer_norm_eps)
-        return ops.dense(h, self.word_embeddings, self.mlm_bias, impl=BERT_GEMM)
+        impl = _skinny(gemm, h.shape[0], self.word_embeddings.shape[0])
+        return ops.dense(h, self.word_embeddings, self.mlm_bias, impl=impl or BERT_GEMM)
 
     # ------------------------------------------------------------------------- generation
     def _check_prompts(self, input_ids, prompt_lens):
@@ -285,14 +317,15 @@ class BertForPreTraining(Layer):
         return lens
 
     @torch.no_grad()
-    def prefill(self, input_ids, prompt_lens, cache, _padded=False, chunk=None):
+    def prefill(self, input_ids, prompt_lens, cache, _padded=False, chunk=None, gemm=None):
         """The causal forward over the right-padded prompts [B, Sp] (``prompt_lens``: CPU lengths
         in [1, Sp]): fills every layer of ``cache``, sets ``cache.pos = prompt_lens`` and returns
         the logits of each row's last real position, [B, vocab_size].
 
         ``chunk=T``: the prompt goes through :meth:`extend` in ``ceil(Sp / T)`` pieces from an
         empty cache instead, piece c with ``n_new = clamp(prompt_lens - c T, 0, T)``: activation
-        memory is that of T tokens per row and Sp needs no padding to a multiple of 64."""
+        memory is that of T tokens per row and Sp needs no padding to a multiple of 64.  ``gemm``
+        goes to those :meth:`extend` calls; the one-shot forward does not take it."""
         lens = self._check_prompts(input_ids, prompt_lens)
         B, Sp = input_ids.shape
         if B != cache.batch or Sp > cache.capacity:
@@ -306,7 +339,8 @@ class BertForPreTraining(Layer):
             logits = None
             for c in range(-(-Sp // T)):
                 part = self.extend(input_ids[:, c * T:(c + 1) * T].contiguous(), cache,
-                                   (lens - c * T).clamp(0, min(T, Sp - c * T)), _padded=_padded)
+                                   (lens - c * T).clamp(0, min(T, Sp - c * T)), _padded=_padded,
+                                   gemm=gemm)
                 logits = part if logits is None else torch.where(piece_of == c, part, logits)
             return logits
         dev = input_ids.device
@@ -320,10 +354,14 @@ class BertForPreTraining(Layer):
         return logits if _padded else logits[:, :self.cfg.vocab_size]
 
     @torch.no_grad()
-    def decode_step(self, ids_new, cache, _padded=False):
+    def decode_step(self, ids_new, cache, _padded=False, gemm=None):
         """One token per sequence (``ids_new`` [B]) at positions ``cache.pos``: every layer runs
         at B rows with ``ops.attention_decode`` against its cache, ``cache.pos`` advances by one
-        on the device.  -> logits [B, vocab_size].  Nothing here reads the device."""
+        on the device.  -> logits [B, vocab_size].  Nothing here reads the device.
+
+        ``gemm="skinny"``: every GEMM of the step (four per layer and the head's two) runs on the
+        weight-streaming kernel of ``ops.dense(impl="skinny")`` when B <= 64; None or "default"
+        and larger batches keep the persistent GEMM."""
         cfg = self.cfg
         if not cfg.causal:
             raise ValueError("incremental decoding needs a causal model (BertConfig(causal=True))")
@@ -339,13 +377,13 @@ class BertForPreTraining(Layer):
         cache.max_len = min(cache.max_len + 1, cache.capacity)
         for i, layer in enumerate(self.layers):
             x = layer.decode(x, cache.k[i], cache.v[i], cache.pos, cache.max_len,
-                             *cache.layer(i)[2:])
+                             *cache.layer(i)[2:], gemm=gemm)
         cache.pos.add_(1)
-        logits = self._head(x)
+        logits = self._head(x, gemm)
         return logits if _padded else logits[:, :cfg.vocab_size]
 
     @torch.no_grad()
-    def extend(self, ids_new, cache, n_new=None, all_logits=False, _padded=False):
+    def extend(self, ids_new, cache, n_new=None, all_logits=False, _padded=False, gemm=None):
         """T new tokens per sequence (``ids_new`` [B, T], the first ``n_new[b]`` of row b real;
         ``n_new``: CPU lengths in [0, T], default T everywhere) at positions ``cache.pos[b] ..``:
         every layer runs at B*T rows with ``ops.attention_append`` against its cache and
@@ -355,7 +393,8 @@ class BertForPreTraining(Layer):
         A row with ``n_new == 0`` and, with ``all_logits``, the positions at or past ``n_new[b]``
         return logits that callers must not use.  The capacity is checked on the host against
         ``cache.max_len``, the host's bound on ``cache.pos`` (``cache.reset()`` and ``prefill``
-        set it); nothing here reads the device."""
+        set it); nothing here reads the device.  ``gemm="skinny"``: as :meth:`decode_step`, for
+        the layers when B*T <= 64 and for the head when its rows are."""
         cfg = self.cfg
         if not cfg.causal:
             raise ValueError("incremental decoding needs a causal model (BertConfig(causal=True))")
@@ -379,19 +418,19 @@ class BertForPreTraining(Layer):
         launch_len = max(T, min(cache.max_len + T, cache.capacity))
         for i, layer in enumerate(self.layers):
             x = layer.extend(x, cache.k[i], cache.v[i], cache.pos, n_d, T, launch_len,
-                             *cache.layer(i)[2:])
+                             *cache.layer(i)[2:], gemm=gemm)
         cache.pos.add_(n_d)
         cache.max_len = min(cache.max_len + int(n.max()), cache.capacity)
         if not all_logits:
             last = torch.arange(B, device=dev) * T + (n_d.long() - 1).clamp(min=0)
             x = x.index_select(0, last)
-        logits = self._head(x)
+        logits = self._head(x, gemm)
         logits = logits if _padded else logits[:, :cfg.vocab_size]
         return logits.view(B, T, -1) if all_logits else logits
 
     def generate(self, input_ids, prompt_lens, max_new_tokens, temperature=0.0, top_k=0,
                  eos_id=None, generator=None, top_p=1.0, seed=None, return_logprobs=False,
-                 prefill_chunk=None, kv_dtype=None):
+                 prefill_chunk=None, kv_dtype=None, decode_gemm=None):
         """Continue the right-padded prompts [B, Sp] by ``max_new_tokens`` tokens -> int64
         [B, max_new_tokens].  Greedy at ``temperature == 0``; otherwise softmax sampling of
         ``logits / temperature`` over the ``top_k`` largest (all when 0) with ``generator``.  A row
@@ -405,8 +444,12 @@ class BertForPreTraining(Layer):
         where ``eos_id`` replaced it).  ``generator`` is not used then.
 
         ``prefill_chunk=T`` feeds the prompt through ``prefill(chunk=T)``, T tokens at a time.
-        ``kv_dtype="fp8"`` keeps the keys and values in an FP8 cache (:class:`KVCache`)."""
+        ``kv_dtype="fp8"`` keeps the keys and values in an FP8 cache (:class:`KVCache`).
+        ``decode_gemm="skinny"`` runs the GEMMs of every decode step, and of a chunked prefill's
+        pieces of at most 64 rows, on the weight-streaming kernel (:meth:`decode_step`); None or
+        "default" is the persistent GEMM."""
         lens = self._check_prompts(input_ids, prompt_lens)
+        _skinny(decode_gemm, 1)
         if seed is None and (top_p != 1.0 or return_logprobs):
             raise ValueError("top_p and return_logprobs need the seeded path: pass seed=")
         if max_new_tokens < 1:
@@ -432,7 +475,7 @@ class BertForPreTraining(Layer):
                     logits = self.prefill(input_ids, lens, cache, _padded=fused)
                 else:
                     logits = self.prefill(input_ids, lens, cache, _padded=fused,
-                                          chunk=prefill_chunk)
+                                          chunk=prefill_chunk, gemm=decode_gemm)
                 for t in range(max_new_tokens):
                     if fused:
                         tok, lps[:, t] = ops.sample_tokens(logits, seed, cache.pos, temperature,
@@ -444,7 +487,7 @@ class BertForPreTraining(Layer):
                         done = done | (tok == eos_id)
                     out[:, t] = tok
                     if t + 1 < max_new_tokens:
-                        logits = self.decode_step(tok, cache, _padded=fused)
+                        logits = self.decode_step(tok, cache, _padded=fused, gemm=decode_gemm)
         finally:
             self.train(was_training)
         return (out, lps) if return_logprobs else out

@@ -178,7 +178,10 @@ def dense(x, w, b=None, relu=False, impl=None, layout="OI"):
     epilogues (tf.layers.dense); "library" = the bias-in-epilogue form BERT uses: its forward and
     data gradient run on our persistent MFMA GEMM (gemm_pp2) for every shape that kernel takes
     (N % 8 == 0, K % 64 == 0 -- all BERT-base layers, the tied decoder on its padded vocabulary
-    included) and fall back to hipBLASLt only for other shapes.
+    included) and fall back to hipBLASLt only for other shapes; "skinny" = the weight-streaming
+    kernel for the 1 to 64 rows of a decode step (forward only: N % 16 == 0, K % 64 == 0, under
+    ``torch.no_grad()`` or with inputs that do not require grad; anything else is a ValueError).
+    The reference path ignores ``impl``.
     ``layout``: "OI" (kernel [out, in], tf.layers / BERT) or "IO" ([in, out], the MLP template's
     ``tf.nn.xw_plus_b`` weights)."""
     if _f32(x):
@@ -284,11 +287,13 @@ def bias_gelu_dense(a, bias, w):
     return reference.dense(reference.bias_gelu(a, bias), w)
 
 
-def dense_gelu_dense(x, w1, b1, w2):
+def dense_gelu_dense(x, w1, b1, w2, impl=None):
     """gelu(x @ w1^T + b1) @ w2^T (w [out, in]): BERT's FFN.  Native: the first GEMM carries
-    the bias + GELU in its epilogue and also writes the pre-activation for the backward."""
+    the bias + GELU in its epilogue and also writes the pre-activation for the backward.
+    ``impl="skinny"`` (native path, forward only, 1 to 64 rows): both GEMMs on the
+    weight-streaming kernel of :func:`dense`'s ``impl="skinny"``; the reference path ignores it."""
     if _use_native(x):
-        return _native().dense_gelu_dense(x, w1, b1, w2)
+        return _native().dense_gelu_dense(x, w1, b1, w2, impl)
     return reference.dense(reference.bias_gelu(reference.dense(x, w1), b1), w2)
 
 

@@ -1764,12 +1764,76 @@ _FFN_GEMM_GELU = os.environ.get("DTF_FFN_GEMM_GELU",
                                 "1" if _DENSE_GEMM == "native" else "0") == "1"
 
 
-def dense_gelu_dense(x, w1, b1, w2):
+SKINNY_MAX_ROWS = 64
+
+
+def _skinny_check(x, w, b, need_bias=False):
+    """The one argument check of the skinny-M kernel (csrc/kernels/dense_skinny.hip) for both ops
+    that reach it -> (x as [M, K] rows, the bf16 weight [N, K]).  Anything the kernel does not
+    take is a ValueError: ``impl="skinny"`` never falls back."""
+    if not x.is_cuda or x.dtype != _BF16:
+        raise ValueError(f"skinny dense expects CUDA bf16 activations, got {x.dtype} on {x.device}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w, b)):
+        raise ValueError("skinny dense is forward-only: call it under torch.no_grad() or with "
+                         "inputs that do not require grad")
+    if w.dim() != 2 or x.dim() < 1 or x.shape[-1] != w.shape[1]:
+        raise ValueError(f"skinny dense: x {tuple(x.shape)} does not match w {tuple(w.shape)}")
+    if need_bias and b is None:
+        raise ValueError("skinny dense: this epilogue needs a bias")
+    N, K = w.shape
+    x2 = x if x.dim() == 2 else x.reshape(-1, K)
+    M = x2.shape[0]
+    if not 1 <= M <= SKINNY_MAX_ROWS:
+        raise ValueError(f"skinny dense takes 1 to {SKINNY_MAX_ROWS} rows, got {M}")
+    if N % 16 or K % 64 or K < 64:
+        raise ValueError(f"skinny dense needs N % 16 == 0 and K % 64 == 0, got N {N}, K {K}")
+    if x2.stride(1) != 1 or x2.stride(0) % 8 or x2.stride(0) < K or x2.data_ptr() % 16:
+        raise ValueError(f"skinny dense needs unit-stride, 16-B aligned rows of x, got strides "
+                         f"{tuple(x2.stride())}")
+    if b is not None and b.numel() != N:
+        raise ValueError(f"skinny dense: bias of {b.numel()} for {N} outputs")
+    wb = _bf16_weight(w)
+    if not wb.is_contiguous():
+        raise ValueError("skinny dense needs a contiguous [out, in] weight")
+    return x2, wb
+
+
+def _skinny_launch(x2, wb, b, epi, splits=0):
+    M, (N, K) = x2.shape[0], wb.shape
+    splits = splits or _K.dense_skinny_splits(M, N, K)
+    ws = (torch.empty(splits * M * N, device=x2.device, dtype=torch.float32)
+          if splits > 1 else None)
+    b32 = None if b is None else b.detach().float().contiguous()
+    y = torch.empty(M, N, device=x2.device, dtype=_BF16)
+    _K.dense_skinny(x2.data_ptr(), wb.data_ptr(), _p(b32), y.data_ptr(), _p(ws), M, N, K,
+                    x2.stride(0), epi if b32 is not None else 0, splits, _st())
+    return y
+
+
+def _dense_skinny(x, w, b=None, gelu=False, splits=0):
+    """act(x @ w^T + b) for 1 to 64 rows on the weight-streaming kernel (``dense(impl="skinny")``;
+    ``gelu``: the bias + GELU epilogue, ``splits``: the K split, 0 = the kernel's choice)."""
+    x2, wb = _skinny_check(x, w, b, need_bias=gelu)
+    y = _skinny_launch(x2, wb, b, 2 if gelu else 1, splits)
+    return y.view(*x.shape[:-1], wb.shape[0])
+
+
+def dense_gelu_dense(x, w1, b1, w2, impl=None):
     """gelu(x @ w1^T + b1) @ w2^T -- BERT's whole FFN (w [out, in], fp32 masters, bf16 shadows).
     The first GEMM runs on our MFMA GEMM with the bias + GELU in its epilogue, writing the
     pre-activation (for the GELU backward) and the activation (for the second GEMM) in one pass
     instead of a library GEMM followed by a bias + GELU pass over its output; the rest is
-    _BiasGeluDense (the GELU derivative in the data-gradient GEMM's epilogue)."""
+    _BiasGeluDense (the GELU derivative in the data-gradient GEMM's epilogue).
+
+    ``impl="skinny"`` (forward only, 1 to 64 rows): two launches of the skinny-M kernel, the
+    first with the bias + GELU epilogue, so only the activation is written between them."""
+    if impl == "skinny":
+        x2, wb1 = _skinny_check(x, w1, b1, need_bias=True)
+        h = _skinny_launch(x2, wb1, b1, 2)
+        h2, wb2 = _skinny_check(h, w2, None)
+        return _skinny_launch(h2, wb2, None, 0).view(*x.shape[:-1], wb2.shape[0])
+    if impl is not None:
+        raise ValueError(f"dense_gelu_dense: unknown impl {impl!r}")
     _check_cuda_bf16(x)
     wb1 = _bf16_weight(w1)
     o, i = wb1.shape
@@ -1893,7 +1957,12 @@ def dense(x, w, b=None, relu=False, impl=None):
     GEMM for every shape it takes (``DTF_DENSE_GEMM=native``, the default; the fp32 bias is added
     in the epilogue, so it is not bit-identical to the hipBLASLt + bf16-bias A/B arm
     ``DTF_DENSE_GEMM=library``) and on hipBLASLt only for other shapes.  Trainable fp32 masters
-    get fp32 dW / db straight in the flat buffer."""
+    get fp32 dW / db straight in the flat buffer.  "skinny": the weight-streaming kernel for 1 to
+    64 rows (decode steps; forward only, csrc/kernels/dense_skinny.hip) -- a shape it does not take
+    or an input that requires grad is a ValueError, never another kernel."""
+    if impl == "skinny":
+        y = _dense_skinny(x, w, b)
+        return torch.relu(y) if relu else y
     impl = impl or _DENSE_IMPL
     if (impl == "native" and w.dtype == torch.float32 and x.dtype == _BF16 and x.is_cuda
             and w.dim() == 2 and x.shape[-1] % 8 == 0):

@@ -1,0 +1,109 @@
+"""The GEMMs of one decode step, each on its own: the skinny-M weight-streaming kernel
+(csrc/kernels/dense_skinny.hip) against the route the step takes today.
+
+    python tools/dense_bench.py [--rounds 5] [--iters 50] [--ms 1,8,16,64] [--splits 1,2,3,4,6]
+
+BERT-base's four layer GEMMs and the 30528 x 768 vocabulary GEMM of the head, M = 1, 8, 16, 64.
+Arms, alternating in one process, device events around ``iters`` calls, medians of ``rounds``:
+  parent  ops.dense(impl=BERT_GEMM) under no-grad with the GEMM's own bias (the FFN pair:
+          ops.dense_gelu_dense without ``impl``), what decode_step runs by default;
+  skinny  ops.dense(impl="skinny") (the FFN pair: dense_gelu_dense(impl="skinny")).
+Every call takes the next of a ring of weight copies that together exceed the 256 MB last-level
+cache, so the weights come from HBM; the weights carry bf16 shadows as after an optimizer build,
+so no arm casts them.  One JSON line per (GEMM, M): microseconds of each arm and the skinny
+kernel's GB/s over the weight bytes as a share of the 8 TB/s peak.  ``--splits`` adds the skinny
+kernel at each forced K split (through the binding) to the line.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from distributedtensorflow_amd import ops  # noqa: E402
+from distributedtensorflow_amd.models.bert import BERT_GEMM  # noqa: E402
+from distributedtensorflow_amd.ops import native  # noqa: E402
+
+PEAK_GBS = 8000.0
+RING_BYTES = 320 << 20
+# name, N, K, bias, or for the FFN pair the second GEMM's N
+GEMMS = (("qkv", 2304, 768, True), ("attn_out", 768, 768, False), ("ffn_pair", 3072, 768, 768),
+         ("ffn2", 768, 3072, False), ("vocab", 30528, 768, True))
+
+
+def _weight(n, k, gen):
+    w = torch.nn.Parameter(0.02 * torch.randn(n, k, device="cuda", generator=gen))
+    w._dtf_shadow = w.detach().to(torch.bfloat16)
+    return w
+
+
+def _med(v):
+    return sorted(v)[len(v) // 2]
+
+
+def bench(name, N, K, extra, M, a, gen):
+    pair = name == "ffn_pair"
+    wbytes = 2 * N * K + (2 * extra * N if pair else 0)
+    ring = min(512, -(-RING_BYTES // wbytes))
+    ws = [_weight(N, K, gen) for _ in range(ring)]
+    w2 = [_weight(extra, N, gen) for _ in range(ring)] if pair else None
+    b = torch.randn(N, device="cuda", generator=gen) if (pair or extra) else None
+    x = torch.randn(M, K, device="cuda", generator=gen).bfloat16()
+    if pair:
+        arms = {"parent": lambda i: ops.dense_gelu_dense(x, ws[i], b, w2[i]),
+                "skinny": lambda i: ops.dense_gelu_dense(x, ws[i], b, w2[i], impl="skinny")}
+    else:
+        arms = {"parent": lambda i: ops.dense(x, ws[i], b, impl=BERT_GEMM),
+                "skinny": lambda i: ops.dense(x, ws[i], b, impl="skinny")}
+        for s in a.splits:
+            if s <= K // 64:
+                arms[f"skinny_splits{s}"] = (
+                    lambda i, s=s: native._dense_skinny(x, ws[i], b, splits=s))
+    us = {k: [] for k in arms}
+    with torch.no_grad():
+        for r in range(a.rounds + 1):                          # round 0 warms every arm up
+            for k, fn in arms.items():
+                e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+                e0.record()
+                for i in range(a.iters):
+                    fn((r * a.iters + i) % ring)
+                e1.record()
+                torch.cuda.synchronize()
+                if r:
+                    us[k].append(e0.elapsed_time(e1) * 1e3 / a.iters)
+        same = float((arms["parent"](0).float() - arms["skinny"](0).float()).abs().max())
+    rec = {"probe": "dense_skinny", "gemm": name, "M": M, "N": N, "K": K, "ring": ring,
+           "ring_MB": round(ring * wbytes / 2 ** 20), "max_abs_diff": round(same, 4),
+           "auto_splits": native._K.dense_skinny_splits(M, N, K)}
+    for k in arms:
+        rec[f"{k}_us"] = round(_med(us[k]), 2)
+        rec[f"{k}_spread_us"] = [round(min(us[k]), 2), round(max(us[k]), 2)]
+    gbs = wbytes / (_med(us["skinny"]) * 1e-6) / 1e9
+    rec["skinny_weight_GBs"] = round(gbs)
+    rec["skinny_share_of_peak"] = round(gbs / PEAK_GBS, 3)
+    rec["speedup"] = round(_med(us["parent"]) / _med(us["skinny"]), 2)
+    print(json.dumps(rec), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--ms", default="1,8,16,64")
+    ap.add_argument("--splits", default="", help="forced K splits to time as well, e.g. 1,2,4")
+    ap.add_argument("--gemms", default=",".join(g[0] for g in GEMMS))
+    a = ap.parse_args()
+    a.splits = [int(s) for s in a.splits.split(",") if s]
+    if not torch.cuda.is_available():
+        raise SystemExit("dense_bench needs a GPU")
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    for name, N, K, extra in GEMMS:
+        if name in a.gemms.split(","):
+            for M in (int(m) for m in a.ms.split(",")):
+                bench(name, N, K, extra, M, a, gen)
+
+
+if __name__ == "__main__":
+    main()

@@ -21,6 +21,12 @@ temperature 0.8, top_k 50.  One JSON line per measurement.
 ``--prefill_chunk T`` times the prefill of a 512-token prompt in one causal forward against
 ``prefill(chunk=T)`` (append attention, T tokens at a time), alternating in one process, with the
 peak of ``torch.cuda.max_memory_allocated`` of each.
+
+    python tools/generate_bench.py --decode_gemm skinny [--batch 64] [--shadows]
+
+``--decode_gemm skinny`` times ``generate(decode_gemm="skinny")`` (csrc/kernels/dense_skinny.hip)
+against plain ``generate`` instead of the recompute arm; ``--shadows`` first gives the weights the
+bf16 shadows an optimizer build leaves, so neither arm casts its fp32 masters on every call.
 """
 import argparse
 import json
@@ -156,13 +162,25 @@ def main():
     ap.add_argument("--kv_dtype", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: generate(kv_dtype='fp8') against the bf16 cache instead of the "
                          "recompute arm; same_tokens is then the share of greedy tokens that agree")
+    ap.add_argument("--decode_gemm", choices=["default", "skinny"], default="default",
+                    help="skinny: generate(decode_gemm='skinny') against the default GEMMs instead "
+                         "of the recompute arm")
+    ap.add_argument("--shadows", action="store_true",
+                    help="give the weights bf16 shadows as an optimizer build does, so no GEMM of "
+                         "either arm casts its fp32 master per call")
     a = ap.parse_args()
     if a.sample:
         return sample_bench(a)
     if a.prefill_chunk:
         return prefill_bench(a)
+    if a.decode_gemm == "skinny" and a.kv_dtype == "fp8":
+        raise SystemExit("--decode_gemm skinny and --kv_dtype fp8 each replace the second arm")
     torch.manual_seed(0)
     model = bert.bert_base(causal=True).cuda().eval()
+    if a.shadows:
+        for p in model.parameters():
+            if p.dim() == 2:
+                p._dtf_shadow = p.detach().to(torch.bfloat16)
     B, P = a.batch, a.prompt
     Sp = -(-P // 64) * 64
     prompt = torch.zeros(B, Sp, dtype=torch.int64, device="cuda")
@@ -172,6 +190,10 @@ def main():
             "recompute": lambda: recompute(model, prompt, P, a.new)}
     if a.kv_dtype == "fp8":
         arms["recompute"] = lambda: model.generate(prompt, lens, a.new, kv_dtype="fp8")
+    second = {"fp8": "kv_cache_fp8"}.get(a.kv_dtype)
+    if a.decode_gemm == "skinny":
+        arms["recompute"] = lambda: model.generate(prompt, lens, a.new, decode_gemm="skinny")
+        second = "kv_cache_skinny"
     times = {k: [] for k in arms}
     outs = {}
     for r in range(a.rounds + 1):                     # round 0 warms both arms up
@@ -185,11 +207,12 @@ def main():
     med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
     cfg = model.cfg
     Hd, I = cfg.hidden_size, cfg.intermediate_size
-    if a.kv_dtype == "fp8":                           # the second arm is the FP8 cache
-        arms = {"kv_cache": None, "kv_cache_fp8": None}
-        times["kv_cache_fp8"], outs["kv_cache_fp8"] = times.pop("recompute"), outs["recompute"]
+    if second:                                        # the second arm is the FP8 cache / skinny GEMMs
+        arms = {"kv_cache": None, second: None}
+        times[second], outs[second] = times.pop("recompute"), outs["recompute"]
     rec = {"probe": "generate", "model": "bert_base", "B": B, "prompt": P, "new": a.new,
-           "rounds": a.rounds, "kv_dtype": a.kv_dtype,
+           "rounds": a.rounds, "kv_dtype": a.kv_dtype, "decode_gemm": a.decode_gemm,
+           "shadows": a.shadows,
            "same_tokens": float((outs["kv_cache"] == outs["recompute"]).float().mean()),
            "decode_gemm_native": {f"{n}x{k}": bool(native._dense_gemm_native(B, n, k))
                                   for n, k in ((3 * Hd, Hd), (Hd, Hd), (I, Hd), (Hd, I))}}
@@ -197,8 +220,8 @@ def main():
         rec[f"{k}_s"] = round(med(times[k]), 4)
         rec[f"{k}_spread_s"] = [round(min(times[k]), 4), round(max(times[k]), 4)]
         rec[f"{k}_tokens_per_sec"] = round(B * a.new / med(times[k]), 1)
-    if a.kv_dtype == "fp8":                           # of the FP8 cache over the bf16 one
-        rec["speedup"] = round(med(times["kv_cache"]) / med(times["kv_cache_fp8"]), 2)
+    if second:                                        # of the second arm over plain generate
+        rec["speedup"] = round(med(times["kv_cache"]) / med(times[second]), 2)
     else:
         rec["speedup"] = round(med(times["recompute"]) / med(times["kv_cache"]), 2)
     print(json.dumps(rec), flush=True)
