@@ -963,6 +963,21 @@ PYBIND11_MODULE(_dtf_hip, m) {
   }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("y"), py::arg("ws"), py::arg("M"),
      py::arg("N"), py::arg("K"), py::arg("ldx"), py::arg("epi"), py::arg("splits"),
      py::arg("st"));
+  m.def("dense_skinny_ln_max_width", &dtf_dense_skinny_ln_max_width);
+  m.def("dense_skinny_ln", [](uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t y, uintptr_t ws,
+                              int M, int N, int K, int ldx, int epi, int splits,
+                              uintptr_t ln_gamma, uintptr_t ln_beta, float ln_eps, int ln_width,
+                              uintptr_t res, int ldres, int res_is_ln, int pre_ln, uintptr_t st) {
+    const DenseSkinnyLnArgs a{{P<const bf16_t>(x), P<const bf16_t>(w), P<const float>(bias),
+                               P<bf16_t>(y), P<float>(ws), M, N, K, ldx, splits, epi},
+                              P<const float>(ln_gamma), P<const float>(ln_beta),
+                              P<const bf16_t>(res), ln_eps, ln_width, ldres, pre_ln, res_is_ln};
+    dtf_dense_skinny_ln(a, S(st));
+    check_launch("dense_skinny_ln");
+  }, py::arg("x"), py::arg("w"), py::arg("bias"), py::arg("y"), py::arg("ws"), py::arg("M"),
+     py::arg("N"), py::arg("K"), py::arg("ldx"), py::arg("epi"), py::arg("splits"),
+     py::arg("ln_gamma"), py::arg("ln_beta"), py::arg("ln_eps"), py::arg("ln_width"),
+     py::arg("res"), py::arg("ldres"), py::arg("res_is_ln"), py::arg("pre_ln"), py::arg("st"));
   m.def("sample_max_keys", &dtf_sample_max_keys, py::arg("large"));
   m.def("sample_tokens", [](uintptr_t logits, uintptr_t counter, uintptr_t tokens,
                             uintptr_t logprob, int B, int V, int ld, uint32_t seed,

@@ -30,6 +30,30 @@
 //     profiles/DECODE.md), less where the x operands of more row tiles need the registers.
 //   * Epilogues: 0 none, 1 + b[n], 2 gelu(. + b[n]) with the gelu_f of common.h that
 //     bias_gelu_fwd_kernel applies -- on the fp32 sum, so the result rounds once.
+//
+// Deferred LayerNorm (dense_skinny_ln_kernel<MT, PRE, RES>, dtf_dense_skinny_ln).  A decode
+// step's bias + residual + LayerNorm launches move at most 64 x 768 elements each and exist only
+// because LayerNorm wants whole rows while this kernel splits the columns over blocks.  Here the
+// kernel that forms a sub-layer's sum r = a + bias + residual stores r UN-normalised and every
+// consumer of LN(r) normalises it itself, lnb(r) = bf16(((r - mean) * rstd) * gamma + beta) with
+// fp32 statistics over the stored bf16 row and the biased variance (reference.layer_norm, rounded
+// once).  No block waits for another; the determinism rule above holds.
+//   * PRE: y = epi(lnb(x) @ W^T + b).  A lane's 16 B of x are unpacked, normalised with the row's
+//     mean / rstd and the gamma / beta of those 8 k (two float4 loads each, shared by the row
+//     tiles) and packed again just before the MFMA.  Rows at or past M are neither loaded nor
+//     normalised: their operand is the same select to zero.
+//   * RES = 1: y = bf16(x @ W^T + b + res), res a bf16 [M, N] matrix; RES = 2: res is lnb(res).
+//     Added to the fp32 sum after the bias (epi == 1 only), by the block or, with K splits, by
+//     dense_skinny_combine_ln_kernel.
+//   * Statistics: every block forms mean / rstd of all M rows of the one normalised matrix
+//     itself.  Row m goes to wave m % 4; a wave loads all of its up to 4 MT rows first (16 B per
+//     lane and 512 columns, so kLnMaxWidth = 1024 is two loads a row), then reduces each row TWICE
+//     from those registers: the mean, then the sum of centred squares (E[x^2] - mean^2 cancels
+//     for rows with a common offset).  Results go to LDS as float2[64].  PRE: a prologue, after
+//     the wave has issued its first batch of W loads (which do not depend on it); RES = 2: between
+//     the main loop and the merge, whose barrier then also publishes the statistics.
+//   * Width of the normalised rows: a multiple of 16 up to kLnMaxWidth (BERT-large's hidden size;
+//     a third load per row was not tried).
 #include <stdexcept>
 #include <string>
 
@@ -171,6 +195,263 @@ constexpr int kMaxM = 64;
 // measured K: two splits need K >= 8192.  Larger K: not measured.
 constexpr int kMinSplitUnits = 64;
 
+// ---- deferred LayerNorm
+constexpr int kLnMaxWidth = 1024;
+constexpr int kLnV = kLnMaxWidth / 512;      // 16-B loads a lane makes of one row
+
+// mean / rstd of rows m_lo + w, m_lo + w + 4, ... < m_hi (RW of them at most) of r -> st[row].
+// Every load first, then two passes over the registers per row; rows past m_hi reduce zeros, so
+// the RW reductions are straight-line code the scheduler can interleave.
+template <int RW>
+DTF_DEV void row_stats(const DenseSkinnyLnArgs& h, const bf16_t* r, int ld, int m_lo, int m_hi,
+                       int w, int lane, float2* st) {
+  const int pieces = h.ln_width / 8;
+  const float inv = 1.f / (float)h.ln_width;
+  uint4 v[RW][kLnV];
+#pragma unroll
+  for (int i = 0; i < RW; ++i)
+#pragma unroll
+    for (int j = 0; j < kLnV; ++j) {
+      v[i][j] = make_uint4(0u, 0u, 0u, 0u);
+      if (m_lo + w + kWaves * i < m_hi && lane + 64 * j < pieces)
+        v[i][j] = *reinterpret_cast<const uint4*>(r + (size_t)(m_lo + w + kWaves * i) * ld +
+                                                  8 * (lane + 64 * j));
+    }
+#pragma unroll
+  for (int i = 0; i < RW; ++i) {
+    float f[kLnV][8], s = 0.f, sq = 0.f;
+#pragma unroll
+    for (int j = 0; j < kLnV; ++j) {
+      unpack8(v[i][j], f[j]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s += f[j][e];
+    }
+    const float mean = wave_sum(s) * inv;
+#pragma unroll
+    for (int j = 0; j < kLnV; ++j)
+      if (lane + 64 * j < pieces) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float d = f[j][e] - mean;
+          sq += d * d;
+        }
+      }
+    const float rstd = rsqrtf(wave_sum(sq) * inv + h.ln_eps);
+    const int m = m_lo + w + kWaves * i;
+    if (lane == 0 && m < m_hi) st[m] = make_float2(mean, rstd);
+  }
+}
+
+// lnb of 8 consecutive elements v with their gamma gm / beta bt, packed as one MFMA operand
+DTF_DEV bf16x8_t lnb8(const uint4& v, float2 ms, const float (&gm)[8], const float (&bt)[8]) {
+  float f[8];
+  unpack8(v, f);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) f[e] = ((f[e] - ms.x) * ms.y) * gm[e] + bt[e];
+  return __builtin_bit_cast(bf16x8_t, pack8(f));
+}
+
+template <int NB>
+DTF_DEV void load_w(const bf16_t* wp, int u, bf16x8_t (&b)[NB][2]) {
+#pragma unroll
+  for (int i = 0; i < NB; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      b[i][j] = *reinterpret_cast<const bf16x8_t*>(wp + (size_t)(u + i) * kUnit + 32 * j);
+}
+
+// run_units with the A operand normalised on load and W already in registers: ms[t] is the
+// (mean, rstd) of the lane's row of tile t, gp / bp point at the lane's k-group of gamma / beta
+template <int MT, int NB>
+DTF_DEV void mma_units_ln(const bf16x8_t (&b)[NB][2], const bf16_t* const (&xp)[MT],
+                          const bool (&live)[MT], const float2 (&ms)[MT], const float* gp,
+                          const float* bp, int u, int nb, f32x4_t (&acc)[MT]) {
+  uint4 a[MT][NB][2];
+#pragma unroll
+  for (int t = 0; t < MT; ++t)
+#pragma unroll
+    for (int i = 0; i < NB; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        a[t][i][j] = make_uint4(0u, 0u, 0u, 0u);
+        if (live[t] && i < nb)
+          a[t][i][j] = *reinterpret_cast<const uint4*>(xp[t] + (size_t)(u + i) * kUnit + 32 * j);
+      }
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    if (i >= nb) break;                    // wave-uniform: a first batch shorter than NB units
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      float gm[8], bt[8];
+      load8f(gp, (u + i) * kUnit + 32 * j, gm);
+      load8f(bp, (u + i) * kUnit + 32 * j, bt);
+#pragma unroll
+      for (int t = 0; t < MT; ++t) {
+        bf16x8_t op = lnb8(a[t][i][j], ms[t], gm, bt);
+        if (!live[t]) op = (bf16x8_t){0, 0, 0, 0, 0, 0, 0, 0};
+        acc[t] = mfma(op, b[i][j], acc[t]);
+      }
+    }
+  }
+}
+
+// store4 with the residual: (s + b[n]) + res, res read plain (RES 1) or as lnb(res) (RES 2)
+template <int RES>
+DTF_DEV void store4_res(const DenseSkinnyLnArgs& h, const float2* st, int m, int n, float4 s) {
+  const DenseSkinnyArgs& g = h.d;
+  if constexpr (RES == 0) {
+    store4(g, m, n, s);
+  } else {
+    const float4 b = *reinterpret_cast<const float4*>(g.bias + n);
+    const uint2 rv = *reinterpret_cast<const uint2*>(h.res + (size_t)m * h.ldres + n);
+    float r[4] = {__builtin_bit_cast(float, rv.x << 16),
+                  __builtin_bit_cast(float, rv.x & 0xffff0000u),
+                  __builtin_bit_cast(float, rv.y << 16),
+                  __builtin_bit_cast(float, rv.y & 0xffff0000u)};
+    if constexpr (RES == 2) {
+      const float2 ms = st[m];
+      const float4 gm = *reinterpret_cast<const float4*>(h.ln_gamma + n);
+      const float4 bt = *reinterpret_cast<const float4*>(h.ln_beta + n);
+      r[0] = bf2f(f2bf(((r[0] - ms.x) * ms.y) * gm.x + bt.x));
+      r[1] = bf2f(f2bf(((r[1] - ms.x) * ms.y) * gm.y + bt.y));
+      r[2] = bf2f(f2bf(((r[2] - ms.x) * ms.y) * gm.z + bt.z));
+      r[3] = bf2f(f2bf(((r[3] - ms.x) * ms.y) * gm.w + bt.w));
+    }
+    s.x = (s.x + b.x) + r[0]; s.y = (s.y + b.y) + r[1];
+    s.z = (s.z + b.z) + r[2]; s.w = (s.w + b.w) + r[3];
+    *reinterpret_cast<uint2*>(g.y + (size_t)m * g.N + n) =
+        make_uint2(pack2(s.x, s.y), pack2(s.z, s.w));
+  }
+}
+
+template <int MT, bool PRE, int RES>
+__global__ void __launch_bounds__(64 * kWaves) dense_skinny_ln_kernel(const DenseSkinnyLnArgs h) {
+  constexpr int UB = MT == 1 ? 8 : MT == 2 ? 4 : 2;       // as dense_skinny_kernel
+  const DenseSkinnyArgs& g = h.d;
+  __shared__ __attribute__((aligned(16))) float Ms[kWaves * MT * 16 * kMp];
+  __shared__ float2 St[kMaxM];
+  const int tid = threadIdx.x, lane = tid & 63, li = lane & 15, gq = lane >> 4;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int n0 = blockIdx.x * 16, split = blockIdx.y;
+  const int U = g.K / kUnit;
+  const int u0 = (int)((long)split * U / g.splits);
+  const int nu = (int)((long)(split + 1) * U / g.splits) - u0;
+  const int wu1 = u0 + (w + 1) * nu / kWaves;
+  int u = u0 + w * nu / kWaves;
+
+  const bf16_t* wp = g.w + (size_t)(n0 + li) * g.K + 8 * gq;
+  const bf16_t* xp[MT];
+  bool live[MT];
+  f32x4_t acc[MT];
+#pragma unroll
+  for (int t = 0; t < MT; ++t) {
+    live[t] = 16 * t + li < g.M;
+    xp[t] = g.x + (size_t)(16 * t + li) * g.ldx + 8 * gq;
+    acc[t] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  }
+  if constexpr (PRE) {
+    // the wave's first batch of W (whole, or one unit of a shorter share) is in flight while
+    // the block forms the statistics of x
+    const int nb0 = u + UB <= wu1 ? UB : u < wu1 ? 1 : 0;
+    bf16x8_t b0[UB][2];
+#pragma unroll
+    for (int i = 0; i < UB; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        b0[i][j] = (bf16x8_t){0, 0, 0, 0, 0, 0, 0, 0};
+        if (i < nb0)
+          b0[i][j] = *reinterpret_cast<const bf16x8_t*>(wp + (size_t)(u + i) * kUnit + 32 * j);
+      }
+    row_stats<4 * MT>(h, g.x, g.ldx, 0, g.M, w, lane, St);
+    __syncthreads();
+    float2 ms[MT];
+#pragma unroll
+    for (int t = 0; t < MT; ++t) ms[t] = live[t] ? St[16 * t + li] : make_float2(0.f, 0.f);
+    const float* gp = h.ln_gamma + 8 * gq;
+    const float* bp = h.ln_beta + 8 * gq;
+    mma_units_ln<MT, UB>(b0, xp, live, ms, gp, bp, u, nb0, acc);
+    u += nb0;
+    for (; u + UB <= wu1; u += UB) {
+      bf16x8_t b[UB][2];
+      load_w<UB>(wp, u, b);
+      mma_units_ln<MT, UB>(b, xp, live, ms, gp, bp, u, UB, acc);
+    }
+    for (; u < wu1; ++u) {
+      bf16x8_t b[1][2];
+      load_w<1>(wp, u, b);
+      mma_units_ln<MT, 1>(b, xp, live, ms, gp, bp, u, 1, acc);
+    }
+  } else {
+    for (; u + UB <= wu1; u += UB) run_units<MT, UB>(wp, xp, live, u, acc);
+    for (; u < wu1; ++u) run_units<MT, 1>(wp, xp, live, u, acc);
+  }
+  mfma_fence();
+  // the residual's statistics: published by the merge barrier below
+  if constexpr (RES == 2)
+    if (g.splits == 1) row_stats<4 * MT>(h, h.res, h.ldres, 0, g.M, w, lane, St);
+
+  float* mine = Ms + w * MT * 16 * kMp;
+#pragma unroll
+  for (int t = 0; t < MT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) mine[(16 * t + 4 * gq + r) * kMp + li] = acc[t][r];
+  __syncthreads();
+
+  if (tid >= MT * 64) return;
+  const int m = tid >> 2, c = (tid & 3) * 4;
+  if (m >= g.M) return;
+  float4 s = *reinterpret_cast<const float4*>(Ms + m * kMp + c);
+#pragma unroll
+  for (int k = 1; k < kWaves; ++k) {
+    const float4 p = *reinterpret_cast<const float4*>(Ms + (k * MT * 16 + m) * kMp + c);
+    s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w;
+  }
+  if (g.splits == 1)
+    store4_res<RES>(h, St, m, n0 + c, s);
+  else
+    *reinterpret_cast<float4*>(g.ws + ((size_t)split * g.M + m) * g.N + n0 + c) = s;
+}
+
+// dense_skinny_combine_kernel with the residual; RES 2: the block first forms the statistics of
+// the rows its 256 threads touch
+template <int RES>
+__global__ void __launch_bounds__(256) dense_skinny_combine_ln_kernel(const DenseSkinnyLnArgs h,
+                                                                      int total) {
+  const DenseSkinnyArgs& g = h.d;
+  __shared__ float2 St[kMaxM];
+  const int nq = g.N / 4;
+  if constexpr (RES == 2) {
+    const int first = blockIdx.x * 256;
+    const int last = (first + 255 < total ? first + 255 : total - 1);
+    row_stats<kMaxM / kWaves>(h, h.res, h.ldres, first / nq, last / nq + 1,
+                              __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63,
+                              St);
+    __syncthreads();
+  }
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const int m = idx / nq, n = (idx % nq) * 4;
+  const float* p = g.ws + (size_t)m * g.N + n;
+  const size_t slab = (size_t)g.M * g.N;
+  float4 s = *reinterpret_cast<const float4*>(p);
+  for (int k = 1; k < g.splits; ++k) {
+    const float4 q = *reinterpret_cast<const float4*>(p + k * slab);
+    s.x += q.x; s.y += q.y; s.z += q.z; s.w += q.w;
+  }
+  store4_res<RES>(h, St, m, n, s);
+}
+
+template <bool PRE, int RES>
+void launch_ln(const DenseSkinnyLnArgs& h, dim3 grid, hipStream_t st) {
+  const dim3 block(64 * kWaves);
+  switch ((h.d.M + 15) / 16) {
+    case 1: hipLaunchKernelGGL((dense_skinny_ln_kernel<1, PRE, RES>), grid, block, 0, st, h); break;
+    case 2: hipLaunchKernelGGL((dense_skinny_ln_kernel<2, PRE, RES>), grid, block, 0, st, h); break;
+    case 3: hipLaunchKernelGGL((dense_skinny_ln_kernel<3, PRE, RES>), grid, block, 0, st, h); break;
+    default: hipLaunchKernelGGL((dense_skinny_ln_kernel<4, PRE, RES>), grid, block, 0, st, h); break;
+  }
+}
+
 }  // namespace
 
 // `splits` for a launch: enough blocks for two per CU, but no split below kMinSplitUnits units.
@@ -185,8 +466,9 @@ int dtf_dense_skinny_splits(int M, int N, int K) {
   return want < 1 ? 1 : want;
 }
 
-void dtf_dense_skinny(const bf16_t* x, const bf16_t* w, const float* bias, bf16_t* y, float* ws,
-                      int M, int N, int K, int ldx, int epi, int splits, hipStream_t st) {
+// the checks common to both entries -> the `splits` of the launch
+static int checked_splits(const bf16_t* x, const bf16_t* w, const float* bias, const bf16_t* y,
+                          const float* ws, int M, int N, int K, int ldx, int epi, int splits) {
   if (!x || !w || !y) throw std::runtime_error("dense_skinny: null pointer");
   if (M < 1 || M > kMaxM)
     throw std::runtime_error("dense_skinny: 1 <= M <= 64, got " + std::to_string(M));
@@ -208,6 +490,12 @@ void dtf_dense_skinny(const bf16_t* x, const bf16_t* w, const float* bias, bf16_
                              std::to_string(K / kUnit) + " 64-k units of K");
   if (splits > 1 && (!ws || (uintptr_t)ws % 16))
     throw std::runtime_error("dense_skinny: splits > 1 needs the workspace");
+  return splits;
+}
+
+void dtf_dense_skinny(const bf16_t* x, const bf16_t* w, const float* bias, bf16_t* y, float* ws,
+                      int M, int N, int K, int ldx, int epi, int splits, hipStream_t st) {
+  splits = checked_splits(x, w, bias, y, ws, M, N, K, ldx, epi, splits);
   const DenseSkinnyArgs g{x, w, bias, y, ws, M, N, K, ldx, splits, epi};
   const dim3 grid(N / 16, splits), block(64 * kWaves);
   switch ((M + 15) / 16) {
@@ -220,5 +508,61 @@ void dtf_dense_skinny(const bf16_t* x, const bf16_t* w, const float* bias, bf16_
     const int total = M * (N / 4);
     hipLaunchKernelGGL(dense_skinny_combine_kernel, dim3(dtf_cdiv(total, 256)), dim3(256), 0, st,
                        g, total);
+  }
+}
+
+int dtf_dense_skinny_ln_max_width() { return kLnMaxWidth; }
+
+void dtf_dense_skinny_ln(const DenseSkinnyLnArgs& a, hipStream_t st) {
+  DenseSkinnyLnArgs h = a;
+  DenseSkinnyArgs& g = h.d;
+  g.splits = checked_splits(g.x, g.w, g.bias, g.y, g.ws, g.M, g.N, g.K, g.ldx, g.epi, g.splits);
+  const bool ln = h.pre_ln || h.res_is_ln;
+  if (!h.pre_ln && !h.res)
+    throw std::runtime_error("dense_skinny_ln: neither a normalised x nor a residual: that is "
+                             "dense_skinny");
+  if (h.pre_ln && h.res_is_ln)
+    throw std::runtime_error("dense_skinny_ln: x and the residual cannot both be normalised: a "
+                             "call holds the row statistics of one matrix");
+  if (h.res_is_ln && !h.res)
+    throw std::runtime_error("dense_skinny_ln: a normalised residual needs the residual");
+  if (h.res && g.epi != 1)
+    throw std::runtime_error("dense_skinny_ln: the residual combines with the bias epilogue only "
+                             "(epilogue 1), got " + std::to_string(g.epi));
+  if (h.res && (h.ldres < g.N || h.ldres % 8 || (uintptr_t)h.res % 16))
+    throw std::runtime_error("dense_skinny_ln: residual rows must start 16-B aligned (row stride " +
+                             std::to_string(h.ldres) + " elements) and hold N elements");
+  if (ln) {
+    if (!h.ln_gamma || !h.ln_beta || ((uintptr_t)h.ln_gamma | (uintptr_t)h.ln_beta) % 16)
+      throw std::runtime_error("dense_skinny_ln: gamma and beta must be 16-B aligned fp32");
+    if (h.ln_width != (h.pre_ln ? g.K : g.N))
+      throw std::runtime_error("dense_skinny_ln: the normalised rows are " +
+                               std::to_string(h.pre_ln ? g.K : g.N) + " wide, got ln_width " +
+                               std::to_string(h.ln_width));
+    if (h.ln_width % 16 || h.ln_width > kLnMaxWidth)
+      throw std::runtime_error("dense_skinny_ln: normalised rows must be a multiple of 16 and at "
+                               "most " + std::to_string(kLnMaxWidth) + " wide, got " +
+                               std::to_string(h.ln_width));
+    if (!(h.ln_eps >= 0.f) || h.ln_eps > 1.f)
+      throw std::runtime_error("dense_skinny_ln: eps must be in [0, 1]");
+  }
+  const dim3 grid(g.N / 16, g.splits);
+  const int res = !h.res ? 0 : h.res_is_ln ? 2 : 1;
+  if (h.pre_ln) {
+    if (res == 0) launch_ln<true, 0>(h, grid, st);
+    else launch_ln<true, 1>(h, grid, st);
+  } else {
+    if (res == 1) launch_ln<false, 1>(h, grid, st);
+    else launch_ln<false, 2>(h, grid, st);
+  }
+  if (g.splits > 1) {
+    const int total = g.M * (g.N / 4);
+    const dim3 cgrid(dtf_cdiv(total, 256)), cblock(256);
+    if (res == 0)
+      hipLaunchKernelGGL(dense_skinny_combine_kernel, cgrid, cblock, 0, st, g, total);
+    else if (res == 1)
+      hipLaunchKernelGGL(dense_skinny_combine_ln_kernel<1>, cgrid, cblock, 0, st, h, total);
+    else
+      hipLaunchKernelGGL(dense_skinny_combine_ln_kernel<2>, cgrid, cblock, 0, st, h, total);
   }
 }

@@ -525,6 +525,22 @@ struct DenseSkinnyArgs {
 int dtf_dense_skinny_splits(int M, int N, int K);
 void dtf_dense_skinny(const bf16_t* x, const bf16_t* w, const float* bias, bf16_t* y, float* ws,
                       int M, int N, int K, int ldx, int epi, int splits, hipStream_t st);
+// ... with a deferred LayerNorm, lnb(r) = bf16(((r - mean) * rstd) * gamma + beta) over whole rows
+// of r: y = epi(lnb(x) @ W^T + b) (pre_ln) and / or y = x @ W^T + b + res, res a plain bf16 matrix
+// or lnb of one (res_is_ln).  A call normalises at most one matrix.
+struct DenseSkinnyLnArgs {
+  DenseSkinnyArgs d;       // d.splits == 0: chosen as dtf_dense_skinny does
+  const float* ln_gamma;   // [ln_width] (pre_ln or res_is_ln)
+  const float* ln_beta;    // [ln_width]
+  const bf16_t* res;       // [M, N], row stride ldres; null: no residual
+  float ln_eps;
+  int ln_width;            // row width of the normalised matrix: K (pre_ln) or N (res_is_ln)
+  int ldres;
+  int pre_ln;              // x is normalised on its way into the MFMA operand
+  int res_is_ln;           // the residual added is lnb(res)
+};
+int dtf_dense_skinny_ln_max_width();
+void dtf_dense_skinny_ln(const DenseSkinnyLnArgs& a, hipStream_t st);
 
 // ---- sample.hip: top-k / top-p filtering and the draw of one token per logits row, one kernel
 struct SampleArgs {

@@ -168,9 +168,11 @@ def build_parser():
     p.add_argument("--generate_kv_dtype", choices=["bf16", "fp8"], default="bf16",
                    help="the KV cache of --generate: the activation dtype, or FP8 (e4m3 bytes with "
                         "one power-of-two scale per row, 68 bytes a cached row instead of 128)")
-    p.add_argument("--generate_decode_gemm", choices=["default", "skinny"], default="default",
-                   help="the GEMMs of the decode steps of --generate: the persistent MFMA GEMM, or "
-                        "the skinny-M weight-streaming kernel (batches of up to 64 rows)")
+    p.add_argument("--generate_decode_gemm", choices=["default", "skinny", "skinny_ln"],
+                   default="default",
+                   help="the GEMMs of the decode steps of --generate: the persistent MFMA GEMM, "
+                        "the skinny-M weight-streaming kernel (batches of up to 64 rows), or that "
+                        "kernel with the layers' LayerNorms deferred into it (skinny_ln)")
     p.add_argument("--generate_seed", type=int, default=None,
                    help="pick every token with the fused on-device sampler, reproducible from "
                         "this seed (default: torch's generator seeded with --seed)")
@@ -587,8 +589,8 @@ def _generate(args, model, device, batch):
         kw["prefill_chunk"] = args.generate_prefill_chunk
     if args.generate_kv_dtype == "fp8":
         kw["kv_dtype"] = "fp8"
-    if args.generate_decode_gemm == "skinny":
-        kw["decode_gemm"] = "skinny"
+    if args.generate_decode_gemm != "default":
+        kw["decode_gemm"] = args.generate_decode_gemm
     try:
         if cuda:
             torch.cuda.synchronize()

@@ -62,13 +62,27 @@ SKINNY_WIDE = 3072
 
 
 def _skinny(gemm, rows, width=0):
-    """The ``impl`` for a GEMM with ``width`` outputs in a decode / extend call over ``rows`` rows:
-    "skinny" when asked for and the rows fit, else None (today's path).  Decided on the host from
+    """The route of a GEMM with ``width`` outputs in a decode / extend call over ``rows`` rows:
+    ``gemm`` ("skinny", or "skinny_ln": the skinny kernel with the layers' LayerNorms deferred
+    into it) when asked for and the rows fit, else None (today's path).  Decided on the host from
     the shapes."""
-    if gemm not in (None, "default", "skinny"):
-        raise ValueError(f"gemm must be None, 'default' or 'skinny', got {gemm!r}")
+    if gemm not in (None, "default", "skinny", "skinny_ln"):
+        raise ValueError(f"gemm must be None, 'default', 'skinny' or 'skinny_ln', got {gemm!r}")
     most = SKINNY_MAX_ROWS_WIDE if width > SKINNY_WIDE else SKINNY_MAX_ROWS
-    return "skinny" if gemm == "skinny" and rows <= most else None
+    return gemm if gemm in ("skinny", "skinny_ln") and rows <= most else None
+
+
+# Under gemm="skinny_ln" the hidden state between layers is a pair (t, ln): ln = (gamma, beta,
+# eps) of the LayerNorm that t still lacks, None when t is already normalised.
+def _deferred(x):
+    return x if isinstance(x, tuple) else (x, None)
+
+
+def _normalised(x):
+    """The tensor a pair stands for (one LayerNorm launch), for a consumer off the skinny path."""
+    if not isinstance(x, tuple):
+        return x
+    return x[0] if x[1] is None else ops.layer_norm(x[0], *x[1])
 
 
 @dataclasses.dataclass
@@ -169,9 +183,10 @@ class BertLayer(nn.Module):
         """One new token per sequence (x [B, H]) at positions ``pos`` against this layer's cache,
         which takes the token's key and value in place (``k_scale`` / ``v_scale``: an FP8 cache's
         row scales).  ``gemm="skinny"``: the QKV and output projections and the FFN run on the
-        weight-streaming kernel when B <= 64."""
-        impl = _skinny(gemm, x.shape[0])
-        qkv = ops.dense(x, self.qkv_kernel, self.qkv_bias, impl=impl or BERT_GEMM)
+        weight-streaming kernel when B <= 64.  ``gemm="skinny_ln"``: also the two LayerNorms, deferred
+        into those GEMMs (five launches); x may then be a ``(t, ln)`` pair and the result is one."""
+        impl = _skinny(gemm, _deferred(x)[0].shape[0])
+        qkv, x = self._qkv(x, impl)
         ctx = ops.attention_decode(qkv, k_cache, v_cache, pos, self.cfg.num_attention_heads,
                                    max_len=max_len, k_scale=k_scale, v_scale=v_scale)
         return self._after_attention(x, ctx, impl)
@@ -180,15 +195,40 @@ class BertLayer(nn.Module):
                v_scale=None, gemm=None):
         """T new tokens per sequence (x [B*T, H]), the first ``n_new[b]`` of them real, at
         positions ``pos[b] ..`` against this layer's cache, which takes their keys and values in
-        place (``ops.attention_append``).  ``gemm="skinny"``: as :meth:`decode`, when B*T <= 64."""
-        impl = _skinny(gemm, x.shape[0])
-        qkv = ops.dense(x, self.qkv_kernel, self.qkv_bias, impl=impl or BERT_GEMM)
+        place (``ops.attention_append``).  ``gemm="skinny"`` / ``"skinny_ln"``: as :meth:`decode`,
+        when B*T <= 64."""
+        impl = _skinny(gemm, _deferred(x)[0].shape[0])
+        qkv, x = self._qkv(x, impl)
         ctx = ops.attention_append(qkv, k_cache, v_cache, pos, self.cfg.num_attention_heads,
                                    n_new=n_new, max_len=max_len, k_scale=k_scale,
                                    v_scale=v_scale)
         return self._after_attention(x, ctx, impl)
 
+    def _qkv(self, x, impl):
+        """The QKV projection of a decode / extend call -> (qkv, x as the rest of the layer takes
+        it: the ``(t, ln)`` pair under "skinny_ln", whose LayerNorm the GEMM applies on load)."""
+        if impl == "skinny_ln":
+            t, ln = x = _deferred(x)
+            return ops.dense(t, self.qkv_kernel, self.qkv_bias, impl="skinny", pre_ln=ln), x
+        x = _normalised(x)
+        return ops.dense(x, self.qkv_kernel, self.qkv_bias, impl=impl or BERT_GEMM), x
+
+    def _after_attention_ln(self, t, ln, ctx):
+        """The rest of the layer with both LayerNorms deferred: the output projection stores
+        t1 = ctx W^T + b + LN(t) and the FFN pair t2 = ffn(LN(t1)) + b + LN(t1), un-normalised; a
+        decode / extend step has no dropout.  -> (t2, its LayerNorm)."""
+        eps = self.cfg.layer_norm_eps
+        t1 = ops.dense(ctx, self.attn_out.kernel, self.attn_out.bias, impl="skinny", residual=t,
+                       residual_ln=ln)
+        ln1 = (self.attn_ln.gamma, self.attn_ln.beta, eps)
+        t2 = ops.dense_gelu_dense(t1, self.inter.kernel, self.inter.bias, self.out.kernel,
+                                  impl="skinny", pre_ln=ln1, b2=self.out.bias, residual=t1,
+                                  residual_ln=ln1)
+        return t2, (self.out_ln.gamma, self.out_ln.beta, eps)
+
     def _after_attention(self, x, ctx, impl=None):
+        if impl == "skinny_ln":
+            return self._after_attention_ln(*x, ctx)
         cfg = self.cfg
         a = self.attn_out.gemm(ctx, impl)
         # x feeds the QKV dense above and the residual here: its two gradients are summed by
@@ -298,13 +338,21 @@ class BertForPreTraining(Layer):
         """Hidden rows [N, H] -> logits over the padded vocabulary [N, Vp] (the padding logits
         are exactly 0).  ``gemm="skinny"``: the transform and vocabulary GEMMs on the
         weight-streaming kernel when N <= 64 (the vocabulary GEMM: N <= 32, see
-        SKINNY_MAX_ROWS_WIDE)."""
-        impl = _skinny(gemm, h.shape[0])
-        h = ops.bias_gelu(self.mlm_transform.gemm(h, impl), self.mlm_transform.bias)
+        SKINNY_MAX_ROWS_WIDE).  ``gemm="skinny_ln"``: h may be a ``(t, ln)`` pair, whose LayerNorm
+        the transform GEMM then applies on load; the vocabulary GEMM is the "skinny" one (its 1908
+        blocks would each recompute the statistics)."""
+        impl = _skinny(gemm, _deferred(h)[0].shape[0])
+        if impl == "skinny_ln":
+            t, ln = _deferred(h)
+            h = ops.dense(t, self.mlm_transform.kernel, None, impl="skinny", pre_ln=ln)
+        else:
+            h = self.mlm_transform.gemm(_normalised(h), impl)
+        h = ops.bias_gelu(h, self.mlm_transform.bias)
         h = ops.bias_dropout_add_layer_norm(h, None, None, self.mlm_ln.gamma, self.mlm_ln.beta,
                                             0.0, self.training, self.cfg.layer_norm_eps)
         impl = _skinny(gemm, h.shape[0], self.word_embeddings.shape[0])
-        return ops.dense(h, self.word_embeddings, self.mlm_bias, impl=impl or BERT_GEMM)
+        return ops.dense(h, self.word_embeddings, self.mlm_bias,
+                         impl="skinny" if impl else BERT_GEMM)
 
     # ------------------------------------------------------------------------- generation
     def _check_prompts(self, input_ids, prompt_lens):
@@ -361,7 +409,10 @@ class BertForPreTraining(Layer):
 
         ``gemm="skinny"``: every GEMM of the step (four per layer and the head's two) runs on the
         weight-streaming kernel of ``ops.dense(impl="skinny")`` when B <= 64; None or "default"
-        and larger batches keep the persistent GEMM."""
+        and larger batches keep the persistent GEMM.  ``gemm="skinny_ln"``: the same GEMMs with
+        every layer's two LayerNorms deferred into them (``ops.dense(pre_ln=, residual_ln=)``): five
+        launches a layer instead of seven, the last layer's LayerNorm applied by the head's
+        transform GEMM; the same row limits."""
         cfg = self.cfg
         if not cfg.causal:
             raise ValueError("incremental decoding needs a causal model (BertConfig(causal=True))")
@@ -423,7 +474,8 @@ class BertForPreTraining(Layer):
         cache.max_len = min(cache.max_len + int(n.max()), cache.capacity)
         if not all_logits:
             last = torch.arange(B, device=dev) * T + (n_d.long() - 1).clamp(min=0)
-            x = x.index_select(0, last)
+            t, ln = _deferred(x)                      # a row-wise LayerNorm commutes with the pick
+            x = t.index_select(0, last) if ln is None else (t.index_select(0, last), ln)
         logits = self._head(x, gemm)
         logits = logits if _padded else logits[:, :cfg.vocab_size]
         return logits.view(B, T, -1) if all_logits else logits
@@ -446,8 +498,9 @@ class BertForPreTraining(Layer):
         ``prefill_chunk=T`` feeds the prompt through ``prefill(chunk=T)``, T tokens at a time.
         ``kv_dtype="fp8"`` keeps the keys and values in an FP8 cache (:class:`KVCache`).
         ``decode_gemm="skinny"`` runs the GEMMs of every decode step, and of a chunked prefill's
-        pieces of at most 64 rows, on the weight-streaming kernel (:meth:`decode_step`); None or
-        "default" is the persistent GEMM."""
+        pieces of at most 64 rows, on the weight-streaming kernel (:meth:`decode_step`),
+        ``"skinny_ln"`` also defers the layers' LayerNorms into it; None or "default" is the
+        persistent GEMM."""
         lens = self._check_prompts(input_ids, prompt_lens)
         _skinny(decode_gemm, 1)
         if seed is None and (top_p != 1.0 or return_logprobs):

@@ -173,7 +173,8 @@ def global_avg_pool(x):
     return reference.global_avg_pool(x)
 
 
-def dense(x, w, b=None, relu=False, impl=None, layout="OI"):
+def dense(x, w, b=None, relu=False, impl=None, layout="OI", pre_ln=None, residual=None,
+          residual_ln=None):
     """``impl`` (native path): None/"native" = the hand-written MFMA GEMM with fused bias/ReLU
     epilogues (tf.layers.dense); "library" = the bias-in-epilogue form BERT uses: its forward and
     data gradient run on our persistent MFMA GEMM (gemm_pp2) for every shape that kernel takes
@@ -183,16 +184,27 @@ def dense(x, w, b=None, relu=False, impl=None, layout="OI"):
     ``torch.no_grad()`` or with inputs that do not require grad; anything else is a ValueError).
     The reference path ignores ``impl``.
     ``layout``: "OI" (kernel [out, in], tf.layers / BERT) or "IO" ([in, out], the MLP template's
-    ``tf.nn.xw_plus_b`` weights)."""
+    ``tf.nn.xw_plus_b`` weights).
+
+    Deferred LayerNorm (native: ``impl="skinny"`` only, any other ``impl`` is a ValueError).
+    ``pre_ln=(gamma, beta, eps)``: x is the UN-normalised input of a LayerNorm and the kernel
+    normalises it on load, ``y = lnb(x) @ w^T + b`` with ``lnb`` = :func:`layer_norm` rounded to
+    x's dtype.  ``residual`` [M, out]: ``y = x @ w^T + b + residual`` on the fp32 sum (needs
+    ``b``, no ``relu``); ``residual_ln=(gamma, beta, eps)``: ``lnb(residual)`` is added instead.
+    ``pre_ln`` with ``residual_ln`` is refused (a call normalises one matrix), as are normalised
+    rows wider than 1024 on the native path."""
+    deferred = pre_ln is not None or residual is not None or residual_ln is not None
     if _f32(x):
+        if deferred:
+            raise ValueError("dense: pre_ln / residual / residual_ln need impl='skinny' (bf16)")
         return _native_f32().dense(x, w, b, relu, layout)
     if layout == "IO":
         w = w.t()
         if _use_native(x):
             w = w.contiguous()
     if _use_native(x):
-        return _native().dense(x, w, b, relu, impl)
-    return reference.dense(x, w, b, relu)
+        return _native().dense(x, w, b, relu, impl, pre_ln, residual, residual_ln)
+    return reference.dense(x, w, b, relu, pre_ln, residual, residual_ln)
 
 
 def sparse_softmax_cross_entropy(logits, labels, label_smoothing=0.0):
@@ -287,14 +299,22 @@ def bias_gelu_dense(a, bias, w):
     return reference.dense(reference.bias_gelu(a, bias), w)
 
 
-def dense_gelu_dense(x, w1, b1, w2, impl=None):
+def dense_gelu_dense(x, w1, b1, w2, impl=None, pre_ln=None, b2=None, residual=None,
+                     residual_ln=None):
     """gelu(x @ w1^T + b1) @ w2^T (w [out, in]): BERT's FFN.  Native: the first GEMM carries
     the bias + GELU in its epilogue and also writes the pre-activation for the backward.
     ``impl="skinny"`` (native path, forward only, 1 to 64 rows): both GEMMs on the
-    weight-streaming kernel of :func:`dense`'s ``impl="skinny"``; the reference path ignores it."""
+    weight-streaming kernel of :func:`dense`'s ``impl="skinny"``; the reference path ignores it.
+
+    Deferred LayerNorm, as :func:`dense` (native: ``impl="skinny"`` only): ``pre_ln`` normalises
+    x on the first GEMM's load; ``b2`` / ``residual`` / ``residual_ln`` are the second GEMM's
+    bias and residual, ``... @ w2^T + b2 + residual``.  Still two launches."""
     if _use_native(x):
-        return _native().dense_gelu_dense(x, w1, b1, w2, impl)
-    return reference.dense(reference.bias_gelu(reference.dense(x, w1), b1), w2)
+        return _native().dense_gelu_dense(x, w1, b1, w2, impl, pre_ln, b2, residual, residual_ln)
+    if pre_ln is None and b2 is None and residual is None and residual_ln is None:
+        return reference.dense(reference.bias_gelu(reference.dense(x, w1), b1), w2)
+    h = reference.bias_gelu(reference.dense(x, w1, pre_ln=pre_ln), b1)
+    return reference.dense(h, w2, b2, residual=residual, residual_ln=residual_ln)
 
 
 def attention_qkv(qkv, mask, batch, seq_len, heads, p=0.0, training=True, scale=None,

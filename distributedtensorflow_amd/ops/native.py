@@ -1767,10 +1767,14 @@ _FFN_GEMM_GELU = os.environ.get("DTF_FFN_GEMM_GELU",
 SKINNY_MAX_ROWS = 64
 
 
-def _skinny_check(x, w, b, need_bias=False):
+def _skinny_check(x, w, b, need_bias=False, pre_ln=None, residual=None, residual_ln=None):
     """The one argument check of the skinny-M kernel (csrc/kernels/dense_skinny.hip) for both ops
     that reach it -> (x as [M, K] rows, the bf16 weight [N, K]).  Anything the kernel does not
-    take is a ValueError: ``impl="skinny"`` never falls back."""
+    take is a ValueError: ``impl="skinny"`` never falls back.  ``pre_ln`` / ``residual`` /
+    ``residual_ln``: the deferred LayerNorm of ``ops.dense`` (``need_bias`` then means the GELU
+    epilogue, which takes no residual)."""
+    from .reference import deferred_ln_check
+    deferred_ln_check(pre_ln, residual, residual_ln, gelu=need_bias, bias=b is not None)
     if not x.is_cuda or x.dtype != _BF16:
         raise ValueError(f"skinny dense expects CUDA bf16 activations, got {x.dtype} on {x.device}")
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w, b)):
@@ -1795,30 +1799,70 @@ def _skinny_check(x, w, b, need_bias=False):
     wb = _bf16_weight(w)
     if not wb.is_contiguous():
         raise ValueError("skinny dense needs a contiguous [out, in] weight")
+    ln = pre_ln or residual_ln
+    if ln is not None:
+        width = K if pre_ln is not None else N
+        if width % 16 or width > _K.dense_skinny_ln_max_width():
+            raise ValueError(f"skinny dense normalises rows of a multiple of 16 up to "
+                             f"{_K.dense_skinny_ln_max_width()} elements, got {width}")
+        for t in ln[:2]:
+            if not t.is_cuda or t.numel() != width:
+                raise ValueError(f"skinny dense: LayerNorm gamma / beta must be CUDA tensors of "
+                                 f"{width} elements")
+        if not 0.0 <= float(ln[2]) <= 1.0:
+            raise ValueError(f"skinny dense: LayerNorm eps {ln[2]} outside [0, 1]")
+    if residual is not None:
+        if not residual.is_cuda or residual.dtype != _BF16 or residual.numel() != M * N:
+            raise ValueError(f"skinny dense: the residual must be CUDA bf16 with {M} x {N} "
+                             f"elements, got {residual.dtype} {tuple(residual.shape)}")
+        r2 = residual if residual.dim() == 2 else residual.reshape(M, N)
+        if (tuple(r2.shape) != (M, N) or r2.stride(1) != 1 or r2.stride(0) % 8 or
+                r2.stride(0) < N or r2.data_ptr() % 16):
+            raise ValueError(f"skinny dense needs unit-stride, 16-B aligned rows of the residual, "
+                             f"got shape {tuple(r2.shape)}, strides {tuple(r2.stride())}")
+        if residual.requires_grad and torch.is_grad_enabled():
+            raise ValueError("skinny dense is forward-only: the residual requires grad")
     return x2, wb
 
 
-def _skinny_launch(x2, wb, b, epi, splits=0):
+def _skinny_launch(x2, wb, b, epi, splits=0, pre_ln=None, residual=None, residual_ln=None):
     M, (N, K) = x2.shape[0], wb.shape
     splits = splits or _K.dense_skinny_splits(M, N, K)
     ws = (torch.empty(splits * M * N, device=x2.device, dtype=torch.float32)
           if splits > 1 else None)
     b32 = None if b is None else b.detach().float().contiguous()
     y = torch.empty(M, N, device=x2.device, dtype=_BF16)
-    _K.dense_skinny(x2.data_ptr(), wb.data_ptr(), _p(b32), y.data_ptr(), _p(ws), M, N, K,
-                    x2.stride(0), epi if b32 is not None else 0, splits, _st())
+    epi = epi if b32 is not None else 0
+    if pre_ln is None and residual is None:
+        _K.dense_skinny(x2.data_ptr(), wb.data_ptr(), _p(b32), y.data_ptr(), _p(ws), M, N, K,
+                        x2.stride(0), epi, splits, _st())
+        return y
+    ln = pre_ln or residual_ln
+    g32 = be32 = None
+    if ln is not None:
+        g32, be32 = (t.detach().float().contiguous() for t in ln[:2])
+    r2 = None if residual is None else residual.reshape(M, N)
+    _K.dense_skinny_ln(x2.data_ptr(), wb.data_ptr(), _p(b32), y.data_ptr(), _p(ws), M, N, K,
+                       x2.stride(0), epi, splits, _p(g32), _p(be32),
+                       float(ln[2]) if ln is not None else 0.0,
+                       (K if pre_ln is not None else N) if ln is not None else 0, _p(r2),
+                       r2.stride(0) if r2 is not None else 0, int(residual_ln is not None),
+                       int(pre_ln is not None), _st())
     return y
 
 
-def _dense_skinny(x, w, b=None, gelu=False, splits=0):
+def _dense_skinny(x, w, b=None, gelu=False, splits=0, pre_ln=None, residual=None,
+                  residual_ln=None):
     """act(x @ w^T + b) for 1 to 64 rows on the weight-streaming kernel (``dense(impl="skinny")``;
-    ``gelu``: the bias + GELU epilogue, ``splits``: the K split, 0 = the kernel's choice)."""
-    x2, wb = _skinny_check(x, w, b, need_bias=gelu)
-    y = _skinny_launch(x2, wb, b, 2 if gelu else 1, splits)
+    ``gelu``: the bias + GELU epilogue, ``splits``: the K split, 0 = the kernel's choice;
+    ``pre_ln`` / ``residual`` / ``residual_ln``: the deferred LayerNorm of ``ops.dense``)."""
+    x2, wb = _skinny_check(x, w, b, gelu, pre_ln, residual, residual_ln)
+    y = _skinny_launch(x2, wb, b, 2 if gelu else 1, splits, pre_ln, residual, residual_ln)
     return y.view(*x.shape[:-1], wb.shape[0])
 
 
-def dense_gelu_dense(x, w1, b1, w2, impl=None):
+def dense_gelu_dense(x, w1, b1, w2, impl=None, pre_ln=None, b2=None, residual=None,
+                     residual_ln=None):
     """gelu(x @ w1^T + b1) @ w2^T -- BERT's whole FFN (w [out, in], fp32 masters, bf16 shadows).
     The first GEMM runs on our MFMA GEMM with the bias + GELU in its epilogue, writing the
     pre-activation (for the GELU backward) and the activation (for the second GEMM) in one pass
@@ -1826,12 +1870,18 @@ def dense_gelu_dense(x, w1, b1, w2, impl=None):
     _BiasGeluDense (the GELU derivative in the data-gradient GEMM's epilogue).
 
     ``impl="skinny"`` (forward only, 1 to 64 rows): two launches of the skinny-M kernel, the
-    first with the bias + GELU epilogue, so only the activation is written between them."""
+    first with the bias + GELU epilogue, so only the activation is written between them.
+    ``pre_ln`` (first launch) and ``b2`` / ``residual`` / ``residual_ln`` (second launch): the
+    deferred LayerNorm of ``ops.dense``, with ``impl="skinny"`` only."""
     if impl == "skinny":
-        x2, wb1 = _skinny_check(x, w1, b1, need_bias=True)
-        h = _skinny_launch(x2, wb1, b1, 2)
-        h2, wb2 = _skinny_check(h, w2, None)
-        return _skinny_launch(h2, wb2, None, 0).view(*x.shape[:-1], wb2.shape[0])
+        x2, wb1 = _skinny_check(x, w1, b1, need_bias=True, pre_ln=pre_ln)
+        h = _skinny_launch(x2, wb1, b1, 2, pre_ln=pre_ln)
+        h2, wb2 = _skinny_check(h, w2, b2, residual=residual, residual_ln=residual_ln)
+        y = _skinny_launch(h2, wb2, b2, 1, residual=residual, residual_ln=residual_ln)
+        return y.view(*x.shape[:-1], wb2.shape[0])
+    if pre_ln is not None or b2 is not None or residual is not None or residual_ln is not None:
+        raise ValueError("dense_gelu_dense: pre_ln / b2 / residual / residual_ln need "
+                         "impl='skinny'")
     if impl is not None:
         raise ValueError(f"dense_gelu_dense: unknown impl {impl!r}")
     _check_cuda_bf16(x)
@@ -1950,7 +2000,7 @@ class _NativeDense(torch.autograd.Function):
         return dx, dw, db, None
 
 
-def dense(x, w, b=None, relu=False, impl=None):
+def dense(x, w, b=None, relu=False, impl=None, pre_ln=None, residual=None, residual_ln=None):
     """Dense layer.  ``impl``: "native" (default; the hand-written MFMA GEMM with fused
     bias / ReLU epilogues) or "library" -- the name is historical: the bias-in-epilogue form
     BERT uses (:class:`_Dense`), whose forward and data gradient also run on our persistent MFMA
@@ -1959,10 +2009,16 @@ def dense(x, w, b=None, relu=False, impl=None):
     ``DTF_DENSE_GEMM=library``) and on hipBLASLt only for other shapes.  Trainable fp32 masters
     get fp32 dW / db straight in the flat buffer.  "skinny": the weight-streaming kernel for 1 to
     64 rows (decode steps; forward only, csrc/kernels/dense_skinny.hip) -- a shape it does not take
-    or an input that requires grad is a ValueError, never another kernel."""
+    or an input that requires grad is a ValueError, never another kernel.  ``pre_ln`` /
+    ``residual`` / ``residual_ln``: the deferred LayerNorm of ``ops.dense``, on "skinny" only."""
     if impl == "skinny":
-        y = _dense_skinny(x, w, b)
+        if relu and residual is not None:
+            raise ValueError("skinny dense: a residual combines with the bias epilogue only")
+        y = _dense_skinny(x, w, b, pre_ln=pre_ln, residual=residual, residual_ln=residual_ln)
         return torch.relu(y) if relu else y
+    if pre_ln is not None or residual is not None or residual_ln is not None:
+        raise ValueError(f"dense: pre_ln / residual / residual_ln need impl='skinny', got "
+                         f"impl={impl!r}")
     impl = impl or _DENSE_IMPL
     if (impl == "native" and w.dtype == torch.float32 and x.dtype == _BF16 and x.is_cuda
             and w.dim() == 2 and x.shape[-1] % 8 == 0):

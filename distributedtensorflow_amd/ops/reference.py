@@ -110,10 +110,44 @@ def global_avg_pool(x):
     return x.float().mean(dim=(1, 2)).to(x.dtype)
 
 
-def dense(x, w, b=None, relu=False):
-    """x: [M, in]; w: [out, in] (GEMM 'NT' layout); b: [out]."""
-    y = F.linear(x, w.to(x.dtype), None if b is None else b.to(x.dtype))
-    return torch.relu(y) if relu else y
+def deferred_ln_check(pre_ln, residual, residual_ln, gelu=False, relu=False, bias=True):
+    """The argument rules of a dense layer with a deferred LayerNorm, one check for both backends.
+    ``pre_ln`` / ``residual_ln``: ``(gamma, beta, eps)`` of the LayerNorm that the input / the
+    residual still lacks; a call normalises at most one matrix."""
+    for ln in (pre_ln, residual_ln):
+        if ln is not None and (not isinstance(ln, (tuple, list)) or len(ln) != 3):
+            raise ValueError("dense: pre_ln / residual_ln are (gamma, beta, eps) tuples")
+    if pre_ln is not None and residual_ln is not None:
+        raise ValueError("dense: pre_ln and residual_ln cannot both be set: a call normalises "
+                         "one matrix")
+    if residual_ln is not None and residual is None:
+        raise ValueError("dense: residual_ln needs the residual it normalises")
+    if residual is not None and (gelu or relu):
+        raise ValueError("dense: a residual combines with the bias epilogue only, not with an "
+                         "activation")
+    if residual is not None and not bias:
+        raise ValueError("dense: the residual epilogue needs a bias")
+
+
+def dense(x, w, b=None, relu=False, pre_ln=None, residual=None, residual_ln=None):
+    """x: [M, in]; w: [out, in] (GEMM 'NT' layout); b: [out].  Deferred LayerNorm (the rule of the
+    skinny-M kernel): ``pre_ln`` -> the input is ``layer_norm(x, *pre_ln)``, rounded to x's dtype;
+    ``residual`` [M, out] (``residual_ln``: ``layer_norm`` of it, rounded likewise) is added to
+    the fp32 sum after the bias, so the result rounds once."""
+    if pre_ln is None and residual is None and residual_ln is None:
+        y = F.linear(x, w.to(x.dtype), None if b is None else b.to(x.dtype))
+        return torch.relu(y) if relu else y
+    deferred_ln_check(pre_ln, residual, residual_ln, relu=relu, bias=b is not None)
+    if pre_ln is not None:
+        x = layer_norm(x, *pre_ln)
+    if residual is None:
+        return dense(x, w, b, relu)
+    if residual.shape != x.shape[:-1] + w.shape[:1]:
+        raise ValueError(f"dense: residual {tuple(residual.shape)} does not match the output")
+    if residual_ln is not None:
+        residual = layer_norm(residual, *residual_ln)
+    y = F.linear(x.float(), w.to(x.dtype).float(), b.float()) + residual.float()
+    return y.to(x.dtype)
 
 
 def sparse_softmax_cross_entropy(logits, labels, label_smoothing=0.0):

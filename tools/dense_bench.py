@@ -13,6 +13,12 @@ cache, so the weights come from HBM; the weights carry bf16 shadows as after an 
 so no arm casts them.  One JSON line per (GEMM, M): microseconds of each arm and the skinny
 kernel's GB/s over the weight bytes as a share of the 8 TB/s peak.  ``--splits`` adds the skinny
 kernel at each forced K split (through the binding) to the line.
+
+    python tools/dense_bench.py --tail [--ms 1,8,16,64]
+
+``--tail`` times a whole layer from the attention output on instead, through the ops, the same
+ring and windows: ``gemm="skinny"`` (5 launches) against ``gemm="skinny_ln"`` (3 launches, the
+LayerNorms deferred into the skinny kernel); one JSON line per M.
 """
 import argparse
 import json
@@ -87,6 +93,54 @@ def bench(name, N, K, extra, M, a, gen):
     print(json.dumps(rec), flush=True)
 
 
+def bench_tail(M, a, gen, H=768, I=3072, eps=1e-12):
+    """A BERT-base layer from the attention output on, arms alternating: "skinny" (output
+    projection, bias + residual + LayerNorm kernel, FFN pair, LayerNorm kernel: 5 launches)
+    against "skinny_ln" (the LayerNorms deferred into the GEMMs: 3 launches)."""
+    ring = min(512, -(-RING_BYTES // (2 * (H * H + 2 * H * I))))
+    wo, w1, w2 = ([_weight(n, k, gen) for _ in range(ring)] for n, k in ((H, H), (I, H), (H, I)))
+    vec = lambda n, at=0.0: at + 0.1 * torch.randn(n, device="cuda", generator=gen)  # noqa: E731
+    bo, b1, b2 = vec(H), vec(I), vec(H)
+    lns = [(vec(H, 1.0), vec(H), eps) for _ in range(3)]       # of the input, attention, output
+    ctx, t = (torch.randn(M, H, device="cuda", generator=gen).bfloat16() for _ in range(2))
+
+    def skinny(i):
+        s = ops.dense(ctx, wo[i], None, impl="skinny")
+        x1 = ops.bias_dropout_add_layer_norm(s, bo, xn, lns[1][0], lns[1][1], 0.0, False, eps)
+        o = ops.dense_gelu_dense(x1, w1[i], b1, w2[i], impl="skinny")
+        return ops.bias_dropout_add_layer_norm(o, b2, x1, lns[2][0], lns[2][1], 0.0, False, eps)
+
+    def skinny_ln(i):
+        t1 = ops.dense(ctx, wo[i], bo, impl="skinny", residual=t, residual_ln=lns[0])
+        t2 = ops.dense_gelu_dense(t1, w1[i], b1, w2[i], impl="skinny", pre_ln=lns[1], b2=b2,
+                                  residual=t1, residual_ln=lns[1])
+        return t2
+
+    arms = {"skinny": skinny, "skinny_ln": skinny_ln}
+    us = {k: [] for k in arms}
+    with torch.no_grad():
+        xn = ops.layer_norm(t, *lns[0])                        # the parent arm's normalised input
+        for r in range(a.rounds + 1):                          # round 0 warms every arm up
+            for k, fn in arms.items():
+                e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+                e0.record()
+                for i in range(a.iters):
+                    fn((r * a.iters + i) % ring)
+                e1.record()
+                torch.cuda.synchronize()
+                if r:
+                    us[k].append(e0.elapsed_time(e1) * 1e3 / a.iters)
+        same =float((skinny(0).float() - ops.layer_norm(skinny_ln(0), *lns[2]).float())
+                     .abs().max())
+    rec = {"probe": "layer_tail", "M": M, "H": H, "I": I, "ring": ring,
+           "max_abs_diff": round(same, 4)}
+    for k in arms:
+        rec[f"{k}_us"] = round(_med(us[k]), 2)
+        rec[f"{k}_spread_us"] = [round(min(us[k]), 2), round(max(us[k]), 2)]
+    rec["speedup"] = round(_med(us["skinny"]) / _med(us["skinny_ln"]), 2)
+    print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -94,11 +148,17 @@ def main():
     ap.add_argument("--ms", default="1,8,16,64")
     ap.add_argument("--splits", default="", help="forced K splits to time as well, e.g. 1,2,4")
     ap.add_argument("--gemms", default=",".join(g[0] for g in GEMMS))
+    ap.add_argument("--tail", action="store_true",
+                    help="time a whole layer tail instead: 'skinny' against 'skinny_ln'")
     a = ap.parse_args()
     a.splits = [int(s) for s in a.splits.split(",") if s]
     if not torch.cuda.is_available():
         raise SystemExit("dense_bench needs a GPU")
     gen = torch.Generator(device="cuda").manual_seed(0)
+    if a.tail:
+        for M in (int(m) for m in a.ms.split(",")):
+            bench_tail(M, a, gen)
+        return
     for name, N, K, extra in GEMMS:
         if name in a.gemms.split(","):
             for M in (int(m) for m in a.ms.split(",")):

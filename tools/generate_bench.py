@@ -27,6 +27,9 @@ peak of ``torch.cuda.max_memory_allocated`` of each.
 ``--decode_gemm skinny`` times ``generate(decode_gemm="skinny")`` (csrc/kernels/dense_skinny.hip)
 against plain ``generate`` instead of the recompute arm; ``--shadows`` first gives the weights the
 bf16 shadows an optimizer build leaves, so neither arm casts its fp32 masters on every call.
+``--decode_gemm skinny_ln`` times ``generate(decode_gemm="skinny_ln")`` (the layers' LayerNorms
+deferred into the skinny kernel) against ``generate(decode_gemm="skinny")``, which then takes the
+``kv_cache_*`` fields of the line.
 """
 import argparse
 import json
@@ -162,9 +165,10 @@ def main():
     ap.add_argument("--kv_dtype", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: generate(kv_dtype='fp8') against the bf16 cache instead of the "
                          "recompute arm; same_tokens is then the share of greedy tokens that agree")
-    ap.add_argument("--decode_gemm", choices=["default", "skinny"], default="default",
+    ap.add_argument("--decode_gemm", choices=["default", "skinny", "skinny_ln"], default="default",
                     help="skinny: generate(decode_gemm='skinny') against the default GEMMs instead "
-                         "of the recompute arm")
+                         "of the recompute arm; skinny_ln: generate(decode_gemm='skinny_ln') "
+                         "against the 'skinny' arm (kv_cache_* in the output is then that arm)")
     ap.add_argument("--shadows", action="store_true",
                     help="give the weights bf16 shadows as an optimizer build does, so no GEMM of "
                          "either arm casts its fp32 master per call")
@@ -173,8 +177,8 @@ def main():
         return sample_bench(a)
     if a.prefill_chunk:
         return prefill_bench(a)
-    if a.decode_gemm == "skinny" and a.kv_dtype == "fp8":
-        raise SystemExit("--decode_gemm skinny and --kv_dtype fp8 each replace the second arm")
+    if a.decode_gemm != "default" and a.kv_dtype == "fp8":
+        raise SystemExit("--decode_gemm and --kv_dtype fp8 each replace the second arm")
     torch.manual_seed(0)
     model = bert.bert_base(causal=True).cuda().eval()
     if a.shadows:
@@ -194,6 +198,10 @@ def main():
     if a.decode_gemm == "skinny":
         arms["recompute"] = lambda: model.generate(prompt, lens, a.new, decode_gemm="skinny")
         second = "kv_cache_skinny"
+    if a.decode_gemm == "skinny_ln":                  # against the "skinny" arm, not the default
+        arms["kv_cache"] = lambda: model.generate(prompt, lens, a.new, decode_gemm="skinny")
+        arms["recompute"] = lambda: model.generate(prompt, lens, a.new, decode_gemm="skinny_ln")
+        second = "kv_cache_skinny_ln"
     times = {k: [] for k in arms}
     outs = {}
     for r in range(a.rounds + 1):                     # round 0 warms both arms up
