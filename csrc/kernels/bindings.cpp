@@ -978,6 +978,36 @@ PYBIND11_MODULE(_dtf_hip, m) {
      py::arg("N"), py::arg("K"), py::arg("ldx"), py::arg("epi"), py::arg("splits"),
      py::arg("ln_gamma"), py::arg("ln_beta"), py::arg("ln_eps"), py::arg("ln_width"),
      py::arg("res"), py::arg("ldres"), py::arg("res_is_ln"), py::arg("pre_ln"), py::arg("st"));
+  m.def("weight_quantize_f8", [](uintptr_t w, uintptr_t q, uintptr_t scale, int N, int K,
+                                 uintptr_t st) {
+    dtf_weight_quantize_f8(P<const bf16_t>(w), P<uint8_t>(q), P<float>(scale), N, K, S(st));
+    check_launch("weight_quantize_f8");
+  }, py::arg("w"), py::arg("q"), py::arg("scale"), py::arg("N"), py::arg("K"), py::arg("st"));
+  m.def("dense_skinny_w8", [](uintptr_t x, uintptr_t q, uintptr_t scale, uintptr_t bias,
+                              uintptr_t y, uintptr_t ws, int M, int N, int K, int ldx, int epi,
+                              int splits, uintptr_t st) {
+    dtf_dense_skinny_w8(P<const bf16_t>(x), P<const uint8_t>(q), P<const float>(scale),
+                        P<const float>(bias), P<bf16_t>(y), P<float>(ws), M, N, K, ldx, epi,
+                        splits, S(st));
+    check_launch("dense_skinny_w8");
+  }, py::arg("x"), py::arg("q"), py::arg("scale"), py::arg("bias"), py::arg("y"), py::arg("ws"),
+     py::arg("M"), py::arg("N"), py::arg("K"), py::arg("ldx"), py::arg("epi"), py::arg("splits"),
+     py::arg("st"));
+  m.def("dense_skinny_ln_w8", [](uintptr_t x, uintptr_t q, uintptr_t scale, uintptr_t bias,
+                                 uintptr_t y, uintptr_t ws, int M, int N, int K, int ldx, int epi,
+                                 int splits, uintptr_t ln_gamma, uintptr_t ln_beta, float ln_eps,
+                                 int ln_width, uintptr_t res, int ldres, int res_is_ln,
+                                 int pre_ln, uintptr_t st) {
+    const DenseSkinnyLnArgs a{{P<const bf16_t>(x), nullptr, P<const float>(bias), P<bf16_t>(y),
+                               P<float>(ws), M, N, K, ldx, splits, epi},
+                              P<const float>(ln_gamma), P<const float>(ln_beta),
+                              P<const bf16_t>(res), ln_eps, ln_width, ldres, pre_ln, res_is_ln};
+    dtf_dense_skinny_ln_w8(a, P<const uint8_t>(q), P<const float>(scale), S(st));
+    check_launch("dense_skinny_ln_w8");
+  }, py::arg("x"), py::arg("q"), py::arg("scale"), py::arg("bias"), py::arg("y"), py::arg("ws"),
+     py::arg("M"), py::arg("N"), py::arg("K"), py::arg("ldx"), py::arg("epi"), py::arg("splits"),
+     py::arg("ln_gamma"), py::arg("ln_beta"), py::arg("ln_eps"), py::arg("ln_width"),
+     py::arg("res"), py::arg("ldres"), py::arg("res_is_ln"), py::arg("pre_ln"), py::arg("st"));
   m.def("sample_max_keys", &dtf_sample_max_keys, py::arg("large"));
   m.def("sample_tokens", [](uintptr_t logits, uintptr_t counter, uintptr_t tokens,
                             uintptr_t logprob, int B, int V, int ld, uint32_t seed,

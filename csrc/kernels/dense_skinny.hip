@@ -57,23 +57,11 @@
 #include <stdexcept>
 #include <string>
 
-#include "launch.h"
+#include "dense_skinny_common.h"
 
 namespace {
 
-constexpr int kWaves = 4;        // waves per block
-constexpr int kUnit = 64;        // k per unit: two MFMA steps, two 16-B loads per lane and row
-constexpr int kMp = 20;          // merge row pitch in floats: 80-B rows keep float4 alignment and
-                                 // put the 4 k-groups' stores on distinct banks
-
-DTF_DEV f32x4_t mfma(const bf16x8_t& a, const bf16x8_t& b, const f32x4_t& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-DTF_DEV void mfma_fence() {
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
+using namespace dtf_skinny;
 
 // NB units from unit u on: every load first, then the MFMAs
 template <int MT, int NB>
@@ -103,19 +91,6 @@ DTF_DEV void run_units(const bf16_t* wp, const bf16_t* const (&xp)[MT], const bo
       for (int t = 0; t < MT; ++t) acc[t] = mfma(a[t][i][j], b[i][j], acc[t]);
 }
 
-// the epilogue on 4 consecutive columns n .. n + 3 of row m
-DTF_DEV void store4(const DenseSkinnyArgs& g, int m, int n, float4 s) {
-  if (g.epi) {
-    const float4 b = *reinterpret_cast<const float4*>(g.bias + n);
-    s.x += b.x; s.y += b.y; s.z += b.z; s.w += b.w;
-    if (g.epi == 2) {
-      s.x = gelu_f(s.x); s.y = gelu_f(s.y); s.z = gelu_f(s.z); s.w = gelu_f(s.w);
-    }
-  }
-  *reinterpret_cast<uint2*>(g.y + (size_t)m * g.N + n) =
-      make_uint2(pack2(s.x, s.y), pack2(s.z, s.w));
-}
-
 template <int MT>
 __global__ void __launch_bounds__(64 * kWaves) dense_skinny_kernel(const DenseSkinnyArgs g) {
   constexpr int UB = MT == 1 ? 8 : MT == 2 ? 4 : 2;       // units loaded ahead of their MFMAs
@@ -143,28 +118,12 @@ __global__ void __launch_bounds__(64 * kWaves) dense_skinny_kernel(const DenseSk
   for (; u < wu1; ++u) run_units<MT, 1>(wp, xp, live, u, acc);
   mfma_fence();
 
-  // acc[t][r] is y[16 t + 4 gq + r][n0 + li]
-  float* mine = Ms + w * MT * 16 * kMp;
-#pragma unroll
-  for (int t = 0; t < MT; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) mine[(16 * t + 4 * gq + r) * kMp + li] = acc[t][r];
-  __syncthreads();
-
-  // thread -> (row, 4 columns): the waves' sums added in wave order
-  if (tid >= MT * 64) return;
-  const int m = tid >> 2, c = (tid & 3) * 4;
-  if (m >= g.M) return;
-  float4 s = *reinterpret_cast<const float4*>(Ms + m * kMp + c);
-#pragma unroll
-  for (int k = 1; k < kWaves; ++k) {
-    const float4 p = *reinterpret_cast<const float4*>(Ms + (k * MT * 16 + m) * kMp + c);
-    s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w;
-  }
-  if (g.splits == 1)
-    store4(g, m, n0 + c, s);
-  else
-    *reinterpret_cast<float4*>(g.ws + ((size_t)split * g.M + m) * g.N + n0 + c) = s;
+  merge_waves<MT>(Ms, acc, tid, w, g.M, [&](int m, int c, float4 s) {
+    if (g.splits == 1)
+      store4(g, m, n0 + c, s);
+    else
+      *reinterpret_cast<float4*>(g.ws + ((size_t)split * g.M + m) * g.N + n0 + c) = s;
+  });
 }
 
 // One thread per (row, 4 columns): the partials of the splits added in split order.
@@ -185,7 +144,6 @@ __global__ void __launch_bounds__(256) dense_skinny_combine_kernel(const DenseSk
 }
 
 constexpr int kCus = 256;            // MI355X
-constexpr int kMaxM = 64;
 // A split must be worth the combine launch: no split below this many 64-k units per block.
 // Measured (tools/dense_bench.py --splits, profiles/SKINNY.md): up to K = 3072 no split wins.
 // 768 x 3072 at M = 8 takes 11.3 us a call with one split against 15.3 to 15.7 with 2 to 12, and
@@ -196,61 +154,6 @@ constexpr int kMaxM = 64;
 constexpr int kMinSplitUnits = 64;
 
 // ---- deferred LayerNorm
-constexpr int kLnMaxWidth = 1024;
-constexpr int kLnV = kLnMaxWidth / 512;      // 16-B loads a lane makes of one row
-
-// mean / rstd of rows m_lo + w, m_lo + w + 4, ... < m_hi (RW of them at most) of r -> st[row].
-// Every load first, then two passes over the registers per row; rows past m_hi reduce zeros, so
-// the RW reductions are straight-line code the scheduler can interleave.
-template <int RW>
-DTF_DEV void row_stats(const DenseSkinnyLnArgs& h, const bf16_t* r, int ld, int m_lo, int m_hi,
-                       int w, int lane, float2* st) {
-  const int pieces = h.ln_width / 8;
-  const float inv = 1.f / (float)h.ln_width;
-  uint4 v[RW][kLnV];
-#pragma unroll
-  for (int i = 0; i < RW; ++i)
-#pragma unroll
-    for (int j = 0; j < kLnV; ++j) {
-      v[i][j] = make_uint4(0u, 0u, 0u, 0u);
-      if (m_lo + w + kWaves * i < m_hi && lane + 64 * j < pieces)
-        v[i][j] = *reinterpret_cast<const uint4*>(r + (size_t)(m_lo + w + kWaves * i) * ld +
-                                                  8 * (lane + 64 * j));
-    }
-#pragma unroll
-  for (int i = 0; i < RW; ++i) {
-    float f[kLnV][8], s = 0.f, sq = 0.f;
-#pragma unroll
-    for (int j = 0; j < kLnV; ++j) {
-      unpack8(v[i][j], f[j]);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) s += f[j][e];
-    }
-    const float mean = wave_sum(s) * inv;
-#pragma unroll
-    for (int j = 0; j < kLnV; ++j)
-      if (lane + 64 * j < pieces) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float d = f[j][e] - mean;
-          sq += d * d;
-        }
-      }
-    const float rstd = rsqrtf(wave_sum(sq) * inv + h.ln_eps);
-    const int m = m_lo + w + kWaves * i;
-    if (lane == 0 && m < m_hi) st[m] = make_float2(mean, rstd);
-  }
-}
-
-// lnb of 8 consecutive elements v with their gamma gm / beta bt, packed as one MFMA operand
-DTF_DEV bf16x8_t lnb8(const uint4& v, float2 ms, const float (&gm)[8], const float (&bt)[8]) {
-  float f[8];
-  unpack8(v, f);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) f[e] = ((f[e] - ms.x) * ms.y) * gm[e] + bt[e];
-  return __builtin_bit_cast(bf16x8_t, pack8(f));
-}
-
 template <int NB>
 DTF_DEV void load_w(const bf16_t* wp, int u, bf16x8_t (&b)[NB][2]) {
 #pragma unroll
@@ -292,35 +195,6 @@ DTF_DEV void mma_units_ln(const bf16x8_t (&b)[NB][2], const bf16_t* const (&xp)[
         acc[t] = mfma(op, b[i][j], acc[t]);
       }
     }
-  }
-}
-
-// store4 with the residual: (s + b[n]) + res, res read plain (RES 1) or as lnb(res) (RES 2)
-template <int RES>
-DTF_DEV void store4_res(const DenseSkinnyLnArgs& h, const float2* st, int m, int n, float4 s) {
-  const DenseSkinnyArgs& g = h.d;
-  if constexpr (RES == 0) {
-    store4(g, m, n, s);
-  } else {
-    const float4 b = *reinterpret_cast<const float4*>(g.bias + n);
-    const uint2 rv = *reinterpret_cast<const uint2*>(h.res + (size_t)m * h.ldres + n);
-    float r[4] = {__builtin_bit_cast(float, rv.x << 16),
-                  __builtin_bit_cast(float, rv.x & 0xffff0000u),
-                  __builtin_bit_cast(float, rv.y << 16),
-                  __builtin_bit_cast(float, rv.y & 0xffff0000u)};
-    if constexpr (RES == 2) {
-      const float2 ms = st[m];
-      const float4 gm = *reinterpret_cast<const float4*>(h.ln_gamma + n);
-      const float4 bt = *reinterpret_cast<const float4*>(h.ln_beta + n);
-      r[0] = bf2f(f2bf(((r[0] - ms.x) * ms.y) * gm.x + bt.x));
-      r[1] = bf2f(f2bf(((r[1] - ms.x) * ms.y) * gm.y + bt.y));
-      r[2] = bf2f(f2bf(((r[2] - ms.x) * ms.y) * gm.z + bt.z));
-      r[3] = bf2f(f2bf(((r[3] - ms.x) * ms.y) * gm.w + bt.w));
-    }
-    s.x = (s.x + b.x) + r[0]; s.y = (s.y + b.y) + r[1];
-    s.z = (s.z + b.z) + r[2]; s.w = (s.w + b.w) + r[3];
-    *reinterpret_cast<uint2*>(g.y + (size_t)m * g.N + n) =
-        make_uint2(pack2(s.x, s.y), pack2(s.z, s.w));
   }
 }
 
@@ -390,26 +264,12 @@ __global__ void __launch_bounds__(64 * kWaves) dense_skinny_ln_kernel(const Dens
   if constexpr (RES == 2)
     if (g.splits == 1) row_stats<4 * MT>(h, h.res, h.ldres, 0, g.M, w, lane, St);
 
-  float* mine = Ms + w * MT * 16 * kMp;
-#pragma unroll
-  for (int t = 0; t < MT; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) mine[(16 * t + 4 * gq + r) * kMp + li] = acc[t][r];
-  __syncthreads();
-
-  if (tid >= MT * 64) return;
-  const int m = tid >> 2, c = (tid & 3) * 4;
-  if (m >= g.M) return;
-  float4 s = *reinterpret_cast<const float4*>(Ms + m * kMp + c);
-#pragma unroll
-  for (int k = 1; k < kWaves; ++k) {
-    const float4 p = *reinterpret_cast<const float4*>(Ms + (k * MT * 16 + m) * kMp + c);
-    s.x += p.x; s.y += p.y; s.z += p.z; s.w += p.w;
-  }
-  if (g.splits == 1)
-    store4_res<RES>(h, St, m, n0 + c, s);
-  else
-    *reinterpret_cast<float4*>(g.ws + ((size_t)split * g.M + m) * g.N + n0 + c) = s;
+  merge_waves<MT>(Ms, acc, tid, w, g.M, [&](int m, int c, float4 s) {
+    if (g.splits == 1)
+      store4_res<RES>(h, St, m, n0 + c, s);
+    else
+      *reinterpret_cast<float4*>(g.ws + ((size_t)split * g.M + m) * g.N + n0 + c) = s;
+  });
 }
 
 // dense_skinny_combine_kernel with the residual; RES 2: the block first forms the statistics of
@@ -466,9 +326,11 @@ int dtf_dense_skinny_splits(int M, int N, int K) {
   return want < 1 ? 1 : want;
 }
 
-// the checks common to both entries -> the `splits` of the launch
-static int checked_splits(const bf16_t* x, const bf16_t* w, const float* bias, const bf16_t* y,
-                          const float* ws, int M, int N, int K, int ldx, int epi, int splits) {
+
+// the checks common to every entry -> the `splits` of the launch
+int dtf_dense_skinny_checked_splits(const bf16_t* x, const void* w, const float* bias,
+                                    const bf16_t* y, const float* ws, int M, int N, int K, int ldx,
+                                    int epi, int splits) {
   if (!x || !w || !y) throw std::runtime_error("dense_skinny: null pointer");
   if (M < 1 || M > kMaxM)
     throw std::runtime_error("dense_skinny: 1 <= M <= 64, got " + std::to_string(M));
@@ -493,9 +355,21 @@ static int checked_splits(const bf16_t* x, const bf16_t* w, const float* bias, c
   return splits;
 }
 
+void dtf_dense_skinny_combine(const DenseSkinnyLnArgs& h, int res, hipStream_t st) {
+  const DenseSkinnyArgs& g = h.d;
+  const int total = g.M * (g.N / 4);
+  const dim3 cgrid(dtf_cdiv(total, 256)), cblock(256);
+  if (res == 0)
+    hipLaunchKernelGGL(dense_skinny_combine_kernel, cgrid, cblock, 0, st, g, total);
+  else if (res == 1)
+    hipLaunchKernelGGL(dense_skinny_combine_ln_kernel<1>, cgrid, cblock, 0, st, h, total);
+  else
+    hipLaunchKernelGGL(dense_skinny_combine_ln_kernel<2>, cgrid, cblock, 0, st, h, total);
+}
+
 void dtf_dense_skinny(const bf16_t* x, const bf16_t* w, const float* bias, bf16_t* y, float* ws,
                       int M, int N, int K, int ldx, int epi, int splits, hipStream_t st) {
-  splits = checked_splits(x, w, bias, y, ws, M, N, K, ldx, epi, splits);
+  splits = dtf_dense_skinny_checked_splits(x, w, bias, y, ws, M, N, K, ldx, epi, splits);
   const DenseSkinnyArgs g{x, w, bias, y, ws, M, N, K, ldx, splits, epi};
   const dim3 grid(N / 16, splits), block(64 * kWaves);
   switch ((M + 15) / 16) {
@@ -504,19 +378,13 @@ void dtf_dense_skinny(const bf16_t* x, const bf16_t* w, const float* bias, bf16_
     case 3: hipLaunchKernelGGL(dense_skinny_kernel<3>, grid, block, 0, st, g); break;
     default: hipLaunchKernelGGL(dense_skinny_kernel<4>, grid, block, 0, st, g); break;
   }
-  if (splits > 1) {
-    const int total = M * (N / 4);
-    hipLaunchKernelGGL(dense_skinny_combine_kernel, dim3(dtf_cdiv(total, 256)), dim3(256), 0, st,
-                       g, total);
-  }
+  if (splits > 1) dtf_dense_skinny_combine(DenseSkinnyLnArgs{g}, 0, st);
 }
 
 int dtf_dense_skinny_ln_max_width() { return kLnMaxWidth; }
 
-void dtf_dense_skinny_ln(const DenseSkinnyLnArgs& a, hipStream_t st) {
-  DenseSkinnyLnArgs h = a;
-  DenseSkinnyArgs& g = h.d;
-  g.splits = checked_splits(g.x, g.w, g.bias, g.y, g.ws, g.M, g.N, g.K, g.ldx, g.epi, g.splits);
+int dtf_dense_skinny_ln_checked_res(const DenseSkinnyLnArgs& h) {
+  const DenseSkinnyArgs& g = h.d;
   const bool ln = h.pre_ln || h.res_is_ln;
   if (!h.pre_ln && !h.res)
     throw std::runtime_error("dense_skinny_ln: neither a normalised x nor a residual: that is "
@@ -546,8 +414,16 @@ void dtf_dense_skinny_ln(const DenseSkinnyLnArgs& a, hipStream_t st) {
     if (!(h.ln_eps >= 0.f) || h.ln_eps > 1.f)
       throw std::runtime_error("dense_skinny_ln: eps must be in [0, 1]");
   }
+  return !h.res ? 0 : h.res_is_ln ? 2 : 1;
+}
+
+void dtf_dense_skinny_ln(const DenseSkinnyLnArgs& a, hipStream_t st) {
+  DenseSkinnyLnArgs h = a;
+  DenseSkinnyArgs& g = h.d;
+  g.splits = dtf_dense_skinny_checked_splits(g.x, g.w, g.bias, g.y, g.ws, g.M, g.N, g.K, g.ldx,
+                                             g.epi, g.splits);
+  const int res = dtf_dense_skinny_ln_checked_res(h);
   const dim3 grid(g.N / 16, g.splits);
-  const int res = !h.res ? 0 : h.res_is_ln ? 2 : 1;
   if (h.pre_ln) {
     if (res == 0) launch_ln<true, 0>(h, grid, st);
     else launch_ln<true, 1>(h, grid, st);
@@ -555,14 +431,5 @@ void dtf_dense_skinny_ln(const DenseSkinnyLnArgs& a, hipStream_t st) {
     if (res == 1) launch_ln<false, 1>(h, grid, st);
     else launch_ln<false, 2>(h, grid, st);
   }
-  if (g.splits > 1) {
-    const int total = g.M * (g.N / 4);
-    const dim3 cgrid(dtf_cdiv(total, 256)), cblock(256);
-    if (res == 0)
-      hipLaunchKernelGGL(dense_skinny_combine_kernel, cgrid, cblock, 0, st, g, total);
-    else if (res == 1)
-      hipLaunchKernelGGL(dense_skinny_combine_ln_kernel<1>, cgrid, cblock, 0, st, h, total);
-    else
-      hipLaunchKernelGGL(dense_skinny_combine_ln_kernel<2>, cgrid, cblock, 0, st, h, total);
-  }
+  if (g.splits > 1) dtf_dense_skinny_combine(h, res, st);
 }

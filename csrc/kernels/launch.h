@@ -541,6 +541,22 @@ struct DenseSkinnyLnArgs {
 };
 int dtf_dense_skinny_ln_max_width();
 void dtf_dense_skinny_ln(const DenseSkinnyLnArgs& a, hipStream_t st);
+// ---- dense_skinny_f8.hip: the same two entries on FP8 weights.  A weight is the pair q [N, K]
+// (e4m3 bytes) and scale [N, K / 64] (fp32, one power of two per row and 64-k unit), the rule of
+// kv_f8.h applied to every 64-k unit of the bf16 matrix; the GEMM computes with exactly the
+// dequantised matrix float(q) * scale.
+struct DenseSkinnyW8Args {
+  DenseSkinnyLnArgs h;     // h.d.w is not used
+  const uint8_t* q;        // [N, K] contiguous
+  const float* scale;      // [N, K / 64] contiguous
+};
+void dtf_weight_quantize_f8(const bf16_t* w, uint8_t* q, float* scale, int N, int K,
+                            hipStream_t st);
+void dtf_dense_skinny_w8(const bf16_t* x, const uint8_t* q, const float* scale, const float* bias,
+                         bf16_t* y, float* ws, int M, int N, int K, int ldx, int epi, int splits,
+                         hipStream_t st);
+void dtf_dense_skinny_ln_w8(const DenseSkinnyLnArgs& a, const uint8_t* q, const float* scale,
+                            hipStream_t st);
 
 // ---- sample.hip: top-k / top-p filtering and the draw of one token per logits row, one kernel
 struct SampleArgs {

@@ -168,11 +168,13 @@ def build_parser():
     p.add_argument("--generate_kv_dtype", choices=["bf16", "fp8"], default="bf16",
                    help="the KV cache of --generate: the activation dtype, or FP8 (e4m3 bytes with "
                         "one power-of-two scale per row, 68 bytes a cached row instead of 128)")
-    p.add_argument("--generate_decode_gemm", choices=["default", "skinny", "skinny_ln"],
+    p.add_argument("--generate_decode_gemm",
+                   choices=["default", "skinny", "skinny_ln", "skinny_w8", "skinny_ln_w8"],
                    default="default",
                    help="the GEMMs of the decode steps of --generate: the persistent MFMA GEMM, "
-                        "the skinny-M weight-streaming kernel (batches of up to 64 rows), or that "
-                        "kernel with the layers' LayerNorms deferred into it (skinny_ln)")
+                        "the skinny-M weight-streaming kernel (batches of up to 64 rows), that "
+                        "kernel with the layers' LayerNorms deferred into it (skinny_ln), or "
+                        "either of the two on FP8 (e4m3) weights (skinny_w8, skinny_ln_w8)")
     p.add_argument("--generate_seed", type=int, default=None,
                    help="pick every token with the fused on-device sampler, reproducible from "
                         "this seed (default: torch's generator seeded with --seed)")

@@ -61,15 +61,30 @@ SKINNY_MAX_ROWS_WIDE = 32
 SKINNY_WIDE = 3072
 
 
+_SKINNY_GEMMS = ("skinny", "skinny_ln", "skinny_w8", "skinny_ln_w8")
+
+
 def _skinny(gemm, rows, width=0):
-    """The route of a GEMM with ``width`` outputs in a decode / extend call over ``rows`` rows:
-    ``gemm`` ("skinny", or "skinny_ln": the skinny kernel with the layers' LayerNorms deferred
-    into it) when asked for and the rows fit, else None (today's path).  Decided on the host from
-    the shapes."""
-    if gemm not in (None, "default", "skinny", "skinny_ln"):
-        raise ValueError(f"gemm must be None, 'default', 'skinny' or 'skinny_ln', got {gemm!r}")
+    """The route of a GEMM with ``width`` outputs in a decode / extend call over ``rows`` rows
+    -> (impl, w8): impl is "skinny", or "skinny_ln" (the skinny kernel with the layers' LayerNorms
+    deferred into it), when ``gemm`` asks for it and the rows fit, else None (today's path on the
+    bf16 shadow); w8: ``gemm`` is "skinny_w8" / "skinny_ln_w8" and the GEMM takes the FP8 pair of
+    :meth:`BertForPreTraining.quantize_weights` in place of the shadow.  The SKINNY_MAX_ROWS_WIDE
+    rule holds for the pairs too (21.1 us at 32 rows, 20.6 at 33 against the default route's 20.4
+    to 20.8: no clearer a crossing than for bf16, profiles/SKINNY_W8.md).
+    Decided on the host from the shapes."""
+    if gemm not in (None, "default") + _SKINNY_GEMMS:
+        raise ValueError(f"gemm must be None, 'default' or one of {_SKINNY_GEMMS}, got {gemm!r}")
     most = SKINNY_MAX_ROWS_WIDE if width > SKINNY_WIDE else SKINNY_MAX_ROWS
-    return gemm if gemm in ("skinny", "skinny_ln") and rows <= most else None
+    if gemm not in _SKINNY_GEMMS or rows > most:
+        return None, False
+    w8 = gemm.endswith("_w8")
+    return (gemm[:-3] if w8 else gemm), w8
+
+
+def _wt(p, w8):
+    """The weight a GEMM takes: the parameter (its bf16 shadow), or its FP8 pair."""
+    return p._dtf_w8 if w8 else p
 
 
 # Under gemm="skinny_ln" the hidden state between layers is a pair (t, ln): ln = (gamma, beta,
@@ -133,8 +148,8 @@ class _Dense(nn.Module):
         self.kernel = _param((n_out, n_in), f"{name}/kernel", std, "OI")
         self.bias = _param((n_out,), f"{name}/bias", fill=0.0)
 
-    def gemm(self, x, impl=None):
-        return ops.dense(x, self.kernel, None, impl=impl or BERT_GEMM)
+    def gemm(self, x, impl=None, w8=False):
+        return ops.dense(x, _wt(self.kernel, w8), None, impl=impl or BERT_GEMM)
 
 
 class _LayerNorm(nn.Module):
@@ -185,11 +200,11 @@ class BertLayer(nn.Module):
         row scales).  ``gemm="skinny"``: the QKV and output projections and the FFN run on the
         weight-streaming kernel when B <= 64.  ``gemm="skinny_ln"``: also the two LayerNorms, deferred
         into those GEMMs (five launches); x may then be a ``(t, ln)`` pair and the result is one."""
-        impl = _skinny(gemm, _deferred(x)[0].shape[0])
-        qkv, x = self._qkv(x, impl)
+        impl, w8 = _skinny(gemm, _deferred(x)[0].shape[0])
+        qkv, x = self._qkv(x, impl, w8)
         ctx = ops.attention_decode(qkv, k_cache, v_cache, pos, self.cfg.num_attention_heads,
                                    max_len=max_len, k_scale=k_scale, v_scale=v_scale)
-        return self._after_attention(x, ctx, impl)
+        return self._after_attention(x, ctx, impl, w8)
 
     def extend(self, x, k_cache, v_cache, pos, n_new, T, max_len=None, k_scale=None,
                v_scale=None, gemm=None):
@@ -197,40 +212,41 @@ class BertLayer(nn.Module):
         positions ``pos[b] ..`` against this layer's cache, which takes their keys and values in
         place (``ops.attention_append``).  ``gemm="skinny"`` / ``"skinny_ln"``: as :meth:`decode`,
         when B*T <= 64."""
-        impl = _skinny(gemm, _deferred(x)[0].shape[0])
-        qkv, x = self._qkv(x, impl)
+        impl, w8 = _skinny(gemm, _deferred(x)[0].shape[0])
+        qkv, x = self._qkv(x, impl, w8)
         ctx = ops.attention_append(qkv, k_cache, v_cache, pos, self.cfg.num_attention_heads,
                                    n_new=n_new, max_len=max_len, k_scale=k_scale,
                                    v_scale=v_scale)
-        return self._after_attention(x, ctx, impl)
+        return self._after_attention(x, ctx, impl, w8)
 
-    def _qkv(self, x, impl):
+    def _qkv(self, x, impl, w8=False):
         """The QKV projection of a decode / extend call -> (qkv, x as the rest of the layer takes
         it: the ``(t, ln)`` pair under "skinny_ln", whose LayerNorm the GEMM applies on load)."""
         if impl == "skinny_ln":
             t, ln = x = _deferred(x)
-            return ops.dense(t, self.qkv_kernel, self.qkv_bias, impl="skinny", pre_ln=ln), x
+            return ops.dense(t, _wt(self.qkv_kernel, w8), self.qkv_bias, impl="skinny",
+                             pre_ln=ln), x
         x = _normalised(x)
-        return ops.dense(x, self.qkv_kernel, self.qkv_bias, impl=impl or BERT_GEMM), x
+        return ops.dense(x, _wt(self.qkv_kernel, w8), self.qkv_bias, impl=impl or BERT_GEMM), x
 
-    def _after_attention_ln(self, t, ln, ctx):
+    def _after_attention_ln(self, t, ln, ctx, w8=False):
         """The rest of the layer with both LayerNorms deferred: the output projection stores
         t1 = ctx W^T + b + LN(t) and the FFN pair t2 = ffn(LN(t1)) + b + LN(t1), un-normalised; a
         decode / extend step has no dropout.  -> (t2, its LayerNorm)."""
         eps = self.cfg.layer_norm_eps
-        t1 = ops.dense(ctx, self.attn_out.kernel, self.attn_out.bias, impl="skinny", residual=t,
-                       residual_ln=ln)
+        t1 = ops.dense(ctx, _wt(self.attn_out.kernel, w8), self.attn_out.bias, impl="skinny",
+                       residual=t, residual_ln=ln)
         ln1 = (self.attn_ln.gamma, self.attn_ln.beta, eps)
-        t2 = ops.dense_gelu_dense(t1, self.inter.kernel, self.inter.bias, self.out.kernel,
-                                  impl="skinny", pre_ln=ln1, b2=self.out.bias, residual=t1,
-                                  residual_ln=ln1)
+        t2 = ops.dense_gelu_dense(t1, _wt(self.inter.kernel, w8), self.inter.bias,
+                                  _wt(self.out.kernel, w8), impl="skinny", pre_ln=ln1,
+                                  b2=self.out.bias, residual=t1, residual_ln=ln1)
         return t2, (self.out_ln.gamma, self.out_ln.beta, eps)
 
-    def _after_attention(self, x, ctx, impl=None):
+    def _after_attention(self, x, ctx, impl=None, w8=False):
         if impl == "skinny_ln":
-            return self._after_attention_ln(*x, ctx)
+            return self._after_attention_ln(*x, ctx, w8)
         cfg = self.cfg
-        a = self.attn_out.gemm(ctx, impl)
+        a = self.attn_out.gemm(ctx, impl, w8)
         # x feeds the QKV dense above and the residual here: its two gradients are summed by
         # that dense's dgrad GEMM (beta = 1), not by a separate add
         x = ops.bias_dropout_add_layer_norm(a, self.attn_out.bias, x, self.attn_ln.gamma,
@@ -239,8 +255,8 @@ class BertLayer(nn.Module):
                                             residual_to_dense=True)
         if impl == "skinny":
             # a decode step's FFN: two launches of the skinny-M kernel, bias + GELU in the first
-            o = ops.dense_gelu_dense(x, self.inter.kernel, self.inter.bias, self.out.kernel,
-                                     impl=impl)
+            o = ops.dense_gelu_dense(x, _wt(self.inter.kernel, w8), self.inter.bias,
+                                     _wt(self.out.kernel, w8), impl=impl)
         elif FUSE_GELU_DGRAD and BERT_GEMM == "library":
             # the whole FFN as one op: the first GEMM applies bias + GELU in its epilogue (our
             # MFMA GEMM); the backward forms d(pre-activation) in one GEMM pass with the GELU
@@ -341,20 +357,43 @@ class BertForPreTraining(Layer):
         SKINNY_MAX_ROWS_WIDE).  ``gemm="skinny_ln"``: h may be a ``(t, ln)`` pair, whose LayerNorm
         the transform GEMM then applies on load; the vocabulary GEMM is the "skinny" one (its 1908
         blocks would each recompute the statistics)."""
-        impl = _skinny(gemm, _deferred(h)[0].shape[0])
+        impl, w8 = _skinny(gemm, _deferred(h)[0].shape[0])
         if impl == "skinny_ln":
             t, ln = _deferred(h)
-            h = ops.dense(t, self.mlm_transform.kernel, None, impl="skinny", pre_ln=ln)
+            h = ops.dense(t, _wt(self.mlm_transform.kernel, w8), None, impl="skinny", pre_ln=ln)
         else:
-            h = self.mlm_transform.gemm(_normalised(h), impl)
+            h = self.mlm_transform.gemm(_normalised(h), impl, w8)
         h = ops.bias_gelu(h, self.mlm_transform.bias)
         h = ops.bias_dropout_add_layer_norm(h, None, None, self.mlm_ln.gamma, self.mlm_ln.beta,
                                             0.0, self.training, self.cfg.layer_norm_eps)
-        impl = _skinny(gemm, h.shape[0], self.word_embeddings.shape[0])
-        return ops.dense(h, self.word_embeddings, self.mlm_bias,
+        impl, w8 = _skinny(gemm, h.shape[0], self.word_embeddings.shape[0])
+        return ops.dense(h, _wt(self.word_embeddings, w8), self.mlm_bias,
                          impl="skinny" if impl else BERT_GEMM)
 
     # ------------------------------------------------------------------------- generation
+    def _w8_params(self):
+        """The matrices the decode path's GEMMs read: every layer's four, the head's transform
+        and the tied vocabulary projection."""
+        for layer in self.layers:
+            yield from (layer.qkv_kernel, layer.attn_out.kernel, layer.inter.kernel,
+                        layer.out.kernel)
+        yield from (self.mlm_transform.kernel, self.word_embeddings)
+
+    @torch.no_grad()
+    def quantize_weights(self):
+        """Build the FP8 pairs (``ops.weight_quantize_fp8``) of the decode path's matrices from
+        their current values, for ``gemm="skinny_w8"`` / ``"skinny_ln_w8"``.  They are kept on the
+        parameters next to the fp32 masters, which the embedding lookup and every other path
+        keep using; call it again after the weights change or move."""
+        for p in self._w8_params():
+            p._dtf_w8 = ops.weight_quantize_fp8(p)
+        return self
+
+    def _check_w8(self, gemm):
+        if gemm in ("skinny_w8", "skinny_ln_w8") and any(
+                getattr(p, "_dtf_w8", None) is None for p in self._w8_params()):
+            raise ValueError(f"gemm={gemm!r} needs the FP8 weights: call quantize_weights() first")
+
     def _check_prompts(self, input_ids, prompt_lens):
         if not self.cfg.causal:
             raise ValueError("incremental decoding needs a causal model (BertConfig(causal=True))")
@@ -379,6 +418,7 @@ class BertForPreTraining(Layer):
         if B != cache.batch or Sp > cache.capacity:
             raise ValueError(f"cache is for batch {cache.batch}, capacity {cache.capacity}")
         if chunk is not None:
+            self._check_w8(gemm)
             T = int(chunk)
             if T < 1:
                 raise ValueError("chunk must be at least 1")
@@ -412,10 +452,14 @@ class BertForPreTraining(Layer):
         and larger batches keep the persistent GEMM.  ``gemm="skinny_ln"``: the same GEMMs with
         every layer's two LayerNorms deferred into them (``ops.dense(pre_ln=, residual_ln=)``): five
         launches a layer instead of seven, the last layer's LayerNorm applied by the head's
-        transform GEMM; the same row limits."""
+        transform GEMM; the same row limits.  ``"skinny_w8"`` / ``"skinny_ln_w8"``: those two
+        with the FP8 weight pairs of :meth:`quantize_weights` (a ValueError before it was called)
+        in place of the bf16 shadows: half the weight bytes a step streams, and the step computes
+        with exactly the dequantised matrices."""
         cfg = self.cfg
         if not cfg.causal:
             raise ValueError("incremental decoding needs a causal model (BertConfig(causal=True))")
+        self._check_w8(gemm)
         dtype = cache.act_dtype
         # the embedding kernel indexes positions by row % S: form word[id] + pos[p] + type[0] as
         # it does (tables rounded to the activation dtype, summed in fp32, rounded once)
@@ -449,6 +493,7 @@ class BertForPreTraining(Layer):
         cfg = self.cfg
         if not cfg.causal:
             raise ValueError("incremental decoding needs a causal model (BertConfig(causal=True))")
+        self._check_w8(gemm)
         B, T = ids_new.shape
         n = torch.full((B,), T) if n_new is None else torch.as_tensor(n_new).reshape(-1).cpu()
         if B != cache.batch or n.numel() != B or int(n.min()) < 0 or int(n.max()) > T:
@@ -499,10 +544,12 @@ class BertForPreTraining(Layer):
         ``kv_dtype="fp8"`` keeps the keys and values in an FP8 cache (:class:`KVCache`).
         ``decode_gemm="skinny"`` runs the GEMMs of every decode step, and of a chunked prefill's
         pieces of at most 64 rows, on the weight-streaming kernel (:meth:`decode_step`),
-        ``"skinny_ln"`` also defers the layers' LayerNorms into it; None or "default" is the
-        persistent GEMM."""
+        ``"skinny_ln"`` also defers the layers' LayerNorms into it; ``"skinny_w8"`` /
+        ``"skinny_ln_w8"`` run them on FP8 weights, quantised here from the current weights
+        (:meth:`quantize_weights`) before the loop; None or "default" is the persistent GEMM."""
         lens = self._check_prompts(input_ids, prompt_lens)
-        _skinny(decode_gemm, 1)
+        if _skinny(decode_gemm, 1)[1]:
+            self.quantize_weights()
         if seed is None and (top_p != 1.0 or return_logprobs):
             raise ValueError("top_p and return_logprobs need the seeded path: pass seed=")
         if max_new_tokens < 1:

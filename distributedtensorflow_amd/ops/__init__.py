@@ -192,8 +192,20 @@ def dense(x, w, b=None, relu=False, impl=None, layout="OI", pre_ln=None, residua
     x's dtype.  ``residual`` [M, out]: ``y = x @ w^T + b + residual`` on the fp32 sum (needs
     ``b``, no ``relu``); ``residual_ln=(gamma, beta, eps)``: ``lnb(residual)`` is added instead.
     ``pre_ln`` with ``residual_ln`` is refused (a call normalises one matrix), as are normalised
-    rows wider than 1024 on the native path."""
+    rows wider than 1024 on the native path.
+
+    FP8 weights: ``w`` may be the pair ``(q, scale)`` of :func:`weight_quantize_fp8`; the result
+    is that of the dequantised matrix ``float(q) * scale``, exactly.  Native: ``impl="skinny"``
+    only (the kernel streams the e4m3 bytes), any other ``impl`` is a ValueError; the reference
+    path dequantises."""
     deferred = pre_ln is not None or residual is not None or residual_ln is not None
+    if reference.is_weight_pair(w):                # checked by whichever backend takes it
+        if layout != "OI":
+            raise ValueError("dense: an FP8 weight pair is [out, in] (layout 'OI')")
+        if _use_native(x):
+            return _native().dense(x, w, b, relu, impl, pre_ln, residual, residual_ln)
+        return reference.dense(x, reference.weight_dequantize(w), b, relu, pre_ln, residual,
+                               residual_ln)
     if _f32(x):
         if deferred:
             raise ValueError("dense: pre_ln / residual / residual_ln need impl='skinny' (bf16)")
@@ -308,13 +320,28 @@ def dense_gelu_dense(x, w1, b1, w2, impl=None, pre_ln=None, b2=None, residual=No
 
     Deferred LayerNorm, as :func:`dense` (native: ``impl="skinny"`` only): ``pre_ln`` normalises
     x on the first GEMM's load; ``b2`` / ``residual`` / ``residual_ln`` are the second GEMM's
-    bias and residual, ``... @ w2^T + b2 + residual``.  Still two launches."""
+    bias and residual, ``... @ w2^T + b2 + residual``.  Still two launches.
+
+    ``w1`` / ``w2`` may be FP8 pairs, as :func:`dense`'s ``w`` (native: ``impl="skinny"`` only)."""
     if _use_native(x):
         return _native().dense_gelu_dense(x, w1, b1, w2, impl, pre_ln, b2, residual, residual_ln)
+    w1, w2 = (reference.weight_dequantize(w) if reference.is_weight_pair(w) else w
+              for w in (w1, w2))
     if pre_ln is None and b2 is None and residual is None and residual_ln is None:
         return reference.dense(reference.bias_gelu(reference.dense(x, w1), b1), w2)
     h = reference.bias_gelu(reference.dense(x, w1, pre_ln=pre_ln), b1)
     return reference.dense(h, w2, b2, residual=residual, residual_ln=residual_ln)
+
+
+def weight_quantize_fp8(w):
+    """An [N, K] dense weight (K % 64 == 0) -> the FP8 pair ``(q, scale)`` that :func:`dense` and
+    :func:`dense_gelu_dense` take in its place: ``q`` float8_e4m3fn [N, K], ``scale`` fp32
+    [N, K / 64], one power of two per output row and 64-k unit -- the FP8 cache's rule
+    (``reference.kv_quantize_rows``) on the bf16-rounded weight.  ``float(q) * scale`` is exact in
+    bf16.  Native: one kernel on the weight's bf16 shadow; both backends give the same bits."""
+    if _use_native(w):
+        return _native().weight_quantize_fp8(w)
+    return reference.weight_quantize_fp8(w)
 
 
 def attention_qkv(qkv, mask, batch, seq_len, heads, p=0.0, training=True, scale=None,

@@ -1767,14 +1767,42 @@ _FFN_GEMM_GELU = os.environ.get("DTF_FFN_GEMM_GELU",
 SKINNY_MAX_ROWS = 64
 
 
+def weight_quantize_fp8(w):
+    """``ops.weight_quantize_fp8``: the quantiser kernel of csrc/kernels/dense_skinny_f8.hip on the
+    weight's bf16 shadow."""
+    wb = _bf16_weight(w)
+    if not wb.is_cuda or wb.dim() != 2 or wb.shape[1] % 64 or not wb.shape[1]:
+        raise ValueError(f"weight_quantize_fp8 takes a CUDA [N, K] weight with K % 64 == 0, got "
+                         f"{tuple(wb.shape)} on {wb.device}")
+    wb = wb.contiguous()
+    N, K = wb.shape
+    q = torch.empty(N, K, device=wb.device, dtype=torch.float8_e4m3fn)
+    scale = torch.empty(N, K // 64, device=wb.device, dtype=torch.float32)
+    _K.weight_quantize_f8(wb.data_ptr(), q.data_ptr(), scale.data_ptr(), N, K, _st())
+    return q, scale
+
+
+def _refuse_pair(name, impl, *ws):
+    from .reference import is_weight_pair
+    if any(is_weight_pair(w) for w in ws):
+        raise ValueError(f"{name}: an FP8 weight pair needs impl='skinny', got impl={impl!r}")
+
+
 def _skinny_check(x, w, b, need_bias=False, pre_ln=None, residual=None, residual_ln=None):
     """The one argument check of the skinny-M kernel (csrc/kernels/dense_skinny.hip) for both ops
-    that reach it -> (x as [M, K] rows, the bf16 weight [N, K]).  Anything the kernel does not
+    that reach it -> (x as [M, K] rows, the bf16 weight [N, K] or, for an FP8 pair ``w``, the
+    checked pair (q, scale) of csrc/kernels/dense_skinny_f8.hip).  Anything the kernel does not
     take is a ValueError: ``impl="skinny"`` never falls back.  ``pre_ln`` / ``residual`` /
     ``residual_ln``: the deferred LayerNorm of ``ops.dense`` (``need_bias`` then means the GELU
     epilogue, which takes no residual)."""
-    from .reference import deferred_ln_check
+    from .reference import check_weight_pair, deferred_ln_check, is_weight_pair
     deferred_ln_check(pre_ln, residual, residual_ln, gelu=need_bias, bias=b is not None)
+    pair = is_weight_pair(w)
+    if pair:
+        pair = check_weight_pair(w)
+        w = pair[0]
+        if w.device != x.device:
+            raise ValueError(f"skinny dense: the FP8 weight is on {w.device}, x on {x.device}")
     if not x.is_cuda or x.dtype != _BF16:
         raise ValueError(f"skinny dense expects CUDA bf16 activations, got {x.dtype} on {x.device}")
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, w, b)):
@@ -1796,8 +1824,8 @@ def _skinny_check(x, w, b, need_bias=False, pre_ln=None, residual=None, residual
                          f"{tuple(x2.stride())}")
     if b is not None and b.numel() != N:
         raise ValueError(f"skinny dense: bias of {b.numel()} for {N} outputs")
-    wb = _bf16_weight(w)
-    if not wb.is_contiguous():
+    wb = pair or _bf16_weight(w)
+    if not pair and not wb.is_contiguous():
         raise ValueError("skinny dense needs a contiguous [out, in] weight")
     ln = pre_ln or residual_ln
     if ln is not None:
@@ -1826,7 +1854,12 @@ def _skinny_check(x, w, b, need_bias=False, pre_ln=None, residual=None, residual
 
 
 def _skinny_launch(x2, wb, b, epi, splits=0, pre_ln=None, residual=None, residual_ln=None):
-    M, (N, K) = x2.shape[0], wb.shape
+    pair = isinstance(wb, tuple)
+    M, (N, K) = x2.shape[0], (wb[0] if pair else wb).shape
+    # the weight's pointers and the two bindings of its format
+    wp, plain, with_ln = (((wb[0].data_ptr(), wb[1].data_ptr()), _K.dense_skinny_w8,
+                           _K.dense_skinny_ln_w8) if pair else
+                          ((wb.data_ptr(),), _K.dense_skinny, _K.dense_skinny_ln))
     splits = splits or _K.dense_skinny_splits(M, N, K)
     ws = (torch.empty(splits * M * N, device=x2.device, dtype=torch.float32)
           if splits > 1 else None)
@@ -1834,20 +1867,19 @@ def _skinny_launch(x2, wb, b, epi, splits=0, pre_ln=None, residual=None, residua
     y = torch.empty(M, N, device=x2.device, dtype=_BF16)
     epi = epi if b32 is not None else 0
     if pre_ln is None and residual is None:
-        _K.dense_skinny(x2.data_ptr(), wb.data_ptr(), _p(b32), y.data_ptr(), _p(ws), M, N, K,
-                        x2.stride(0), epi, splits, _st())
+        plain(x2.data_ptr(), *wp, _p(b32), y.data_ptr(), _p(ws), M, N, K, x2.stride(0), epi,
+              splits, _st())
         return y
     ln = pre_ln or residual_ln
     g32 = be32 = None
     if ln is not None:
         g32, be32 = (t.detach().float().contiguous() for t in ln[:2])
     r2 = None if residual is None else residual.reshape(M, N)
-    _K.dense_skinny_ln(x2.data_ptr(), wb.data_ptr(), _p(b32), y.data_ptr(), _p(ws), M, N, K,
-                       x2.stride(0), epi, splits, _p(g32), _p(be32),
-                       float(ln[2]) if ln is not None else 0.0,
-                       (K if pre_ln is not None else N) if ln is not None else 0, _p(r2),
-                       r2.stride(0) if r2 is not None else 0, int(residual_ln is not None),
-                       int(pre_ln is not None), _st())
+    with_ln(x2.data_ptr(), *wp, _p(b32), y.data_ptr(), _p(ws), M, N, K, x2.stride(0), epi, splits,
+            _p(g32), _p(be32), float(ln[2]) if ln is not None else 0.0,
+            (K if pre_ln is not None else N) if ln is not None else 0, _p(r2),
+            r2.stride(0) if r2 is not None else 0, int(residual_ln is not None),
+            int(pre_ln is not None), _st())
     return y
 
 
@@ -1858,7 +1890,7 @@ def _dense_skinny(x, w, b=None, gelu=False, splits=0, pre_ln=None, residual=None
     ``pre_ln`` / ``residual`` / ``residual_ln``: the deferred LayerNorm of ``ops.dense``)."""
     x2, wb = _skinny_check(x, w, b, gelu, pre_ln, residual, residual_ln)
     y = _skinny_launch(x2, wb, b, 2 if gelu else 1, splits, pre_ln, residual, residual_ln)
-    return y.view(*x.shape[:-1], wb.shape[0])
+    return y.view(*x.shape[:-1], y.shape[1])
 
 
 def dense_gelu_dense(x, w1, b1, w2, impl=None, pre_ln=None, b2=None, residual=None,
@@ -1878,7 +1910,8 @@ def dense_gelu_dense(x, w1, b1, w2, impl=None, pre_ln=None, b2=None, residual=No
         h = _skinny_launch(x2, wb1, b1, 2, pre_ln=pre_ln)
         h2, wb2 = _skinny_check(h, w2, b2, residual=residual, residual_ln=residual_ln)
         y = _skinny_launch(h2, wb2, b2, 1, residual=residual, residual_ln=residual_ln)
-        return y.view(*x.shape[:-1], wb2.shape[0])
+        return y.view(*x.shape[:-1], y.shape[1])
+    _refuse_pair("dense_gelu_dense", impl, w1, w2)
     if pre_ln is not None or b2 is not None or residual is not None or residual_ln is not None:
         raise ValueError("dense_gelu_dense: pre_ln / b2 / residual / residual_ln need "
                          "impl='skinny'")
@@ -2016,6 +2049,7 @@ def dense(x, w, b=None, relu=False, impl=None, pre_ln=None, residual=None, resid
             raise ValueError("skinny dense: a residual combines with the bias epilogue only")
         y = _dense_skinny(x, w, b, pre_ln=pre_ln, residual=residual, residual_ln=residual_ln)
         return torch.relu(y) if relu else y
+    _refuse_pair("dense", impl, w)
     if pre_ln is not None or residual is not None or residual_ln is not None:
         raise ValueError(f"dense: pre_ln / residual / residual_ln need impl='skinny', got "
                          f"impl={impl!r}")

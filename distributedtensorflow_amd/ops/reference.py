@@ -387,6 +387,45 @@ def kv_dequantize(q, scale, dtype=torch.float32):
     return (q.float() * scale.unsqueeze(-1)).to(dtype)
 
 
+def weight_quantize_fp8(w):
+    """An [N, K] weight (K % 64 == 0) -> the FP8 pair ``(q, scale)`` of the skinny-M dense kernel:
+    :func:`kv_quantize_rows` on every 64-k unit of the bf16-ROUNDED weight (what the bf16 path
+    consumes), ``q`` float8_e4m3fn [N, K] and ``scale`` fp32 [N, K / 64]."""
+    if w.dim() != 2 or w.shape[1] % 64 or not w.shape[1]:
+        raise ValueError(f"weight_quantize_fp8 takes an [N, K] weight with K % 64 == 0, got "
+                         f"{tuple(w.shape)}")
+    N, K = w.shape
+    q, scale = kv_quantize_rows(w.detach().to(torch.bfloat16).reshape(N, K // 64, 64))
+    return q.view(N, K), scale
+
+
+def is_weight_pair(w):
+    return isinstance(w, (tuple, list))
+
+
+def check_weight_pair(w):
+    """The one rule of an FP8 weight pair, for both backends -> (q, scale)."""
+    if len(w) != 2 or not all(isinstance(t, torch.Tensor) for t in w):
+        raise ValueError("dense: an FP8 weight is the pair (q, scale) of weight_quantize_fp8")
+    q, scale = w
+    if q.dtype != F8 or q.dim() != 2 or q.shape[1] % 64 or not q.is_contiguous():
+        raise ValueError(f"dense: q must be a contiguous float8_e4m3fn [N, K] with K % 64 == 0, "
+                         f"got {q.dtype} {tuple(q.shape)}, strides {tuple(q.stride())}")
+    if (scale.dtype != torch.float32 or tuple(scale.shape) != (q.shape[0], q.shape[1] // 64)
+            or not scale.is_contiguous() or scale.device != q.device):
+        raise ValueError(f"dense: scale must be a contiguous fp32 "
+                         f"{[q.shape[0], q.shape[1] // 64]} on q's device, got {scale.dtype} "
+                         f"{tuple(scale.shape)}")
+    return q, scale
+
+
+def weight_dequantize(w, dtype=torch.float32):
+    """The matrix an FP8 weight pair stands for, exactly (see :func:`kv_dequantize`)."""
+    q, scale = check_weight_pair(w)
+    N, K = q.shape
+    return kv_dequantize(q.view(N, K // 64, 64), scale, dtype).view(N, K)
+
+
 def check_kv_dtypes(name, qkv, k_cache, v_cache, k_scale, v_scale):
     """The one rule for the cache's data type, shared by the three cache ops and both backends ->
     True for an FP8 cache.  ``float8_e4m3fn`` caches need both fp32 [B, heads, C] scales; any

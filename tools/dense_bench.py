@@ -14,6 +14,11 @@ so no arm casts them.  One JSON line per (GEMM, M): microseconds of each arm and
 kernel's GB/s over the weight bytes as a share of the 8 TB/s peak.  ``--splits`` adds the skinny
 kernel at each forced K split (through the binding) to the line.
 
+``--w8`` adds the arm ``skinny_w8``: the same calls on the FP8 pairs of the ring's weights
+(``ops.weight_quantize_fp8``, csrc/kernels/dense_skinny_f8.hip).  The ring is then sized by the
+FP8 bytes, half the bf16 bytes, so that both arms' weights exceed the last-level cache; the line
+gains the arm's GB/s over ITS weight bytes (bytes and scales) and ``w8_speedup``, skinny / skinny_w8.
+
     python tools/dense_bench.py --tail [--ms 1,8,16,64]
 
 ``--tail`` times a whole layer from the attention output on instead, through the ops, the same
@@ -52,9 +57,13 @@ def _med(v):
 def bench(name, N, K, extra, M, a, gen):
     pair = name == "ffn_pair"
     wbytes = 2 * N * K + (2 * extra * N if pair else 0)
-    ring = min(512, -(-RING_BYTES // wbytes))
+    w8bytes = wbytes // 2 + wbytes // 32                   # a byte per weight, 4 per 64 of them
+    ring = min(1024 if a.w8 else 512, -(-RING_BYTES // (w8bytes if a.w8 else wbytes)))
     ws = [_weight(N, K, gen) for _ in range(ring)]
     w2 = [_weight(extra, N, gen) for _ in range(ring)] if pair else None
+    if a.w8:
+        qs = [ops.weight_quantize_fp8(w) for w in ws]
+        q2 = [ops.weight_quantize_fp8(w) for w in w2] if pair else None
     b = torch.randn(N, device="cuda", generator=gen) if (pair or extra) else None
     x = torch.randn(M, K, device="cuda", generator=gen).bfloat16()
     if pair:
@@ -67,6 +76,10 @@ def bench(name, N, K, extra, M, a, gen):
             if s <= K // 64:
                 arms[f"skinny_splits{s}"] = (
                     lambda i, s=s: native._dense_skinny(x, ws[i], b, splits=s))
+    if a.w8 and pair:
+        arms["skinny_w8"] = lambda i: ops.dense_gelu_dense(x, qs[i], b, q2[i], impl="skinny")
+    elif a.w8:
+        arms["skinny_w8"] = lambda i: ops.dense(x, qs[i], b, impl="skinny")
     us = {k: [] for k in arms}
     with torch.no_grad():
         for r in range(a.rounds + 1):                          # round 0 warms every arm up
@@ -80,6 +93,8 @@ def bench(name, N, K, extra, M, a, gen):
                 if r:
                     us[k].append(e0.elapsed_time(e1) * 1e3 / a.iters)
         same = float((arms["parent"](0).float() - arms["skinny"](0).float()).abs().max())
+        if a.w8:
+            same8 = float((arms["skinny"](0).float() - arms["skinny_w8"](0).float()).abs().max())
     rec = {"probe": "dense_skinny", "gemm": name, "M": M, "N": N, "K": K, "ring": ring,
            "ring_MB": round(ring * wbytes / 2 ** 20), "max_abs_diff": round(same, 4),
            "auto_splits": native._K.dense_skinny_splits(M, N, K)}
@@ -90,6 +105,12 @@ def bench(name, N, K, extra, M, a, gen):
     rec["skinny_weight_GBs"] = round(gbs)
     rec["skinny_share_of_peak"] = round(gbs / PEAK_GBS, 3)
     rec["speedup"] = round(_med(us["parent"]) / _med(us["skinny"]), 2)
+    if a.w8:
+        gbs = w8bytes / (_med(us["skinny_w8"]) * 1e-6) / 1e9
+        rec["skinny_w8_weight_GBs"] = round(gbs)
+        rec["skinny_w8_share_of_peak"] = round(gbs / PEAK_GBS, 3)
+        rec["w8_speedup"] = round(_med(us["skinny"]) / _med(us["skinny_w8"]), 2)
+        rec["w8_max_abs_diff"] = round(same8, 4)
     print(json.dumps(rec), flush=True)
 
 
@@ -148,6 +169,8 @@ def main():
     ap.add_argument("--ms", default="1,8,16,64")
     ap.add_argument("--splits", default="", help="forced K splits to time as well, e.g. 1,2,4")
     ap.add_argument("--gemms", default=",".join(g[0] for g in GEMMS))
+    ap.add_argument("--w8", action="store_true",
+                    help="add the arm 'skinny_w8': the skinny kernel on FP8 weight pairs")
     ap.add_argument("--tail", action="store_true",
                     help="time a whole layer tail instead: 'skinny' against 'skinny_ln'")
     a = ap.parse_args()

@@ -29,7 +29,9 @@ against plain ``generate`` instead of the recompute arm; ``--shadows`` first giv
 bf16 shadows an optimizer build leaves, so neither arm casts its fp32 masters on every call.
 ``--decode_gemm skinny_ln`` times ``generate(decode_gemm="skinny_ln")`` (the layers' LayerNorms
 deferred into the skinny kernel) against ``generate(decode_gemm="skinny")``, which then takes the
-``kv_cache_*`` fields of the line.
+``kv_cache_*`` fields of the line.  ``--decode_gemm skinny_w8`` / ``skinny_ln_w8`` time the FP8-weight
+form (csrc/kernels/dense_skinny_f8.hip; every call quantises the weights first, as ``generate``
+does) against ``skinny`` / ``skinny_ln`` in the same way.
 """
 import argparse
 import json
@@ -165,10 +167,14 @@ def main():
     ap.add_argument("--kv_dtype", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: generate(kv_dtype='fp8') against the bf16 cache instead of the "
                          "recompute arm; same_tokens is then the share of greedy tokens that agree")
-    ap.add_argument("--decode_gemm", choices=["default", "skinny", "skinny_ln"], default="default",
+    ap.add_argument("--decode_gemm",
+                    choices=["default", "skinny", "skinny_ln", "skinny_w8", "skinny_ln_w8"],
+                    default="default",
                     help="skinny: generate(decode_gemm='skinny') against the default GEMMs instead "
                          "of the recompute arm; skinny_ln: generate(decode_gemm='skinny_ln') "
-                         "against the 'skinny' arm (kv_cache_* in the output is then that arm)")
+                         "against the 'skinny' arm (kv_cache_* in the output is then that arm); "
+                         "skinny_w8 / skinny_ln_w8: the FP8-weight form against 'skinny' / "
+                         "'skinny_ln' (same_tokens is then the share of greedy tokens that agree)")
     ap.add_argument("--shadows", action="store_true",
                     help="give the weights bf16 shadows as an optimizer build does, so no GEMM of "
                          "either arm casts its fp32 master per call")
@@ -202,6 +208,11 @@ def main():
         arms["kv_cache"] = lambda: model.generate(prompt, lens, a.new, decode_gemm="skinny")
         arms["recompute"] = lambda: model.generate(prompt, lens, a.new, decode_gemm="skinny_ln")
         second = "kv_cache_skinny_ln"
+    if a.decode_gemm.endswith("_w8"):                 # against the same GEMMs on bf16 weights
+        base = a.decode_gemm[:-3]
+        arms["kv_cache"] = lambda: model.generate(prompt, lens, a.new, decode_gemm=base)
+        arms["recompute"] = lambda: model.generate(prompt, lens, a.new, decode_gemm=a.decode_gemm)
+        second = "kv_cache_" + a.decode_gemm
     times = {k: [] for k in arms}
     outs = {}
     for r in range(a.rounds + 1):                     # round 0 warms both arms up
